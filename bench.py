@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- views/sec of the Fast3R single-forward-pass inference hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--views V] [--dtype fp16|bf16] [--precision fast|high] [--no-alt] [--fusion-only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--views V] [--dtype fp16|bf16] [--precision fast|high] [--fusion-only]
+                    [--dump-outputs DIR] [--full [--no-alt] [--no-hot] ...]
+
+A plain run sets up, runs W warm-up and K timed steps, and prints the headline line (`value`, `ms_per_step`, `roofline` of the timed
+fusion-attention launches).  Everything else the line can carry -- the other operand format, the hot weights, n100 / fusion_only_n20 /
+robust_tier, parity, the inference() timing, the per-family roofline, the committed PMC figures and the CPU baseline -- runs only with
+--full (the --no-* switches then leave single parts out).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 
 Workload (default): BASELINE.json's headline configuration -- Fast3R ViT-Large encoder + ViT-Large fusion decoder + both
 DPT heads, V = 320 synthetic views of 512x512, ONE forward pass = one step -- the configuration the metric
@@ -20,7 +26,7 @@ heads, DESIGN.md section 3 (Precision modes)) -- the format whose pointmaps are 
 as on the default-init protocol.  `alt_format` in the same line is the same workload measured right after in bf16 / "fast" (one
 16-bit number per operand: the round-1 headline format, faster, 2e-2 on the stress fixture); --no-alt skips it.
 
-Extra objects in the JSON line:
+Extra objects in the JSON line (all but `roofline` without `traffic` / `reference_pmc` / `others` need --full):
   roofline     fusion-attention kernel (the dominant kernel: 94.7 % of all FLOPs at N=320): algorithmic FLOPs per launch
                4*Tq*Tk*64*heads divided by the average launch duration measured live with events on the launch stream,
                against the dense 16-bit MFMA peak of 2.5 PFLOP/s (MI355X_MICROARCH.md).  `e2e` = all algorithmic FLOPs of the
@@ -96,7 +102,16 @@ def parse(argv=None):
     ap.add_argument("--reserve-cus", type=int, default=32,
                     help="view-sharded runs (and --emulate-rank): CUs the persistent local-shard attention launch leaves to the kernels of the K / V^T "
                          "exchange (f3r_attn_args.reserve_cus; profiles/r06_exchange_under_persistent_attention.json)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra measurement and check of the line (alt_format, hot_weights, robust_tier, n100, fusion_only_n20, parity, "
+                         "inference, roofline.others / traffic / reference_pmc, cpu_baseline); a plain run times the headline workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32; above 64 MB in all a fixed, seeded sample)")
+    args = ap.parse_args(argv)
+    if not args.full:   # the extras below are --full only; with --full the --no-* switches leave single ones out
+        for k in ("no_alt", "no_hot", "no_extra_configs", "no_cpu_baseline", "no_families", "no_parity", "no_inference"):
+            setattr(args, k, True)
+    return args
 
 
 class Watchdog:
@@ -502,7 +517,8 @@ def main():
     from fast3r_amd.synthetic import make_views, synth_state_dict, vit_large_args
 
     enc, dec, head = vit_large_args(max_image_idx=max(1000, V))
-    shapes = {k: tuple(v.shape) for k, v in Fast3R(enc, dec, head).state_dict().items()}
+    with torch.device("meta"):   # shapes only (the real init of 647 M parameters costs seconds of CPU for nothing)
+        shapes = {k: tuple(v.shape) for k, v in Fast3R(enc, dec, head).state_dict().items()}
     sds = {}
 
     def state_dict_for(weights):
@@ -522,9 +538,10 @@ def main():
     views = [v if v is not None else placeholder for v in views]  # never read outside [lo, hi)
 
     def measure(dtype_name, precision, steps=None, warmup=None, weights=None, parity_exact=False, time_inference=False, n_views=None, fusion_only=None,
-                parity=True, families=False):
+                parity=True, families=False, dump_dir=None):
         """W warm-up + K timed steps of one operand format -> the measured fields of the JSON line.  n_views / fusion_only: the bounded extra
-        objects of the default line (the first n_views of the resident views; BASELINE configs[1] / [2]) -- single-GPU runs only."""
+        objects of the default line (the first n_views of the resident views; BASELINE configs[1] / [2]) -- single-GPU runs only.  dump_dir:
+        write what the last timed step returned there (rank 0)."""
         V = args.views if n_views is None else n_views
         fo = args.fusion_only if fusion_only is None else fusion_only
         vlist = views if V == args.views else views[:V]
@@ -583,6 +600,8 @@ def main():
             # f3r_attn_args.dbg_counters (ABI 330): u32 entries, u32 waves, u64 tiles, u64 shader-clock cycles, u64 constant-clock ticks
             counters = [u32[0], u32[1], u32[2] | (u32[3] << 32), u32[4] | (u32[5] << 32), u32[6] | (u32[7] << 32)]
             counters.append([[u32[8 + 6 * x + 2 * i] | (u32[9 + 6 * x + 2 * i] << 32) for i in range(3)] for x in range(8)])  # per XCD: cycles, ticks, waves
+            if dump_dir is not None and rank == 0:
+                dump_outputs(last_out, dump_dir)
         dt = max_over_ranks(dt)
         exch = None
         if distributed:
@@ -712,7 +731,8 @@ def main():
         workload = f"Fast3R ViT-L 512x512 end-to-end single forward pass (encoder + fusion decoder + 2 DPT heads), N={V} views"
 
     try:
-        main_res = measure(args.dtype, args.precision, parity_exact=args.parity_exact, time_inference=not args.no_inference, families=not args.no_families)
+        main_res = measure(args.dtype, args.precision, parity_exact=args.parity_exact, time_inference=not args.no_inference, families=not args.no_families,
+                           dump_dir=args.dump_outputs)
     except Exception as exc:  # noqa: BLE001  -- a failed run still ends with ONE line on rank 0's stdout, and a non-zero exit code
         import traceback
         traceback.print_exc(file=sys.stderr)
@@ -804,8 +824,10 @@ def main():
                        "head_tail_fused": not args.no_fused_tail},
             # `live` = this run's own clock / utilisation / power record; `traffic` and `reference_pmc` are read from committed rocprofv3
             # PMC passes of other runs (they carry their source file) and are there to be compared with `live`, not to stand in for it
-            "roofline": dict(main_res["roofline"], traffic=load_traffic(V, world), reference_pmc=load_pmc(main_res["dtype"])),
+            "roofline": dict(main_res["roofline"]),
         }
+        if args.full:
+            out["roofline"].update(traffic=load_traffic(V, world), reference_pmc=load_pmc(main_res["dtype"]))
         out.update(extra)
         if robust_extra is not None:
             out["robust_tier"] = robust_extra
@@ -1061,6 +1083,53 @@ def cpu_baseline(sd, enc, dec, head, n_views):
             "sample": f"same model (ViT-L/ViT-L/2 DPT), {n_views} views of 512x512, fp32, SDPA attention; 1 warm-up + 2 timed forwards "
                       f"({', '.join('%.1f s' % t for t in times)}; best reported) at {best} threads of {nproc}",
             "thread_sweep_s_per_view": {str(k): round(v, 2) for k, v in sweep.items()}}
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: float32 payload of all files together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: what one step returned, as directory/<name>.npy in float32.  The forward's per-view dicts become one array per output
+    name over all views (view-major: (V, B, H, W[, 3]) when the views share a shape); the fusion-only step's tokens are `tokens`.  If everything
+    together is larger than DUMP_BUDGET_BYTES, each name keeps a share of the budget proportional to its size: elements of its flattened,
+    view-major array at sorted indices drawn from a generator seeded with the name's position, the same from run to run."""
+    import numpy as np
+    import torch
+    if torch.is_tensor(out):
+        arrays = {"tokens": [out]}
+    elif isinstance(out, (list, tuple)) and all(torch.is_tensor(t) for t in out):
+        arrays = {f"tokens_{i}": [t] for i, t in enumerate(out)}
+    else:
+        arrays = {}
+        for o in out:
+            for k, v in o.items():
+                arrays.setdefault(k, []).append(v)
+    os.makedirs(directory, exist_ok=True)
+    total = sum(t.numel() for ts in arrays.values() for t in ts)
+    budget = DUMP_BUDGET_BYTES // 4
+    for seed, name in enumerate(sorted(arrays)):
+        ts = arrays[name]
+        n = sum(t.numel() for t in ts)
+        if total <= budget:
+            if all(t.shape == ts[0].shape for t in ts):
+                a = torch.stack([t.detach().float().cpu() for t in ts]).numpy()
+            else:
+                a = torch.cat([t.detach().float().cpu().reshape(-1) for t in ts]).numpy()
+        else:
+            k = max(1, budget * n // total)
+            idx, _ = torch.sort(torch.randint(n, (k,), generator=torch.Generator().manual_seed(seed)))
+            ends = torch.tensor([t.numel() for t in ts]).cumsum(0)
+            cut = torch.searchsorted(idx, ends).tolist()   # idx[cut[i-1]:cut[i]] fall into ts[i]
+            pieces = []
+            for i, t in enumerate(ts):
+                sel = idx[(cut[i - 1] if i else 0):cut[i]]
+                if sel.numel():
+                    sel = sel - (int(ends[i]) - t.numel())
+                    pieces.append(t.detach().reshape(-1)[sel.to(t.device)].float().cpu())
+            a = torch.cat(pieces).numpy()
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print(f"[bench] outputs of the last timed step -> {directory}: " + ", ".join(sorted(arrays)) +
+          ("" if total <= budget else f" (seeded sample of {budget} of {total} elements)"), file=sys.stderr, flush=True)
 
 
 if __name__ == "__main__":

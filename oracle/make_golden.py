@@ -5,7 +5,8 @@ The reference ships no golden vectors, so these are "outpu
 here": each fixture stores the constructor args, the input recipe (seeds; inputs and weights are regenerated
 bit-identically by fast3r_amd/synthetic.py), the image ids the reference drew, and the reference outputs.
 Weights are NOT stored (the DPT heads alone are 2 x 20.5 M parameters): both sides rebuild them from
-synth_state_dict(shapes, seed).
+synth_state_dict(shapes, seed).  Two more fixtures hold what the host-side tests compare with: reference_tiny_model (the reference's
+state_dict layout, image-id table and attention scales) and reference_oracle_case (its outputs on a model of another width).
 """
 import copy
 import os
@@ -16,6 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fast3r_amd.synthetic import make_views, synth_state_dict, tiny_args  # noqa: E402
+from oracle import fixture_io  # noqa: E402
 from oracle.ref_loader import load_reference  # noqa: E402
 
 OUT_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
@@ -102,17 +104,66 @@ def main(only=None, check=False):
                    torch_version=torch.__version__)
         path = os.path.join(OUT_DIR, name + ".pt")
         if check:
-            old = torch.load(path, weights_only=False)
+            old = fixture_io.load(path)
             same = old["state_shapes"] == shp and all(torch.equal(a[k], b[k]) for a, b in zip(old["preds"], fix["preds"]) for k in b) and \
                 (old["image_ids"] is None) == (ids is None) and (ids is None or torch.equal(old["image_ids"], ids))
             print(name, "bit-identical to the committed fixture" if same else "DIFFERS from the committed fixture")
             if not same:
                 bad.append(name)
             continue
-        torch.save(fix, path)
+        path = fixture_io.save(fix, path)
         print(name, os.path.getsize(path) // 1024, "KB", {k: tuple(v.shape) for k, v in preds[0].items()})
+    for name, make in (("reference_tiny_model", _reference_tiny_model), ("reference_oracle_case", _reference_oracle_case)):
+        if only and name not in only:
+            continue
+        fix = make(Fast3R, inference)
+        path = os.path.join(OUT_DIR, name + ".pt")
+        if check:
+            old = fixture_io.load(path)
+            same = set(old) == set(fix) and all(_same(old[k], v) for k, v in fix.items() if k != "torch_version")
+            print(name, "bit-identical to the committed fixture" if same else "DIFFERS from the committed fixture")
+            if not same:
+                bad.append(name)
+            continue
+        path = fixture_io.save(fix, path)
+        print(name, os.path.getsize(path) // 1024, "KB")
     if bad:
         sys.exit(1)
+
+
+def _same(a, b):
+    if torch.is_tensor(b):
+        return torch.is_tensor(a) and a.shape == b.shape and torch.equal(a, b)
+    if isinstance(b, dict):
+        return isinstance(a, dict) and set(a) == set(b) and all(_same(a[k], b[k]) for k in b)
+    if isinstance(b, (list, tuple)):
+        return isinstance(a, (list, tuple)) and len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return a == b
+
+
+def _reference_tiny_model(Fast3R, inference):
+    """What tests/test_host_logic.py::test_strict_load_of_reference_state_dict checks the product against: the reference's own state_dict
+    layout for tiny_args(), its image-id table and its two attention scales (the weights themselves are the reference's random init: not kept)."""
+    enc, dec, head = tiny_args()
+    ref = Fast3R(copy.deepcopy(enc), copy.deepcopy(dec), copy.deepcopy(head))
+    blk = ref.decoder.dec_blocks[0].attn
+    return dict(state_shapes={k: tuple(v.shape) for k, v in ref.state_dict().items()}, image_idx_emb=ref.decoder.image_idx_emb.clone(),
+                attn_bias_scale=float(blk.attn_bias_scale), scale=float(blk.scale), torch_version=str(torch.__version__))
+
+
+ORACLE_CASE = dict(tiny_kwargs=dict(embed_dim=192, num_heads=3, enc_depth=2, dec_depth=10), weight_seed=11, views=(4, 48, 80), rng_seed=3)
+
+
+def _reference_oracle_case(Fast3R, inference):
+    """What tests/test_oracle.py::test_oracle_matches_live_reference compares the oracle with: the reference's outputs on a model of another
+    width (192 / 3 heads, 10 fusion layers) and views of 48 x 80, weights synth_state_dict(shapes, 11), views make_views(4, 48, 80), seed 3."""
+    c = ORACLE_CASE
+    enc, dec, head = tiny_args(**c["tiny_kwargs"])
+    m = Fast3R(copy.deepcopy(enc), copy.deepcopy(dec), copy.deepcopy(head)).eval()
+    m.load_state_dict(synth_state_dict({k: v.shape for k, v in m.state_dict().items()}, seed=c["weight_seed"]), strict=True)
+    torch.manual_seed(c["rng_seed"])
+    preds = inference(make_views(*c["views"]), m, torch.device("cpu"), dtype="32", verbose=False)["preds"]
+    return dict(c, preds=[{k: v.clone() for k, v in p.items()} for p in preds], torch_version=str(torch.__version__))
 
 
 if __name__ == "__main__":

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from oracle import cv2_stub, ref_loader  # noqa: E402
+from oracle import cv2_stub, fixture_io, ref_loader  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "pose_cases.pt")
 
@@ -98,15 +98,15 @@ def main():
         err = max(float(np.abs(out["first_view_from_global_head"]["poses"][b][v] - gt[v][b].numpy()).max()) for v in range(V) for b in range(B))
         print(sc, "max |pose - gt| =", f"{err:.2e}", "focals", [round(f, 2) for f in out["individual"]["focals"][0]])
     if "--check" in sys.argv:  # compare with the committed fixture instead of writing it
-        old = torch.load(OUT, weights_only=False)["cases"]
+        old = fixture_io.load(OUT)["cases"]
         same = len(old) == len(cases) and all(
             all(torch.equal(pa[k], pb[k]) for pa, pb in zip(a["preds"], b["preds"]) for k in pb) and
             all(np.array_equal(x, y) for m in a["reference"] for sa, sb in zip(a["reference"][m]["poses"], b["reference"][m]["poses"]) for x, y in zip(sa, sb)) and
             all(a["reference"][m]["focals"] == b["reference"][m]["focals"] for m in a["reference"]) for a, b in zip(old, cases))
         print("pose fixture:", "bit-identical to the committed one" if same else "DIFFERS from the committed one")
         sys.exit(0 if same else 1)
-    torch.save(dict(cases=cases, torch_version=torch.__version__), OUT)
-    print("wrote", OUT, os.path.getsize(OUT) // 1024, "KB")
+    out = fixture_io.save(dict(cases=cases, torch_version=torch.__version__), OUT)
+    print("wrote", out, os.path.getsize(out) // 1024, "KB")
 
 
 if __name__ == "__main__":

@@ -11,7 +11,8 @@ GOLDEN_CASES = ["tiny_3x64", "tiny_mixed", "tiny_b2_seqids", "tiny_oddgrid", "ti
 
 
 def load_golden(name):
-    return torch.load(os.path.join(GOLDEN_DIR, name + ".pt"), weights_only=False)
+    from oracle import fixture_io
+    return fixture_io.load(os.path.join(GOLDEN_DIR, name + ".pt"))
 
 
 def golden_views(fix, seed=1000):

@@ -1,5 +1,5 @@
 """The oracle (oracle/fast3r_oracle.py) against (a) the committed reference outputs under tests/golden/ -- runs
-everywhere -- and (b) the live reference, wherever /root/reference exists (the build container)."""
+everywhere -- and (b) the live reference, wherever its checkout exists (oracle/ref_loader.py)."""
 import copy
 import warnings
 
@@ -61,24 +61,32 @@ def test_postprocess_invariants():
     assert (r["conf"] >= 1).all()
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference checkout only exists in the build container")
 def test_oracle_matches_live_reference():
-    from oracle.ref_loader import load_reference
+    """A model of another width (192 / 3 heads, 10 fusion layers) on 48 x 80 views: the oracle against the reference's outputs recorded in
+    tests/golden/reference_oracle_case.pt (oracle/make_golden.py) everywhere, and against the live reference where its checkout exists."""
+    from fast3r_amd import Fast3R as Fast3RProduct
     from fast3r_amd.synthetic import make_views, synth_state_dict, tiny_args
-    warnings.filterwarnings("ignore")
-    Fast3R, inference = load_reference()
+    fix = load_golden("reference_oracle_case")
+    assert (fix["tiny_kwargs"], fix["weight_seed"], tuple(fix["views"]), fix["rng_seed"]) == (dict(embed_dim=192, num_heads=3, enc_depth=2, dec_depth=10), 11, (4, 48, 80), 3)
     enc, dec, head = tiny_args(embed_dim=192, num_heads=3, enc_depth=2, dec_depth=10)
-    m = Fast3R(copy.deepcopy(enc), copy.deepcopy(dec), copy.deepcopy(head)).eval()
-    sd = synth_state_dict({k: v.shape for k, v in m.state_dict().items()}, seed=11)
-    m.load_state_dict(sd, strict=True)
+    sd = synth_state_dict({k: tuple(v.shape) for k, v in Fast3RProduct(enc, dec, head).state_dict().items()}, seed=11)
     views = make_views(4, 48, 80)
-    torch.manual_seed(3)
-    ref = inference(copy.deepcopy(views), m, torch.device("cpu"), dtype="32", verbose=False)["preds"]
+    refs = [fix["preds"]]
+    if reference_available():
+        from oracle.ref_loader import load_reference
+        warnings.filterwarnings("ignore")
+        Fast3R, inference = load_reference()
+        m = Fast3R(copy.deepcopy(enc), copy.deepcopy(dec), copy.deepcopy(head)).eval()
+        m.load_state_dict(sd, strict=True)
+        torch.manual_seed(3)
+        refs.append(inference(copy.deepcopy(views), m, torch.device("cpu"), dtype="32", verbose=False)["preds"])
     torch.manual_seed(3)
     ora = O.forward(views, sd, enc, dec, head)
-    for o, g in zip(ora, ref):
-        for k in g:
-            assert rel_l2(o[k], g[k]) < TOL, (k, rel_l2(o[k], g[k]))
+    for ref in refs:
+        assert len(ref) == len(ora)
+        for o, g in zip(ora, ref):
+            for k in g:
+                assert rel_l2(o[k], g[k]) < TOL, (k, rel_l2(o[k], g[k]))
 
 
 # ------------------------------------------------------------------------------------------------ fixtures are what the reference returns

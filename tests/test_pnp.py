@@ -242,7 +242,8 @@ def test_hip_estimate_camera_poses_api(built_lib):
 # the product's algorithm.
 def _pose_cases():
     import os
-    return torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_cases.pt"), weights_only=False)["cases"]
+    from oracle import fixture_io
+    return fixture_io.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_cases.pt"))["cases"]
 
 
 def test_reference_wrapper_fixture_recovers_the_known_cameras():

@@ -3,7 +3,8 @@ import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fast3r_amd import MultiViewDUSt3RLitModule
-cases = torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "pose_cases.pt"), weights_only=False)["cases"]
+from oracle import fixture_io
+cases = fixture_io.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "pose_cases.pt"))["cases"]
 for c in cases:
     V, B = c["scene"][1], c["scene"][2]
     preds = [{k: v.cuda() for k, v in p.items()} for p in c["preds"]]

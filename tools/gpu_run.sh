@@ -168,7 +168,7 @@ json.dump(out, open(f"{d}/conv_pmc.json", "w"), indent=1)
 PY
       find $d/pmc -name "*kernel_trace.csv" -delete ;;
     benchquick) # the default line, short: live roofline + power sampler + n100 / fusion_only_n20 objects (no alt format, no CPU baseline, no hot weights)
-      timeout 900 python bench.py --steps ${BENCH_STEPS:-1} --warmup 1 --no-alt --no-cpu-baseline --no-hot ${BENCH_EXTRA:-} > $d/bench_quick.json 2> $d/err.log; tail -c 5000 $d/bench_quick.json; tail -5 $d/err.log ;;
+      timeout 900 python bench.py --full --steps ${BENCH_STEPS:-1} --warmup 1 --no-alt --no-cpu-baseline --no-hot ${BENCH_EXTRA:-} > $d/bench_quick.json 2> $d/err.log; tail -c 5000 $d/bench_quick.json; tail -5 $d/err.log ;;
     attnasm)    # the generated attention kernels (the clock bracket of round 5 touched prologue + epilogue)
       timeout 900 python -m pytest tests/test_attn_asm_gpu.py -q -x -p no:cacheprovider 2>&1 | tail -40 > $d/pytest.log; tail -12 $d/pytest.log ;;
     gemmf8)     # parity of the fp8-low-plane GEMM + LayerNorm rows, then W2 vs W2F8 timings of the transformer's linear roles
@@ -176,7 +176,7 @@ PY
       timeout 600 python tools/kernel_bench.py --what gemmf8 --views ${F8_VIEWS:-320,100} > $d/gemm_w2_vs_w2f8.jsonl 2> $d/err.log; cat $d/gemm_w2_vs_w2f8.jsonl | cut -c1-300; tail -3 $d/err.log ;;
     f8model)    # the model with Fast3R.low_plane = "fp8": kernel chain test, parity at ViT-L depth (N = 3, 8 vs the CPU oracle; N = 100 vs the exact mode), then the bench A/B
       timeout 1500 python -m pytest tests/test_gemm_asm_gpu.py tests/test_depth_parity_gpu.py -q -s -p no:cacheprovider -k "fp8 or f8 or stress_weights_vs_cpu_oracle or n100_stress" > $d/pytest_full.log 2>&1; grep -E "\[parity\]|\[w2f8|passed|failed|^E " $d/pytest_full.log | sed 's/^[.sF]*//' | cut -c1-300 > $d/parity_lines.txt; cat $d/parity_lines.txt; tail -60 $d/pytest_full.log > $d/pytest.log; rm -f $d/pytest_full.log
-      for lpn in fp8 fp16; do timeout 600 python bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline --no-hot --no-inference --low-plane $lpn > $d/bench_$lpn.json 2> $d/err_$lpn.log; python - $d/bench_$lpn.json <<'PY'
+      for lpn in fp8 fp16; do timeout 600 python bench.py --full --steps 2 --warmup 1 --no-alt --no-cpu-baseline --no-hot --no-inference --low-plane $lpn > $d/bench_$lpn.json 2> $d/err_$lpn.log; python - $d/bench_$lpn.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 r = lambda x, n=2: None if x is None else round(x, n)
@@ -219,7 +219,7 @@ PY
     qkvasm)     # QKV on the hand-scheduled kernel: RoPE-2D epilogue + fp8 low plane (tests), then the model parity at depth and the bench A/B vs low_plane fp16
       timeout 900 python -m pytest tests/test_gemm_asm_gpu.py -q -x -s -p no:cacheprovider -k "qkv" 2>&1 | tail -30 > $d/pytest.log; grep -E "passed|failed|Error|assert|^E " $d/pytest.log | tail -12
       timeout 900 python -m pytest tests/test_depth_parity_gpu.py tests/test_e2e_gpu.py -q -s -p no:cacheprovider -k "stress_weights_vs_cpu_oracle or n100_stress or vit_large_512_n8 or sharded_forward_equals_unsharded" > $d/pytest_full.log 2>&1; grep -E "\[parity\]|passed|failed|^E " $d/pytest_full.log | sed 's/^[.sF]*//' | cut -c1-260 > $d/parity_lines.txt; cat $d/parity_lines.txt; tail -40 $d/pytest_full.log > $d/pytest2.log; rm -f $d/pytest_full.log
-      timeout 600 python bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline --no-hot --no-inference > $d/bench_fp8.json 2> $d/err.log; python - $d/bench_fp8.json <<'PY'
+      timeout 600 python bench.py --full --steps 2 --warmup 1 --no-alt --no-cpu-baseline --no-hot --no-inference > $d/bench_fp8.json 2> $d/err.log; python - $d/bench_fp8.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 r = lambda x, n=2: None if x is None else round(x, n)
@@ -237,18 +237,18 @@ PY
       timeout 2400 python -m pytest tests -m gpu -q -rA -s --durations=70 -p no:cacheprovider > $d/pytest_full.log 2>&1; grep -E "^\[parity\]|^\[exact" $d/pytest_full.log > $d/parity_lines.txt; sed -n '/slowest/,/short test summary/p' $d/pytest_full.log > $d/durations.txt; grep -E "passed|failed" $d/pytest_full.log | tail -3; grep -E "^(FAILED|ERROR)" $d/pytest_full.log | head -20; sed -n '/=== FAILURES ===/,/=== short test summary/p' $d/pytest_full.log | tail -400 > $d/failures.txt; grep -E "\[parity\]|\[exact" $d/pytest_full.log | sed 's/^[.sF]*//' > $d/parity_lines.txt; tail -150 $d/pytest_full.log > $d/pytest.log; rm -f $d/pytest_full.log
       timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $d/smoke.log 2>&1; tail -2 $d/smoke.log ;;
     hot100)     # N = 100 on the hot weights: views/s, attention frac, re-base rate, parity vs the exact mode -- and the default weights beside it
-      timeout 900 python bench.py --views 100 --weights hot --steps 3 --warmup 1 --no-alt --no-cpu-baseline --parity-exact > $d/bench_n100_hot.json 2> $d/hot.err; tail -c 1500 $d/bench_n100_hot.json
-      timeout 900 python bench.py --views 100 --steps 3 --warmup 1 --no-alt --no-cpu-baseline --no-hot > $d/bench_n100_default.json 2> $d/def.err; tail -c 600 $d/bench_n100_default.json ;;
+      timeout 900 python bench.py --full --views 100 --weights hot --steps 3 --warmup 1 --no-alt --no-cpu-baseline --parity-exact > $d/bench_n100_hot.json 2> $d/hot.err; tail -c 1500 $d/bench_n100_hot.json
+      timeout 900 python bench.py --full --views 100 --steps 3 --warmup 1 --no-alt --no-cpu-baseline --no-hot > $d/bench_n100_default.json 2> $d/def.err; tail -c 600 $d/bench_n100_default.json ;;
     bench320)   # the default line (N = 320, fp16 / high) with its hot-weights object, short
-      timeout 1200 python bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline > $d/bench_n320.json 2> $d/err.log; tail -c 2500 $d/bench_n320.json ;;
-    benchfull)  # what the driver runs
-      timeout 1500 python bench.py > $d/bench_default.json 2> $d/err.log; tail -c 3000 $d/bench_default.json ;;
+      timeout 1200 python bench.py --full --steps 2 --warmup 1 --no-alt --no-cpu-baseline > $d/bench_n320.json 2> $d/err.log; tail -c 2500 $d/bench_n320.json ;;
+    benchfull)  # the full line: every extra measurement and check (--full)
+      timeout 1500 python bench.py --full > $d/bench_default.json 2> $d/err.log; tail -c 3000 $d/bench_default.json ;;
     gemmref)    # the transformer GEMM roles at N = 320 beside the vendor library
       timeout 900 python tools/kernel_bench.py --what gemmref --views ${GEMM_VIEWS:-320} --sels ${GEMM_SELS:-2} > $d/gemmref.jsonl 2> $d/err.log; cat $d/gemmref.jsonl | cut -c1-260 ;;
     gemmpmc)    # rocprofv3 PMC over the GEMM micro-benchmark
       timeout 900 bash tools/pmc_gemm.sh > $d/pmc.log 2>&1; tail -30 $d/pmc.log; cp gpurun_out/pmcg/gemm_pmc.json $d/ 2>/dev/null ;;
     prof320)    # rocprofv3 kernel stats of the default bench command (3 forwards)
-      ( cd /tmp; rocprofv3 --kernel-trace --stats -d $OLDPWD/$d/prof --output-format csv -- python $OLDPWD/bench.py --steps 2 --warmup 1 --no-alt --no-cpu-baseline --no-hot --no-parity --no-inference --no-extra-configs > $OLDPWD/$d/bench.json 2> $OLDPWD/$d/err.log )
+      ( cd /tmp; rocprofv3 --kernel-trace --stats -d $OLDPWD/$d/prof --output-format csv -- python $OLDPWD/bench.py --full --steps 2 --warmup 1 --no-alt --no-cpu-baseline --no-hot --no-parity --no-inference --no-extra-configs > $OLDPWD/$d/bench.json 2> $OLDPWD/$d/err.log )
       f=$(ls $d/prof/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $d/kernel_stats.csv && head -12 $d/kernel_stats.csv | cut -c1-200
       find $d/prof -name "*kernel_trace.csv" -delete ;;
     *) echo "unknown step $step" ;;
