@@ -7,3 +7,4 @@ from .align import align_local_pts3d_to_global  # noqa: F401
 from .focal import estimate_focal, estimate_focals  # noqa: F401
 from .pose import estimate_camera_poses, estimate_poses  # noqa: F401
 from .image import load_images  # noqa: F401
+from .recon_metric import accuracy, completion, completion_ratio, estimate_normals, nearest_neighbors  # noqa: F401

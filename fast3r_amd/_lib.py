@@ -106,6 +106,16 @@ SYMBOLS = {
     "f3r_focal_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "f3r_estimate_focal": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           _c_f32, _c_f32, _c_f32, ctypes.c_int, _c_f32, _c_f32, _c_vp]),
+    "f3r_nn_index_bytes": (ctypes.c_size_t, [_c_i64]),
+    "f3r_nn_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "f3r_nn_build": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, ctypes.c_size_t, _c_vp, ctypes.c_size_t, _c_vp]),
+    "f3r_nn_query": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
+    "f3r_estimate_normals": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "f3r_recon_stats_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "f3r_recon_stats": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, ctypes.c_double, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
+    "f3r_recon_prepare_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, _c_i64]),
+    "f3r_recon_prepare": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, ctypes.c_int, _c_i64, _c_f32, _c_f32, _c_vp, _c_vp,
+                                         _c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
     "f3r_resample_u8": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
     "f3r_imgnorm_u8": (ctypes.c_int, [_c_vp, _c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_vp]),
     "f3r_silu_mul": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_int, ctypes.c_int, _c_vp]),
@@ -133,7 +143,8 @@ class F3RError(RuntimeError):
     pass
 
 
-ABI_VERSION = 350  # f3r_version() of include/f3r.h this file mirrors
+ABI_VERSION = 350  # f3r_version() of include/f3r.h this file mirrors (the reconstruction metrics need RECON_ABI_VERSION)
+RECON_ABI_VERSION = 360
 
 
 def lib():

@@ -11,54 +11,11 @@
 #include "f3r_common.h"
 
 #include "f3r_linalg.h"
+#include "f3r_post_common.h"
 
 namespace {
 
 constexpr int PNT = 1024;  // threads per problem workgroup
-
-// float -> unsigned key with the same ordering (handles negatives too; conf is >= vmin > 0 in practice)
-__device__ __forceinline__ uint32_t fkey(float f) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __builtin_bit_cast(float, u);
-}
-
-// k-th smallest key (0-based) of conf[0..n) by radix select over 11 + 11 + 10 bits; all threads return the same value.
-__device__ uint32_t select_kth(const float* __restrict__ conf, int64_t n, int64_t k, uint32_t* hist /*2048*/, int64_t* sh_i64 /*2*/) {
-  uint32_t prefix = 0, prefix_mask = 0;
-  const int shifts[3] = {21, 10, 0};
-  const int bits[3] = {11, 11, 10};
-  for (int pass = 0; pass < 3; ++pass) {
-    const int nb = 1 << bits[pass];
-    for (int i = threadIdx.x; i < nb; i += PNT) hist[i] = 0;
-    __syncthreads();
-    for (int64_t i = threadIdx.x; i < n; i += PNT) {
-      const uint32_t key = fkey(conf[i]);
-      if ((key & prefix_mask) == prefix) atomicAdd(&hist[(key >> shifts[pass]) & (nb - 1)], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int64_t acc = 0;
-      int b = 0;
-      for (; b < nb; ++b) {
-        if (acc + hist[b] > k) break;
-        acc += hist[b];
-      }
-      sh_i64[0] = b;
-      sh_i64[1] = k - acc;
-    }
-    __syncthreads();
-    const uint32_t b = (uint32_t)sh_i64[0];
-    k = sh_i64[1];
-    prefix |= b << shifts[pass];
-    prefix_mask |= (uint32_t)(nb - 1) << shifts[pass];
-    __syncthreads();
-  }
-  return prefix;
-}
 
 // workspace per problem: 40 doubles: [0..16] moments of mask A (conf & valid), [17..33] of mask B (valid), [34] thr (as double)
 constexpr int WS_PER = 40;
@@ -77,20 +34,7 @@ __global__ __launch_bounds__(PNT) void align_stats_kernel(const float* __restric
   const uint8_t* vm = valid ? valid + prob * npix : nullptr;
 
   // ---- 1. quantile, exactly as torch.quantile (linear): rank = q*(n-1) in fp32, lerp between the two order statistics
-  const float rank = q * (float)(npix - 1);
-  const float rlo = floorf(rank);
-  const int64_t klo = (int64_t)rlo;
-  const int64_t khi = (int64_t)ceilf(rank);
-  const float vlo = fkey_inv(select_kth(cf, npix, klo, hist, sh_i64));
-  float vhi = vlo;
-  if (khi != klo) vhi = fkey_inv(select_kth(cf, npix, khi, hist, sh_i64));
-  if (threadIdx.x == 0) {
-    const float w = rank - rlo;
-    const float d = vhi - vlo;
-    sh_thr = (w < 0.5f) ? vlo + w * d : vhi - d * (1.0f - w);  // at::lerp
-  }
-  __syncthreads();
-  const float thr = sh_thr;
+  const float thr = block_quantile<PNT>(cf, npix, q, hist, sh_i64, &sh_thr);
 
   // ---- 2./3. masked raw moments in fp64: n, sum x(3), sum y(3), sum y_i x_j (9), sum |x|^2   for both masks
   double mA[17], mB[17];
@@ -138,29 +82,10 @@ __global__ void align_solve_kernel(const double* __restrict__ ws, float* __restr
   if (m[0] < 3.0) m += 17;  // fewer than 3 confident points: use the valid mask only (:495-503)
   float* o = rts + prob * 13;
   if (m[0] < 3.0) {  // identity (:506-510)
-    for (int i = 0; i < 9; ++i) o[i] = (i % 4 == 0) ? 1.f : 0.f;
-    o[9] = o[10] = o[11] = 0.f;
-    o[12] = 1.f;
+    identity_rts(o);
     return;
   }
-  const double n = m[0];
-  const double xm[3] = {m[1] / n, m[2] / n, m[3] / n}, ym[3] = {m[4] / n, m[5] / n, m[6] / n};
-  double M[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) M[i][j] = m[7 + i * 3 + j] - n * ym[i] * xm[j];
-  const double sx2 = m[16] - n * (xm[0] * xm[0] + xm[1] * xm[1] + xm[2] * xm[2]);
-  double U[3][3], S[3], V[3][3];
-  f3r_la::svd3(M, U, S, V);
-  const double d = (f3r_la::det3(U) * f3r_la::det3(V) < 0) ? -1.0 : 1.0;
-  double R[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * V[j][0] + U[i][1] * V[j][1] + d * U[i][2] * V[j][2];
-  const double scale = (S[0] + S[1] + d * S[2]) / sx2;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) o[i * 3 + j] = (float)R[i][j];
-    o[9 + i] = (float)(ym[i] - scale * (R[i][0] * xm[0] + R[i][1] * xm[1] + R[i][2] * xm[2]));
-  }
-  o[12] = (float)scale;
+  similarity_from_moments(m, o);
 }
 
 // out = s * (x R^T) + t, fp32, the reference's own operation order (scale the rotated point, then translate)
@@ -224,20 +149,7 @@ __global__ __launch_bounds__(PNT) void focal_kernel(const float* __restrict__ pt
   float4v* wk = work + prob * npix;
 
   // ---- threshold = torch.quantile(conf, q) (linear interpolation, fp32 rank and at::lerp; as in align_stats_kernel)
-  const float rank = q * (float)(npix - 1);
-  const float rlo = floorf(rank);
-  const int64_t klo = (int64_t)rlo;
-  const int64_t khi = (int64_t)ceilf(rank);
-  const float vlo = fkey_inv(select_kth(cf, npix, klo, hist, sh_i64));
-  float vhi = vlo;
-  if (khi != klo) vhi = fkey_inv(select_kth(cf, npix, khi, hist, sh_i64));
-  if (threadIdx.x == 0) {
-    const float w = rank - rlo;
-    const float d = vhi - vlo;
-    sh_thr = (w < 0.5f) ? vlo + w * d : vhi - d * (1.0f - w);
-  }
-  __syncthreads();
-  const float thr = sh_thr;
+  const float thr = block_quantile<PNT>(cf, npix, q, hist, sh_i64, &sh_thr);
   if (threadIdx.x == 0 && thr_out) thr_out[prob] = thr;
 
   // ---- pass 0: per-point terms + the closed-form start  focal = mean(dot_xy_px) / mean(dot_xy_xy)  (post_process.py:121-128)

@@ -1,0 +1,1065 @@
+// Reconstruction metrics (MultiViewDUSt3RLitModule.evaluate_reconstruction, fast3r/models/multiview_dust3r_module.py:551-735, and
+// accuracy / completion / completion_ratio, fast3r/eval/recon_metric.py:14-49) on the GPU:
+//   * an exact nearest-neighbour index over a point cloud: a uniform grid whose cell is sized from the occupied-cell count (surfaces),
+//     points sorted by cell key with a stable LSD counting sort (per-tile histograms, exclusive scan, ordered per-tile scatter: slot
+//     order never depends on arrival order), float4 records {x, y, z, original index}, a dense cell-start table for small grids and
+//     a binary search in the sorted keys otherwise;
+//   * exact 1-NN (what scipy's cKDTree.query returns: fp64 distances of the fp32 coordinates, ties to the smaller index) by
+//     Chebyshev rings of cells around the query's cell, stopped by a lower bound on every unvisited cell (grid_search);
+//   * k-NN (k <= 64) and the normal of Open3D's PointCloud.estimate_normals() (KNN 30, fast_normal_computation): one-pass cumulant
+//     covariance in fp64, eigenvector of the smallest eigenvalue by Jacobi rotations (f3r_linalg.h);
+//   * statistics: fp64 means by a fixed two-level reduction, exact medians (np.median) by an 8 x 8-bit radix select on 64-bit
+//     order-preserving keys of the fp64 values, |n_a . n_b[idx]|, the completion ratio;
+//   * the per-sample pipeline: per-view torch.quantile thresholds, stable compaction across views in torch.cat order, one weighted
+//     similarity registration per sample (the align path's Umeyama solve), s (x R^T) + t.
+// Integer atomics only (histogram counts); no float atomics anywhere: every output is deterministic.
+#include "f3r_common.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <cmath>
+#include <cstring>
+
+#include "f3r_linalg.h"
+#include "f3r_post_common.h"
+
+// build.sh compiles this file with -ffp-contract=off: every product and sum is rounded on its own, as the reference's numpy / torch CPU
+// operations and cKDTree's distance are (the __d*_rn intrinsics alone do not stop the compiler from fusing them into FMAs).
+
+namespace {
+
+constexpr int TILE = 2048;         // elements per sort / compaction workgroup (one wave walks its tile in 64-element steps)
+constexpr int MAX_DIM = 1024;      // grid cells per axis: keys fit 30 bits
+constexpr int64_t DENSE_EXTRA = 65536;
+constexpr int HDR_BYTES = 256;
+constexpr int MISC_BYTES = 512;    // workspace tail: bbox / count words [0, 8), quantiles [8, 14), a header copy from word 16
+constexpr double SLACK = 1e-6;     // cells: covers the rounding of the cell coordinates in the lower bounds (see grid_search)
+constexpr int PNT = 1024;
+
+// one uniform grid: its cells are keys [base, base + ncells) of the index's key space; every point it holds lies in [lo, hi]
+struct Grid {
+  double lo[3], hi[3];
+  double h, inv_h;
+  int32_t dims[3];
+  uint32_t base;
+  int64_t ncells;
+};
+
+// g[0] covers the box of most points; with ngrid == 2 it is trimmed to the 1st..99th percentiles (plus a margin) and g[1] covers
+// the whole bounding box but holds only the points outside g[0] (far outliers), so that they do not stretch g[0]'s cells
+struct NNHeader {
+  Grid g[2];
+  int32_t ngrid;
+  int32_t dense;     // 1: uint32 start[ncells + 1] after the keys; 0: binary search in the sorted keys
+  int64_t m, ncells, occupied;
+  int32_t key_bits, pad;
+};
+static_assert(sizeof(NNHeader) <= HDR_BYTES && 64 + sizeof(NNHeader) <= MISC_BYTES, "header");
+static_assert(sizeof(Grid) == 88 && offsetof(NNHeader, ngrid) == 176, "tests/test_recon_metric_gpu.py reads ngrid at byte 176");
+
+inline int64_t tiles_of(int64_t n) { return (n + TILE - 1) / TILE; }
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline int64_t dense_cap(int64_t m) { return 2 * m + DENSE_EXTRA; }
+
+__device__ __forceinline__ const float4v* hdr_recs(const uint8_t* ix) { return (const float4v*)(ix + HDR_BYTES); }
+__device__ __forceinline__ const uint32_t* hdr_keys(const uint8_t* ix, int64_t m) { return (const uint32_t*)(ix + HDR_BYTES + 16 * m); }
+__device__ __forceinline__ const uint32_t* hdr_table(const uint8_t* ix, int64_t m) { return (const uint32_t*)(ix + HDR_BYTES + 20 * m); }
+
+__device__ __forceinline__ int cell_coord(double u, int G) {
+  const double f = floor(u);
+  if (!(f >= 0.0)) return 0;  // also NaN
+  if (f >= (double)(G - 1)) return G - 1;
+  return (int)f;
+}
+
+__device__ __forceinline__ uint32_t cell_key(const Grid& g, double x, double y, double z) {
+  const int cx = cell_coord((x - g.lo[0]) * g.inv_h, g.dims[0]);
+  const int cy = cell_coord((y - g.lo[1]) * g.inv_h, g.dims[1]);
+  const int cz = cell_coord((z - g.lo[2]) * g.inv_h, g.dims[2]);
+  return g.base + ((uint32_t)cz * (uint32_t)g.dims[1] + (uint32_t)cy) * (uint32_t)g.dims[0] + (uint32_t)cx;
+}
+
+__device__ __forceinline__ bool in_box(const Grid& g, double x, double y, double z) {
+  return x >= g.lo[0] && x <= g.hi[0] && y >= g.lo[1] && y <= g.hi[1] && z >= g.lo[2] && z <= g.hi[2];
+}
+
+// the grid a point belongs to (the same rule for database points and, for ordering only, for queries)
+__device__ __forceinline__ uint32_t point_key(const NNHeader& H, float x, float y, float z) {
+  const double X = x, Y = y, Z = z;
+  return (H.ngrid == 2 && !in_box(H.g[0], X, Y, Z)) ? cell_key(H.g[1], X, Y, Z) : cell_key(H.g[0], X, Y, Z);
+}
+
+// squared distance of fp32 points in fp64, ((dx^2 + dy^2) + dz^2) without contraction: what cKDTree computes on its float64 copies
+__device__ __forceinline__ double dist2(double qx, double qy, double qz, const float4v r) {
+  const double dx = __dsub_rn(qx, (double)r[0]), dy = __dsub_rn(qy, (double)r[1]), dz = __dsub_rn(qz, (double)r[2]);
+  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// bounding box: order-preserving uint keys with integer atomics (min / max do not depend on order)
+__global__ void bbox_kernel(const float* __restrict__ p, int64_t m, uint32_t* __restrict__ bb /*6: min xyz, max xyz*/) {
+  uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+    for (int a = 0; a < 3; ++a) {
+      const uint32_t k = fkey(p[i * 3 + a]);
+      mn[a] = min(mn[a], k);
+      mx[a] = max(mx[a], k);
+    }
+  for (int a = 0; a < 3; ++a)
+    for (int off = 32; off > 0; off >>= 1) {
+      mn[a] = min(mn[a], (uint32_t)__shfl_xor((int)mn[a], off, 64));
+      mx[a] = max(mx[a], (uint32_t)__shfl_xor((int)mx[a], off, 64));
+    }
+  if ((threadIdx.x & 63) == 0)
+    for (int a = 0; a < 3; ++a) {
+      atomicMin(&bb[a], mn[a]);
+      atomicMax(&bb[3 + a], mx[a]);
+    }
+}
+
+__global__ void key_kernel(const float* __restrict__ p, int64_t n, const NNHeader* __restrict__ hdr, uint32_t* __restrict__ keys,
+                           uint32_t* __restrict__ vals) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  keys[i] = point_key(*hdr, p[i * 3 + 0], p[i * 3 + 1], p[i * 3 + 2]);
+  vals[i] = (uint32_t)i;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// stable LSD counting sort of (key, val) pairs, 8 bits per pass.  Tile t of TILE elements is one 64-lane workgroup.
+__global__ __launch_bounds__(64) void radix_hist_kernel(const uint32_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
+                                                        int64_t ntiles) {
+  __shared__ uint32_t cnt[256];
+  for (int d = threadIdx.x; d < 256; d += 64) cnt[d] = 0;
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * TILE;
+  const int64_t end = min(base + TILE, n);
+  for (int64_t i = base + threadIdx.x; i < end; i += 64) atomicAdd(&cnt[(keys[i] >> shift) & 255u], 1u);
+  __syncthreads();
+  for (int d = threadIdx.x; d < 256; d += 64) hist[(int64_t)d * ntiles + blockIdx.x] = cnt[d];  // digit-major: the scan gives slot bases
+}
+
+// exclusive scan of each row (blockIdx.x) of `len` uint32 in place; totals[row] = the row's sum (if totals)
+__global__ __launch_bounds__(1024) void scan_rows_kernel(uint32_t* __restrict__ a, int64_t len, uint32_t* __restrict__ totals) {
+  __shared__ uint32_t sh[1024];
+  uint32_t* r = a + (int64_t)blockIdx.x * len;
+  const int64_t per = (len + 1023) / 1024;
+  const int64_t b0 = min((int64_t)threadIdx.x * per, len), b1 = min(b0 + per, len);
+  uint32_t s = 0;
+  for (int64_t i = b0; i < b1; ++i) s += r[i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const uint32_t t = threadIdx.x >= (unsigned)off ? sh[threadIdx.x - off] : 0u;
+    __syncthreads();
+    sh[threadIdx.x] += t;
+    __syncthreads();
+  }
+  uint32_t run = sh[threadIdx.x] - s;
+  for (int64_t i = b0; i < b1; ++i) {
+    const uint32_t v = r[i];
+    r[i] = run;
+    run += v;
+  }
+  if (threadIdx.x == 1023 && totals) totals[blockIdx.x] = sh[1023];
+}
+
+__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+
+__global__ __launch_bounds__(64) void radix_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, int64_t n, int shift,
+                                                           const uint32_t* __restrict__ hist, int64_t ntiles, uint32_t* __restrict__ kout,
+                                                           uint32_t* __restrict__ vout) {
+  __shared__ uint32_t run[256];
+  for (int d = threadIdx.x; d < 256; d += 64) run[d] = hist[(int64_t)d * ntiles + blockIdx.x];
+  __syncthreads();
+  const int64_t base = (int64_t)blockIdx.x * TILE;
+  const int64_t end = min(base + TILE, n);
+  for (int64_t c = base; c < end; c += 64) {
+    const int64_t i = c + threadIdx.x;
+    const bool ok = i < end;
+    const uint32_t k = ok ? kin[i] : 0u;
+    const uint32_t d = (k >> shift) & 255u;
+    uint64_t peers = __ballot(ok);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const uint64_t bal = __ballot(bit);
+      peers &= bit ? bal : ~bal;
+    }
+    const uint32_t slot = run[d] + (uint32_t)__popcll(peers & lanes_below());  // lanes of the same digit keep their order
+    __syncthreads();
+    if (ok) {
+      kout[slot] = k;
+      vout[slot] = vin[i];
+      if ((peers & lanes_below()) == 0) run[d] += (uint32_t)__popcll(peers);
+    }
+    __syncthreads();
+  }
+}
+
+// sorts (k0, v0) by the low key_bits bits; returns which buffer pair holds the result (0: k0/v0, 1: k1/v1)
+int radix_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t* hist, int64_t n, int key_bits, hipStream_t s) {
+  const int64_t nt = tiles_of(n);
+  int cur = 0;
+  for (int shift = 0; shift < key_bits; shift += 8) {
+    uint32_t *ki = cur ? k1 : k0, *vi = cur ? v1 : v0, *ko = cur ? k0 : k1, *vo = cur ? v0 : v1;
+    hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)nt), dim3(64), 0, s, ki, n, shift, hist, nt);
+    hipLaunchKernelGGL(scan_rows_kernel, dim3(1), dim3(1024), 0, s, hist, 256 * nt, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)nt), dim3(64), 0, s, ki, vi, n, shift, hist, nt, ko, vo);
+    cur ^= 1;
+  }
+  return cur;
+}
+
+__global__ void count_heads_kernel(const uint32_t* __restrict__ keys, int64_t n, uint32_t* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool head = i < n && (i == 0 || keys[i] != keys[i - 1]);
+  const uint64_t b = __ballot(head);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+}
+
+__global__ void dense_start_kernel(const uint32_t* __restrict__ keys, int64_t m, int64_t ncells, uint32_t* __restrict__ start) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c > ncells) return;
+  int64_t lo = 0, hi = m;  // first position with key >= c
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < (uint32_t)c) lo = mid + 1; else hi = mid;
+  }
+  start[c] = (uint32_t)lo;
+}
+
+__global__ void recs_kernel(const float* __restrict__ p, const uint32_t* __restrict__ order, int64_t m, float4v* __restrict__ recs) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t i = order[j];
+  recs[j] = float4v{p[(int64_t)i * 3 + 0], p[(int64_t)i * 3 + 1], p[(int64_t)i * 3 + 2], __uint_as_float(i)};
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Exact search.  u = (q - lo) / h is the query's continuous cell coordinate, ci its cell clamped to the grid.  Every database
+// point of a grid lies in its (clamped) cell c_p, and since the grid spans the box [lo, hi] of its points, u_p in [c_p, c_p + 1]
+// (to within the rounding of u, far below SLACK cells).  Ring R = the cells at Chebyshev distance R from ci.  A cell c at
+// distance >= R has an axis a with |c_a - ci_a| >= R:
+//   * upper side (c_a >= ci_a + R, exists only if ci_a + R <= G_a - 1, so ci_a < G_a - 1 and u_a < ci_a + 1):
+//       |p_a - q_a| >= (c_a - u_a) h >= (ci_a + R - u_a) h  > (R - 1) h
+//   * lower side (c_a <= ci_a - R, exists only if ci_a >= R >= 1, so u_a >= ci_a):
+//       |p_a - q_a| >= (u_a - c_a - 1) h >= (u_a - ci_a + R - 1) h >= (R - 1) h
+// and on every other axis b, |p_b - q_b| >= out_b h, out_b = the distance of u_b from [0, G_b] (non-zero for queries outside the
+// box).  So  LB(R)^2 = h^2 min over (a, side) of [gap_a^2 + sum_{b != a} out_b^2]  bounds the squared distance of every point in
+// every unvisited ring, each gap shrunk by SLACK.  The search stops once LB(R)^2 > best^2 (strict: a point at exactly the best
+// distance but a smaller index is still visited), or when no side has cells left; a cell whose own box is farther than the best
+// is skipped.  Queries outside the box are exact: they only visit more rings.  With two grids each is searched in turn with the
+// same running result (the one holding the query first), and the bound of each covers exactly its own points.
+template <class V>
+__device__ void grid_search(const uint8_t* __restrict__ ix, int gi, double qx, double qy, double qz, V& vis) {
+  const NNHeader& H = *(const NNHeader*)ix;
+  const Grid& g = H.g[gi];
+  const float4v* __restrict__ recs = hdr_recs(ix);
+  const uint32_t* __restrict__ keys = hdr_keys(ix, H.m);
+  const uint32_t* __restrict__ table = hdr_table(ix, H.m);
+  const double q[3] = {qx, qy, qz};
+  double u[3], out2[3];
+  int ci[3], G[3];
+  for (int a = 0; a < 3; ++a) {
+    G[a] = g.dims[a];
+    u[a] = (q[a] - g.lo[a]) * g.inv_h;
+    ci[a] = cell_coord(u[a], G[a]);
+    const double o = u[a] < 0.0 ? -u[a] : (u[a] > (double)G[a] ? u[a] - (double)G[a] : 0.0);
+    const double os = fmax(o - SLACK, 0.0);
+    out2[a] = os * os;
+  }
+  const double h2 = g.h * g.h;
+  for (int R = 0;; ++R) {
+    if (R > 0) {
+      double lb2 = INFINITY;
+      for (int a = 0; a < 3; ++a) {
+        double g = INFINITY;
+        if (ci[a] + R <= G[a] - 1) g = (double)(ci[a] + R) - u[a];
+        if (ci[a] - R >= 0) g = fmin(g, u[a] - (double)(ci[a] - R + 1));
+        if (g == INFINITY) continue;
+        g = fmax(g - SLACK, 0.0);
+        lb2 = fmin(lb2, g * g + (out2[0] + out2[1] + out2[2] - out2[a]));
+      }
+      if (lb2 == INFINITY) break;            // every cell has been visited
+      if (lb2 * h2 > vis.bound()) break;     // nothing unvisited can be as close as the current result
+    }
+    const int z0 = max(ci[2] - R, 0), z1 = min(ci[2] + R, G[2] - 1);
+    const int y0 = max(ci[1] - R, 0), y1 = min(ci[1] + R, G[1] - 1);
+    const int x0 = max(ci[0] - R, 0), x1 = min(ci[0] + R, G[0] - 1);
+    for (int cz = z0; cz <= z1; ++cz) {
+      const double gz = fmax(fmax((double)cz - u[2], u[2] - (double)(cz + 1)) - SLACK, 0.0);
+      for (int cy = y0; cy <= y1; ++cy) {
+        const double gy = fmax(fmax((double)cy - u[1], u[1] - (double)(cy + 1)) - SLACK, 0.0);
+        const bool full = (abs(cz - ci[2]) == R) || (abs(cy - ci[1]) == R);
+        const int step = full ? 1 : 2 * R;
+        for (int cx = full ? x0 : ci[0] - R; cx <= (full ? x1 : ci[0] + R); cx += step) {
+          if (cx < 0 || cx >= G[0]) continue;
+          const double gx = fmax(fmax((double)cx - u[0], u[0] - (double)(cx + 1)) - SLACK, 0.0);
+          if ((gx * gx + gy * gy + gz * gz) * h2 > vis.bound()) continue;
+          const uint32_t key = g.base + ((uint32_t)cz * (uint32_t)G[1] + (uint32_t)cy) * (uint32_t)G[0] + (uint32_t)cx;
+          int64_t j, e;
+          if (H.dense) {
+            j = table[key];
+            e = table[key + 1];
+          } else {
+            int64_t lo = 0, hi = H.m;
+            while (lo < hi) {
+              const int64_t mid = (lo + hi) >> 1;
+              if (keys[mid] < key) lo = mid + 1; else hi = mid;
+            }
+            j = lo;
+            e = H.m;
+          }
+          for (; j < e; ++j) {
+            if (!H.dense && keys[j] != key) break;
+            const float4v r = recs[j];
+            vis.add(dist2(qx, qy, qz, r), (int)__float_as_uint(r.w));
+          }
+        }
+      }
+    }
+  }
+}
+
+template <class V>
+__device__ void search(const uint8_t* __restrict__ ix, double qx, double qy, double qz, V& vis) {
+  const NNHeader& H = *(const NNHeader*)ix;
+  if (H.ngrid == 1) {
+    grid_search(ix, 0, qx, qy, qz, vis);
+    return;
+  }
+  const int first = in_box(H.g[0], qx, qy, qz) ? 0 : 1;
+  grid_search(ix, first, qx, qy, qz, vis);
+  grid_search(ix, 1 - first, qx, qy, qz, vis);
+}
+
+struct Best1 {
+  double d2 = INFINITY;
+  int i = 0x7fffffff;
+  __device__ double bound() const { return d2; }
+  __device__ void add(double d, int j) {
+    if (d < d2 || (d == d2 && j < i)) { d2 = d; i = j; }
+  }
+};
+
+// k best in (d2, index) lexicographic order, in LDS columns [slot][thread] (conflict-free)
+struct BestK {
+  double* d;
+  int* id;
+  int k, n = 0, stride;
+  __device__ double bound() const { return n < k ? INFINITY : d[(k - 1) * stride]; }
+  __device__ void add(double dd, int j) {
+    if (n == k) {
+      const double wd = d[(k - 1) * stride];
+      if (!(dd < wd || (dd == wd && j < id[(k - 1) * stride]))) return;
+    }
+    int p = (n < k) ? n++ : k - 1;
+    while (p > 0) {
+      const double pd = d[(p - 1) * stride];
+      const int pi = id[(p - 1) * stride];
+      if (pd < dd || (pd == dd && pi < j)) break;
+      d[p * stride] = pd;
+      id[p * stride] = pi;
+      --p;
+    }
+    d[p * stride] = dd;
+    id[p * stride] = j;
+  }
+};
+
+__global__ __launch_bounds__(128) void nn1_kernel(const uint8_t* __restrict__ ix, const float* __restrict__ q, const uint32_t* __restrict__ order,
+                                                  int64_t n, double* __restrict__ dist, int32_t* __restrict__ idx) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t qi = order[t];
+  Best1 b;
+  search(ix, (double)q[qi * 3 + 0], (double)q[qi * 3 + 1], (double)q[qi * 3 + 2], b);
+  const bool found = b.i != 0x7fffffff;  // always, for the finite queries f3r_nn_query admits
+  dist[qi] = found ? __dsqrt_rn(b.d2) : INFINITY;
+  idx[qi] = found ? b.i : (int32_t)((const NNHeader*)ix)->m;  // cKDTree's "no neighbour": index m
+}
+
+__global__ void empty_query_kernel(int64_t n, double* __restrict__ dist, int32_t* __restrict__ idx) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  dist[t] = INFINITY;  // cKDTree: no neighbour -> inf, index n (= 0)
+  idx[t] = 0;
+}
+
+constexpr int KNT = 64;  // k-NN threads per workgroup: 64 x 64 slots x 12 bytes of LDS at k = 64
+
+// k nearest of every database point (itself included), walked in sorted order; normal of Open3D's EstimateNormals (fast path):
+// cumulants in (distance, index) order, covariance E[x x^T] - mu mu^T, eigenvector of the smallest eigenvalue; < 3 neighbours -> +z
+__global__ __launch_bounds__(KNT) void knn_normals_kernel(const uint8_t* __restrict__ ix, const float* __restrict__ pts, int k,
+                                                          double* __restrict__ normals, int32_t* __restrict__ knn_idx, double* __restrict__ knn_dist) {
+  extern __shared__ char smem[];
+  const NNHeader& H = *(const NNHeader*)ix;
+  const int64_t j = (int64_t)blockIdx.x * KNT + threadIdx.x;
+  if (j >= H.m) return;
+  const float4v r = hdr_recs(ix)[j];
+  const int64_t self = __float_as_uint(r.w);
+  if (self >= H.m) return;  // records hold indices < m by construction
+  BestK b;
+  b.d = (double*)smem + threadIdx.x;
+  b.id = (int*)((double*)smem + (size_t)k * KNT) + threadIdx.x;
+  b.k = k;
+  b.stride = KNT;
+  search(ix, (double)r[0], (double)r[1], (double)r[2], b);
+  if (knn_idx)
+    for (int s = 0; s < b.n; ++s) {
+      knn_idx[self * k + s] = b.id[s * KNT];
+      if (knn_dist) knn_dist[self * k + s] = __dsqrt_rn(b.d[s * KNT]);
+    }
+  if (!normals) return;
+  double nrm[3] = {0.0, 0.0, 1.0};
+  if (b.n >= 3) {
+    double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int s = 0; s < b.n; ++s) {
+      const int64_t i = b.id[s * KNT];
+      const double x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+      c[0] = __dadd_rn(c[0], x);
+      c[1] = __dadd_rn(c[1], y);
+      c[2] = __dadd_rn(c[2], z);
+      c[3] = __dadd_rn(c[3], __dmul_rn(x, x));
+      c[4] = __dadd_rn(c[4], __dmul_rn(x, y));
+      c[5] = __dadd_rn(c[5], __dmul_rn(x, z));
+      c[6] = __dadd_rn(c[6], __dmul_rn(y, y));
+      c[7] = __dadd_rn(c[7], __dmul_rn(y, z));
+      c[8] = __dadd_rn(c[8], __dmul_rn(z, z));
+    }
+    const double cnt = (double)b.n;
+    for (int t = 0; t < 9; ++t) c[t] = __ddiv_rn(c[t], cnt);
+    double A[3][3], V[3][3];
+    A[0][0] = __dsub_rn(c[3], __dmul_rn(c[0], c[0]));
+    A[0][1] = A[1][0] = __dsub_rn(c[4], __dmul_rn(c[0], c[1]));
+    A[0][2] = A[2][0] = __dsub_rn(c[5], __dmul_rn(c[0], c[2]));
+    A[1][1] = __dsub_rn(c[6], __dmul_rn(c[1], c[1]));
+    A[1][2] = A[2][1] = __dsub_rn(c[7], __dmul_rn(c[1], c[2]));
+    A[2][2] = __dsub_rn(c[8], __dmul_rn(c[2], c[2]));
+    f3r_la::jacobi_sym<3>(A, V);
+    int e = 0;
+    if (A[1][1] < A[e][e]) e = 1;
+    if (A[2][2] < A[e][e]) e = 2;
+    const double len = sqrt(V[0][e] * V[0][e] + V[1][e] * V[1][e] + V[2][e] * V[2][e]);
+    if (len > 0.0)
+      for (int a = 0; a < 3; ++a) nrm[a] = V[a][e] / len;
+  }
+  for (int a = 0; a < 3; ++a) normals[self * 3 + a] = nrm[a];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// statistics
+constexpr int RED_BLOCKS = 256, RED_NT = 256;
+
+__device__ __forceinline__ uint64_t dkey(double v) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double dkey_inv(uint64_t k) {
+  const uint64_t u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
+  return __builtin_bit_cast(double, u);
+}
+
+// dots[i] = |nq[i] . ndb[idx[i]]|, numpy's ((a0 b0 + a1 b1) + a2 b2)
+__global__ void dots_kernel(const int32_t* __restrict__ idx, const double* __restrict__ nq, const double* __restrict__ ndb, int64_t n,
+                            int64_t m_db, double* __restrict__ dots) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t j = idx[i];
+  if (j < 0 || j >= m_db) {  // cannot happen for indices from f3r_nn_query on the same cloud
+    dots[i] = NAN;
+    return;
+  }
+  const double s = __dadd_rn(__dadd_rn(__dmul_rn(ndb[j * 3 + 0], nq[i * 3 + 0]), __dmul_rn(ndb[j * 3 + 1], nq[i * 3 + 1])),
+                             __dmul_rn(ndb[j * 3 + 2], nq[i * 3 + 2]));
+  dots[i] = fabs(s);
+}
+
+// partial[b] = {sum dist, sum dots, count(dist < th)} over a fixed element -> block assignment, reduced in a fixed tree
+__global__ __launch_bounds__(RED_NT) void reduce_kernel(const double* __restrict__ dist, const double* __restrict__ dots, int64_t n, double th,
+                                                        double* __restrict__ partial) {
+  __shared__ double red[RED_NT / 64][3];
+  double a = 0.0, b = 0.0, c = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * RED_NT + threadIdx.x; i < n; i += (int64_t)RED_BLOCKS * RED_NT) {
+    a += dist[i];
+    if (dots) b += dots[i];
+    c += (dist[i] < th) ? 1.0 : 0.0;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+    c += __shfl_xor(c, off, 64);
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  if (lane == 0) { red[wv][0] = a; red[wv][1] = b; red[wv][2] = c; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double s = 0.0;
+    for (int w = 0; w < RED_NT / 64; ++w) s += red[w][threadIdx.x];
+    partial[blockIdx.x * 3 + threadIdx.x] = s;
+  }
+}
+
+// out[0] = mean dist, out[2] = mean dots, out[4] = completion ratio as np.mean(float32 (d < th)) computes it (exact counts below 2^24)
+__global__ void reduce_final_kernel(const double* __restrict__ partial, int64_t n, bool has_dots, double* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int b = 0; b < RED_BLOCKS; ++b)
+    for (int t = 0; t < 3; ++t) s[t] += partial[b * 3 + t];
+  out[0] = n ? s[0] / (double)n : NAN;
+  out[2] = (has_dots && n) ? s[1] / (double)n : NAN;
+  out[4] = n ? (double)__fdiv_rn((float)s[2], (float)n) : NAN;
+}
+
+// median select state: {prefix key, remaining rank} for the two middle ranks
+struct SelState {
+  uint64_t prefix[2];
+  int64_t k[2];
+};
+
+__global__ void sel_init_kernel(SelState* st, int64_t n, uint32_t* hist) {
+  const int t = threadIdx.x;
+  if (t < 512) hist[t] = 0;
+  if (t == 0) {
+    st->prefix[0] = st->prefix[1] = 0;
+    st->k[0] = (n - 1) / 2;  // np.median: the middle value, or the mean of the two middle values for even n
+    st->k[1] = n / 2;
+  }
+}
+
+__global__ __launch_bounds__(256) void sel_hist_kernel(const double* __restrict__ v, int64_t n, const SelState* __restrict__ st, int pass,
+                                                       uint32_t* __restrict__ hist /*[2][256]*/) {
+  __shared__ uint32_t cnt[2][256];
+  cnt[0][threadIdx.x] = 0;
+  cnt[1][threadIdx.x] = 0;
+  __syncthreads();
+  const int shift = 56 - 8 * pass;
+  const uint64_t mask = pass == 0 ? 0ull : (~0ull << (64 - 8 * pass));
+  const uint64_t p0 = st->prefix[0], p1 = st->prefix[1];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const uint64_t key = dkey(v[i]);
+    const uint32_t d = (uint32_t)(key >> shift) & 255u;
+    if ((key & mask) == p0) atomicAdd(&cnt[0][d], 1u);
+    if ((key & mask) == p1) atomicAdd(&cnt[1][d], 1u);
+  }
+  __syncthreads();
+  for (int t = 0; t < 2; ++t)
+    if (cnt[t][threadIdx.x]) atomicAdd(&hist[t * 256 + threadIdx.x], cnt[t][threadIdx.x]);
+}
+
+__global__ void sel_pick_kernel(SelState* st, int pass, uint32_t* hist) {
+  const int t = threadIdx.x;
+  if (t < 2) {
+    const int shift = 56 - 8 * pass;
+    int64_t acc = 0, k = st->k[t];
+    int b = 0;
+    for (; b < 255; ++b) {
+      if (acc + hist[t * 256 + b] > k) break;
+      acc += hist[t * 256 + b];
+    }
+    st->prefix[t] |= (uint64_t)b << shift;
+    st->k[t] = k - acc;
+  }
+  __syncthreads();
+  for (int i = t; i < 512; i += blockDim.x) hist[i] = 0;
+}
+
+__global__ void sel_final_kernel(const SelState* st, int64_t n, double* out) {
+  if (threadIdx.x != 0) return;
+  if (n == 0) { *out = NAN; return; }
+  const double a = dkey_inv(st->prefix[0]), b = dkey_inv(st->prefix[1]);
+  *out = (n & 1) ? a : (a + b) / 2.0;
+}
+
+void median_async(const double* v, int64_t n, SelState* st, uint32_t* hist, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(sel_init_kernel, dim3(1), dim3(512), 0, s, st, n, hist);
+  if (n > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
+    for (int pass = 0; pass < 8; ++pass) {
+      hipLaunchKernelGGL(sel_hist_kernel, dim3(grid), dim3(256), 0, s, v, n, st, pass, hist);
+      hipLaunchKernelGGL(sel_pick_kernel, dim3(1), dim3(256), 0, s, st, pass, hist);
+    }
+  }
+  hipLaunchKernelGGL(sel_final_kernel, dim3(1), dim3(64), 0, s, st, n, out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// evaluate_reconstruction, per sample: the data of sample i is the concatenation over its views of (conf, pred xyz, gt xyz, valid)
+// at pixel offsets seg[i*V + j] .. seg[i*V + j + 1]; every sample spans L pixels.
+__global__ __launch_bounds__(PNT) void recon_thr_kernel(const float* __restrict__ conf, const int64_t* __restrict__ seg, float q_metric, float q_icp,
+                                                        float* __restrict__ thr) {
+  __shared__ uint32_t hist[2048];
+  __shared__ int64_t sh_i64[2];
+  __shared__ float sh_thr;
+  const int64_t s0 = seg[blockIdx.x], n = seg[blockIdx.x + 1] - s0;
+  const float tm = block_quantile<PNT>(conf + s0, n, q_metric, hist, sh_i64, &sh_thr);
+  __syncthreads();
+  const float ti = block_quantile<PNT>(conf + s0, n, q_icp, hist, sh_i64, &sh_thr);
+  if (threadIdx.x == 0) {
+    thr[2 * blockIdx.x] = tm;
+    thr[2 * blockIdx.x + 1] = ti;
+  }
+}
+
+__device__ __forceinline__ int seg_of(const int64_t* __restrict__ seg, int lo, int hi, int64_t g) {  // last s in [lo, hi) with seg[s] <= g
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (seg[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// masks of pixel g: bit 0 = pred / ICP-GT (valid & conf >= thr_metric), bit 1 = metrics GT (valid), bit 2 = ICP weight (conf >= thr_icp)
+__device__ __forceinline__ uint32_t pix_mask(const float* conf, const uint8_t* valid, const float* thr, int s, int64_t g) {
+  const float c = conf[g];
+  const bool v = valid[g] != 0;
+  return (v && c >= thr[2 * s] ? 1u : 0u) | (v ? 2u : 0u) | (c >= thr[2 * s + 1] ? 4u : 0u);
+}
+
+__global__ __launch_bounds__(64) void recon_count_kernel(const float* __restrict__ conf, const uint8_t* __restrict__ valid, const int64_t* __restrict__ seg,
+                                                         const float* __restrict__ thr, int V, int64_t L, int64_t ntiles, uint32_t* __restrict__ cnt) {
+  const int i = blockIdx.y;
+  const int64_t base = (int64_t)blockIdx.x * TILE, end = min(base + TILE, L);
+  uint32_t a = 0, b = 0;
+  for (int64_t p = base + threadIdx.x; p < end; p += 64) {
+    const int64_t g = (int64_t)i * L + p;
+    const uint32_t mk = pix_mask(conf, valid, thr, seg_of(seg, i * V, (i + 1) * V, g), g);
+    a += mk & 1u;
+    b += (mk >> 1) & 1u;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+  }
+  if (threadIdx.x == 0) {
+    cnt[(int64_t)i * ntiles + blockIdx.x] = a;
+    cnt[((int64_t)gridDim.y + i) * ntiles + blockIdx.x] = b;
+  }
+}
+
+// ordered writes: pred / ICP-GT / weight at [i*L + rank among bit 0], metrics GT at [i*L + rank among bit 1]
+__global__ __launch_bounds__(64) void recon_compact_kernel(const float* __restrict__ conf, const float* __restrict__ pred, const float* __restrict__ gt,
+                                                           const uint8_t* __restrict__ valid, const int64_t* __restrict__ seg, const float* __restrict__ thr,
+                                                           int V, int64_t L, int64_t ntiles, const uint32_t* __restrict__ cnt, float* __restrict__ pred_c,
+                                                           float* __restrict__ gticp_c, uint8_t* __restrict__ w_c, float* __restrict__ gt_c) {
+  const int i = blockIdx.y;
+  const int64_t base = (int64_t)blockIdx.x * TILE, end = min(base + TILE, L);
+  uint32_t ra = cnt[(int64_t)i * ntiles + blockIdx.x], rb = cnt[((int64_t)gridDim.y + i) * ntiles + blockIdx.x];
+  for (int64_t c = base; c < end; c += 64) {
+    const int64_t p = c + threadIdx.x;
+    const int64_t g = (int64_t)i * L + p;
+    const uint32_t mk = p < end ? pix_mask(conf, valid, thr, seg_of(seg, i * V, (i + 1) * V, g), g) : 0u;
+    const uint64_t ba = __ballot(mk & 1u), bb = __ballot(mk & 2u);
+    if (mk & 1u) {
+      const int64_t o = (int64_t)i * L + ra + __popcll(ba & lanes_below());
+      for (int a = 0; a < 3; ++a) {
+        pred_c[o * 3 + a] = pred[g * 3 + a];
+        gticp_c[o * 3 + a] = gt[g * 3 + a];
+      }
+      w_c[o] = (mk & 4u) ? 1 : 0;
+    }
+    if (mk & 2u) {
+      const int64_t o = (int64_t)i * L + rb + __popcll(bb & lanes_below());
+      for (int a = 0; a < 3; ++a) gt_c[o * 3 + a] = gt[g * 3 + a];
+    }
+    ra += (uint32_t)__popcll(ba);
+    rb += (uint32_t)__popcll(bb);
+  }
+}
+
+// weighted (0/1) Umeyama over the kept points of sample blockIdx.x: fp64 raw moments of the weight-1 pairs, then the align solve
+__global__ __launch_bounds__(PNT) void recon_register_kernel(const float* __restrict__ x_c, const float* __restrict__ y_c, const uint8_t* __restrict__ w_c,
+                                                             const uint32_t* __restrict__ counts, int64_t L, float* __restrict__ rts) {
+  __shared__ double red[PNT / 64][17];
+  __shared__ double mm[17];
+  const int i = blockIdx.x;
+  const int64_t n = counts[i];
+  const float* px = x_c + (int64_t)i * L * 3;
+  const float* py = y_c + (int64_t)i * L * 3;
+  const uint8_t* pw = w_c + (int64_t)i * L;
+  double m[17];
+#pragma unroll
+  for (int j = 0; j < 17; ++j) m[j] = 0.0;
+  for (int64_t k = threadIdx.x; k < n; k += PNT) {
+    if (!pw[k]) continue;
+    const double x0 = px[k * 3 + 0], x1 = px[k * 3 + 1], x2 = px[k * 3 + 2];
+    const double y0 = py[k * 3 + 0], y1 = py[k * 3 + 1], y2 = py[k * 3 + 2];
+    const double t[17] = {1.0, x0, x1, x2, y0, y1, y2, y0 * x0, y0 * x1, y0 * x2, y1 * x0, y1 * x1, y1 * x2, y2 * x0, y2 * x1, y2 * x2,
+                          x0 * x0 + x1 * x1 + x2 * x2};
+#pragma unroll
+    for (int j = 0; j < 17; ++j) m[j] += t[j];
+  }
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < 17; ++j) {
+    double a = m[j];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+    if (lane == 0) red[wv][j] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x < 17) {
+    double s = 0.0;
+    for (int w = 0; w < PNT / 64; ++w) s += red[w][threadIdx.x];
+    mm[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (mm[0] < 3.0) identity_rts(rts + i * 13);
+    else similarity_from_moments(mm, rts + i * 13);
+  }
+}
+
+// out = s * (x R^T) + t in fp32 (the reference's `s * (x @ R.T) + t`, :664), kept points only
+__global__ void recon_apply_kernel(const float* __restrict__ x_c, const float* __restrict__ rts, const uint32_t* __restrict__ counts, int64_t L,
+                                   int B, float* __restrict__ out) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (int64_t)B * L) return;
+  const int i = (int)(g / L);
+  if (g - (int64_t)i * L >= (int64_t)counts[i]) return;
+  const float* r = rts + i * 13;
+  const float x0 = x_c[g * 3 + 0], x1 = x_c[g * 3 + 1], x2 = x_c[g * 3 + 2];
+  const float s = r[12];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[g * 3 + c] = s * (x0 * r[c * 3 + 0] + x1 * r[c * 3 + 1] + x2 * r[c * 3 + 2]) + r[9 + c];
+}
+
+// count of non-finite coordinates (integer atomics)
+__global__ void nonfinite_kernel(const float* __restrict__ p, int64_t n3, uint32_t* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool bad = i < n3 && !isfinite(p[i]);
+  const uint64_t b = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+}
+
+__global__ void deinterleave_kernel(const float* __restrict__ p, int64_t m, float* __restrict__ x, float* __restrict__ y, float* __restrict__ z) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  x[i] = p[i * 3 + 0];
+  y[i] = p[i * 3 + 1];
+  z[i] = p[i * 3 + 2];
+}
+
+// block b: order statistic k_lo (b even) or k_hi (b odd) of axis b / 2 -> out[b]
+__global__ __launch_bounds__(PNT) void axis_quantiles_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                                                             int64_t m, int64_t k_lo, int64_t k_hi, float* __restrict__ out) {
+  __shared__ uint32_t hist[2048];
+  __shared__ int64_t sh_i64[2];
+  const float* v = blockIdx.x < 2 ? x : (blockIdx.x < 4 ? y : z);
+  const uint32_t key = select_kth<PNT>(v, m, (blockIdx.x & 1) ? k_hi : k_lo, hist, sh_i64);
+  if (threadIdx.x == 0) out[blockIdx.x] = fkey_inv(key);
+}
+
+// count of points outside the box g
+__global__ void outside_kernel(const float* __restrict__ p, int64_t m, Grid g, uint32_t* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool out = i < m && !in_box(g, p[i * 3 + 0], p[i * 3 + 1], p[i * 3 + 2]);
+  const uint64_t b = __ballot(out);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+}
+
+__global__ void to_i32_kernel(const uint32_t* __restrict__ a, int n, int32_t* __restrict__ o) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) o[t] = (int32_t)a[t];
+}
+
+inline unsigned blocks_of(int64_t n, int nt) { return (unsigned)((n + nt - 1) / nt); }
+
+// the sort buffers of f3r_nn_workspace_bytes(n), carved from ws
+struct SortWs {
+  uint32_t *k0, *v0, *k1, *v1, *hist, *misc;
+};
+SortWs carve(void* ws, int64_t n) {
+  char* p = (char*)ws;
+  SortWs w;
+  w.k0 = (uint32_t*)p; p += align256(4 * n);
+  w.v0 = (uint32_t*)p; p += align256(4 * n);
+  w.k1 = (uint32_t*)p; p += align256(4 * n);
+  w.v1 = (uint32_t*)p; p += align256(4 * n);
+  w.hist = (uint32_t*)p; p += align256(4 * (256 * tiles_of(n) + 1));
+  w.misc = (uint32_t*)p;
+  return w;
+}
+
+int key_bits_of(int64_t ncells) {
+  int b = 0;
+  while (b < 32 && ((int64_t)1 << b) < ncells) ++b;
+  return b;
+}
+
+// grid of cell h over the (finite) box [lo, hi]: at most MAX_DIM cells per axis
+void set_grid(Grid& g, const double lo[3], const double hi[3], double h) {
+  double ext = 0.0;
+  for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[a] - lo[a]);
+  if (!(ext > 0.0)) h = 1.0;
+  else if (!(h >= ext / (MAX_DIM - 0.5))) h = ext / (MAX_DIM - 0.5);  // also a NaN / zero h
+  g.h = h;
+  g.inv_h = 1.0 / h;
+  g.ncells = 1;
+  for (int a = 0; a < 3; ++a) {
+    g.lo[a] = lo[a];
+    g.hi[a] = hi[a];
+    g.dims[a] = (int)std::min<double>(std::max(std::floor((hi[a] - lo[a]) * g.inv_h) + 1.0, 1.0), MAX_DIM);
+    g.ncells *= g.dims[a];
+  }
+}
+
+// key space of the grids: g[1] after g[0]
+void finish_grids(NNHeader& H) {
+  H.g[1].base = (uint32_t)H.g[0].ncells;
+  H.ncells = H.g[0].ncells + (H.ngrid == 2 ? H.g[1].ncells : 0);
+  H.key_bits = key_bits_of(H.ncells);
+}
+
+double box_volume(const double lo[3], const double hi[3]) {
+  double ext = 0.0, vol = 1.0;
+  for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[a] - lo[a]);
+  for (int a = 0; a < 3; ++a) vol *= std::max(hi[a] - lo[a], 1e-3 * ext);
+  return vol;
+}
+
+}  // namespace
+
+extern "C" size_t f3r_nn_index_bytes(int64_t m) {
+  if (m < 0) return 0;
+  return align256(HDR_BYTES + 20 * (size_t)m + 4 * (size_t)(dense_cap(m) + 1));
+}
+
+extern "C" size_t f3r_nn_workspace_bytes(int64_t n) {
+  if (n < 0) return 0;
+  return 4 * align256(4 * (size_t)n) + align256(4 * (size_t)(256 * tiles_of(n) + 1)) + MISC_BYTES;
+}
+
+extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t index_bytes, void* workspace, size_t ws_bytes, f3r_stream_t stream) {
+  F3R_REQUIRE(index && workspace && (pts || m == 0), "f3r_nn_build: null pointer");
+  F3R_REQUIRE(m >= 0 && m < ((int64_t)1 << 31), "f3r_nn_build: m = %lld outside [0, 2^31)", (long long)m);
+  F3R_REQUIRE(index_bytes >= f3r_nn_index_bytes(m) && (((uintptr_t)index) & 15) == 0, "f3r_nn_build: index too small / misaligned");
+  F3R_REQUIRE(ws_bytes >= f3r_nn_workspace_bytes(m) && (((uintptr_t)workspace) & 255) == 0, "f3r_nn_build: workspace too small / misaligned");
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t* ix = (uint8_t*)index;
+  NNHeader H{};
+  H.m = 0;
+  H.ngrid = 1;
+  const double unit_lo[3] = {0.0, 0.0, 0.0}, unit_hi[3] = {0.0, 0.0, 0.0};
+  set_grid(H.g[0], unit_lo, unit_hi, 1.0);
+  finish_grids(H);
+  // an empty index first: if the build fails below, the buffer still holds a valid (empty) index
+  if (hipMemcpyAsync(ix, &H, sizeof(H), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return f3r_check_launch("f3r_nn_build");
+  if (m == 0) return f3r_check_launch("f3r_nn_build");
+  SortWs w = carve(workspace, m);
+  // ---- bounding box.  NaN keys order beyond +-inf, so any NaN or inf coordinate makes an end of the box non-finite.
+  const uint32_t bb_init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
+  uint32_t bb[8];
+  (void)hipMemcpyAsync(w.misc, bb_init, sizeof(bb_init), hipMemcpyHostToDevice, s);
+  hipLaunchKernelGGL(bbox_kernel, dim3(std::min<unsigned>(blocks_of(m, 256), 1024)), dim3(256), 0, s, pts, m, w.misc);
+  (void)hipMemcpyAsync(bb, w.misc, sizeof(bb), hipMemcpyDeviceToHost, s);
+  if (hipStreamSynchronize(s) != hipSuccess) return f3r_check_launch("f3r_nn_build");
+  double lo[3], hi[3];
+  auto kinv = [](uint32_t k) {
+    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float f;
+    memcpy(&f, &u, 4);
+    return (double)f;
+  };
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = kinv(bb[a]);
+    hi[a] = kinv(bb[3 + a]);
+    F3R_REQUIRE(std::isfinite(lo[a]) && std::isfinite(hi[a]), "f3r_nn_build: non-finite coordinates (NaN or inf)");
+  }
+  double ext = 0.0;
+  for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[a] - lo[a]);
+  // ---- far outliers: the box of the 1st..99th percentiles per axis, widened by a quarter of its extent on each side.  If the
+  //      bounding box is more than 4x as large, the points outside it go to a second grid over the whole box.
+  double tlo[3] = {lo[0], lo[1], lo[2]}, thi[3] = {hi[0], hi[1], hi[2]};
+  int64_t m_out = 0;
+  if (m >= 4096 && ext > 0.0) {
+    float* ax = (float*)w.k0;
+    float* ay = (float*)w.v0;
+    float* az = (float*)w.k1;
+    float* qv = (float*)(w.misc + 8);
+    float q[6];
+    hipLaunchKernelGGL(deinterleave_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, m, ax, ay, az);
+    hipLaunchKernelGGL(axis_quantiles_kernel, dim3(6), dim3(PNT), 0, s, ax, ay, az, m, (m - 1) / 100, (m - 1) - (m - 1) / 100, qv);
+    (void)hipMemcpyAsync(q, qv, sizeof(q), hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return f3r_check_launch("f3r_nn_build");
+    double text = 0.0;
+    for (int a = 0; a < 3; ++a) {
+      const double w4 = 0.25 * ((double)q[2 * a + 1] - (double)q[2 * a]);
+      tlo[a] = std::max(lo[a], (double)q[2 * a] - w4);
+      thi[a] = std::min(hi[a], (double)q[2 * a + 1] + w4);
+      text = std::max(text, thi[a] - tlo[a]);
+    }
+    if (text < 0.25 * ext) {
+      Grid t;
+      set_grid(t, tlo, thi, 1.0);
+      uint32_t cnt = 0;
+      (void)hipMemsetAsync(w.misc + 7, 0, 4, s);
+      hipLaunchKernelGGL(outside_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, m, t, w.misc + 7);
+      (void)hipMemcpyAsync(&cnt, w.misc + 7, 4, hipMemcpyDeviceToHost, s);
+      if (hipStreamSynchronize(s) != hipSuccess) return f3r_check_launch("f3r_nn_build");
+      m_out = cnt;
+    }
+  }
+  H.m = m;
+  if (m_out > 0) {
+    H.ngrid = 2;
+    set_grid(H.g[1], lo, hi, std::cbrt(box_volume(lo, hi) * 16.0 / (double)m_out));
+  } else {
+    for (int a = 0; a < 3; ++a) { tlo[a] = lo[a]; thi[a] = hi[a]; }
+  }
+  const int64_t m_in = m - m_out;
+  // ---- cell size of g[0]: 16 points per cell if the cloud filled its box, then one refinement from the occupied-cell count unless
+  //      that lands within 8..32 already
+  set_grid(H.g[0], tlo, thi, std::cbrt(box_volume(tlo, thi) * 16.0 / (double)m_in));
+  finish_grids(H);
+  uint32_t* dhdr = w.misc + 16;  // a device copy of the header for the key kernel (after the bbox / count / quantile words)
+  int res = 0;
+  for (int round = 0; round < 2; ++round) {
+    (void)hipMemcpyAsync(dhdr, &H, sizeof(H), hipMemcpyHostToDevice, s);
+    hipLaunchKernelGGL(key_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, m, (const NNHeader*)dhdr, w.k0, w.v0);
+    res = radix_sort(w.k0, w.v0, w.k1, w.v1, w.hist, m, H.key_bits, s);
+    uint32_t* ks = res ? w.k1 : w.k0;
+    uint32_t occ = 0;
+    (void)hipMemsetAsync(w.misc + 7, 0, 4, s);
+    hipLaunchKernelGGL(count_heads_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, ks, m, w.misc + 7);
+    (void)hipMemcpyAsync(&occ, w.misc + 7, 4, hipMemcpyDeviceToHost, s);
+    if (hipStreamSynchronize(s) != hipSuccess) return f3r_check_launch("f3r_nn_build");
+    H.occupied = occ;
+    const double ppc = (double)m / (double)std::max<uint32_t>(occ, 1);
+    if (round == 1 || (ppc >= 8.0 && ppc <= 32.0) || H.g[0].ncells == 1) break;
+    // too few points per cell: a surface (~h^2 per cell); too many: the points fill a smaller volume than the box (~h^3 per cell)
+    const double h_old = H.g[0].h;
+    set_grid(H.g[0], tlo, thi, H.g[0].h * (ppc < 8.0 ? std::sqrt(16.0 / ppc) : std::cbrt(16.0 / ppc)));
+    finish_grids(H);
+    if (H.g[0].h == h_old) break;
+  }
+  // ---- records, keys, cell table
+  const uint32_t* ks = res ? w.k1 : w.k0;
+  const uint32_t* vs = res ? w.v1 : w.v0;
+  H.dense = (H.ncells <= dense_cap(m)) ? 1 : 0;
+  hipLaunchKernelGGL(recs_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, vs, m, (float4v*)(ix + HDR_BYTES));
+  uint32_t* keys = (uint32_t*)(ix + HDR_BYTES + 16 * m);
+  (void)hipMemcpyAsync(keys, ks, 4 * (size_t)m, hipMemcpyDeviceToDevice, s);
+  if (H.dense)
+    hipLaunchKernelGGL(dense_start_kernel, dim3(blocks_of(H.ncells + 1, 256)), dim3(256), 0, s, keys, m, H.ncells, (uint32_t*)(ix + HDR_BYTES + 20 * m));
+  (void)hipMemcpyAsync(ix, &H, sizeof(H), hipMemcpyHostToDevice, s);
+  if (hipStreamSynchronize(s) != hipSuccess) return f3r_check_launch("f3r_nn_build");
+  return f3r_check_launch("f3r_nn_build");
+}
+
+static int read_header(const void* index, NNHeader* H, hipStream_t s) {
+  if (hipMemcpyAsync(H, index, sizeof(NNHeader), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
+  return hipStreamSynchronize(s) == hipSuccess ? 0 : -1;
+}
+
+extern "C" int f3r_nn_query(const void* index, const float* query, int64_t n, double* dist, int32_t* idx, void* workspace, size_t ws_bytes,
+                            f3r_stream_t stream) {
+  F3R_REQUIRE(index && workspace && ((query && dist && idx) || n == 0), "f3r_nn_query: null pointer");
+  F3R_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "f3r_nn_query: n = %lld outside [0, 2^31)", (long long)n);
+  F3R_REQUIRE(ws_bytes >= f3r_nn_workspace_bytes(n) && (((uintptr_t)workspace) & 255) == 0, "f3r_nn_query: workspace too small / misaligned");
+  F3R_REQUIRE((((uintptr_t)index) & 15) == 0, "f3r_nn_query: index misaligned");
+  if (n == 0) return F3R_OK;
+  hipStream_t s = (hipStream_t)stream;
+  // cKDTree rejects non-finite queries (ValueError); so does this, before the search
+  uint32_t* bad = carve(workspace, n).misc;
+  uint32_t nbad = 0;
+  (void)hipMemsetAsync(bad, 0, 4, s);
+  hipLaunchKernelGGL(nonfinite_kernel, dim3(blocks_of(3 * n, 256)), dim3(256), 0, s, query, 3 * n, bad);
+  (void)hipMemcpyAsync(&nbad, bad, 4, hipMemcpyDeviceToHost, s);
+  NNHeader H;
+  if (read_header(index, &H, s)) return f3r_check_launch("f3r_nn_query");
+  F3R_REQUIRE(nbad == 0, "f3r_nn_query: %u non-finite query coordinates (NaN or inf)", nbad);
+  if (H.m == 0) {
+    hipLaunchKernelGGL(empty_query_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, n, dist, idx);
+    return f3r_check_launch("f3r_nn_query");
+  }
+  // queries sorted by their (clamped) cell of the same grid: neighbouring threads walk neighbouring cells
+  SortWs w = carve(workspace, n);
+  hipLaunchKernelGGL(key_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, query, n, (const NNHeader*)index, w.k0, w.v0);
+  const int res = radix_sort(w.k0, w.v0, w.k1, w.v1, w.hist, n, H.key_bits, s);
+  hipLaunchKernelGGL(nn1_kernel, dim3(blocks_of(n, 128)), dim3(128), 0, s, (const uint8_t*)index, query, res ? w.v1 : w.v0, n, dist, idx);
+  return f3r_check_launch("f3r_nn_query");
+}
+
+extern "C" int f3r_estimate_normals(const void* index, const float* pts, int k, double* normals, int32_t* knn_idx, double* knn_dist,
+                                    f3r_stream_t stream) {
+  F3R_REQUIRE(index && pts, "f3r_estimate_normals: null pointer");
+  F3R_REQUIRE(k >= 1 && k <= 64, "f3r_estimate_normals: k = %d outside 1..64", k);
+  F3R_REQUIRE(normals || knn_idx, "f3r_estimate_normals: no output");
+  F3R_REQUIRE((((uintptr_t)index) & 15) == 0, "f3r_estimate_normals: index misaligned");
+  hipStream_t s = (hipStream_t)stream;
+  NNHeader H;
+  if (read_header(index, &H, s)) return f3r_check_launch("f3r_estimate_normals");
+  if (H.m == 0) return F3R_OK;
+  const int kk = (int)std::min<int64_t>(k, H.m);  // Open3D: k = min(knn, size)
+  const size_t lds = (size_t)kk * KNT * 12;
+  hipLaunchKernelGGL(knn_normals_kernel, dim3(blocks_of(H.m, KNT)), dim3(KNT), lds, s, (const uint8_t*)index, pts, kk, normals, knn_idx, knn_dist);
+  return f3r_check_launch("f3r_estimate_normals");
+}
+
+extern "C" size_t f3r_recon_stats_workspace_bytes(int64_t n) {
+  if (n < 0) return 0;
+  return align256(8 * (size_t)n) + align256(8 * 3 * RED_BLOCKS) + align256(sizeof(SelState)) + align256(4 * 512);
+}
+
+extern "C" int f3r_recon_stats(const double* dist, const int32_t* idx, const double* normals_q, const double* normals_db, int64_t n, int64_t m_db,
+                               double dist_th,
+                               double* out, void* workspace, size_t ws_bytes, f3r_stream_t stream) {
+  F3R_REQUIRE(out && workspace && (dist || n == 0), "f3r_recon_stats: null pointer");
+  F3R_REQUIRE(n >= 0 && m_db >= 0, "f3r_recon_stats: n or m_db < 0");
+  F3R_REQUIRE(!normals_q == !normals_db && (!normals_q || idx || n == 0), "f3r_recon_stats: normals need both clouds' normals and idx");
+  F3R_REQUIRE(ws_bytes >= f3r_recon_stats_workspace_bytes(n) && (((uintptr_t)workspace) & 255) == 0, "f3r_recon_stats: workspace too small / misaligned");
+  hipStream_t s = (hipStream_t)stream;
+  char* p = (char*)workspace;
+  double* dots = (double*)p; p += align256(8 * (size_t)n);
+  double* partial = (double*)p; p += align256(8 * 3 * RED_BLOCKS);
+  SelState* st = (SelState*)p; p += align256(sizeof(SelState));
+  uint32_t* hist = (uint32_t*)p;
+  const bool nrm = normals_q != nullptr;
+  if (nrm && n) hipLaunchKernelGGL(dots_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, idx, normals_q, normals_db, n, m_db, dots);
+  hipLaunchKernelGGL(reduce_kernel, dim3(RED_BLOCKS), dim3(RED_NT), 0, s, dist, nrm ? dots : nullptr, n, dist_th, partial);
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, s, partial, n, nrm, out);
+  median_async(dist, n, st, hist, out + 1, s);
+  if (nrm) median_async(dots, n, st, hist, out + 3, s);
+  else (void)hipMemcpyAsync(out + 3, out + 2, 8, hipMemcpyDeviceToDevice, s);  // NaN
+  return f3r_check_launch("f3r_recon_stats");
+}
+
+extern "C" size_t f3r_recon_prepare_workspace_bytes(int n_samples, int n_views, int64_t L) {
+  if (n_samples <= 0 || n_views <= 0 || L <= 0) return 0;
+  const size_t BL = (size_t)n_samples * (size_t)L;
+  return align256(4 * 2 * (size_t)n_samples * (size_t)n_views) + align256(4 * 2 * (size_t)n_samples * (size_t)tiles_of(L)) +
+         align256(4 * 2 * (size_t)n_samples) + 2 * align256(12 * BL) + align256(BL);
+}
+
+extern "C" int f3r_recon_prepare(const float* conf, const float* pred, const float* gt, const uint8_t* valid, const int64_t* seg, int n_samples,
+                                 int n_views, int64_t L, float q_metric, float q_icp, float* pred_out, float* gt_out, int32_t* counts, float* rts,
+                                 void* workspace, size_t ws_bytes, f3r_stream_t stream) {
+  F3R_REQUIRE(conf && pred && gt && valid && seg && pred_out && gt_out && counts && rts && workspace, "f3r_recon_prepare: null pointer");
+  F3R_REQUIRE(n_samples > 0 && n_views > 0 && L > 0 && L < ((int64_t)1 << 31), "f3r_recon_prepare: bad sizes");
+  F3R_REQUIRE(q_metric >= 0.f && q_metric <= 1.f && q_icp >= 0.f && q_icp <= 1.f, "f3r_recon_prepare: quantile outside [0, 1]");
+  F3R_REQUIRE(ws_bytes >= f3r_recon_prepare_workspace_bytes(n_samples, n_views, L) && (((uintptr_t)workspace) & 255) == 0,
+              "f3r_recon_prepare: workspace too small / misaligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int B = n_samples, V = n_views;
+  const int64_t nt = tiles_of(L);
+  const size_t BL = (size_t)B * (size_t)L;
+  char* p = (char*)workspace;
+  float* thr = (float*)p; p += align256(4 * 2 * (size_t)B * V);
+  uint32_t* cnt = (uint32_t*)p; p += align256(4 * 2 * (size_t)B * nt);
+  uint32_t* tot = (uint32_t*)p; p += align256(4 * 2 * (size_t)B);
+  float* pred_c = (float*)p; p += align256(12 * BL);
+  float* gticp_c = (float*)p; p += align256(12 * BL);
+  uint8_t* w_c = (uint8_t*)p;
+  hipLaunchKernelGGL(recon_thr_kernel, dim3(B * V), dim3(PNT), 0, s, conf, seg, q_metric, q_icp, thr);
+  hipLaunchKernelGGL(recon_count_kernel, dim3((unsigned)nt, B), dim3(64), 0, s, conf, valid, seg, thr, V, L, nt, cnt);
+  hipLaunchKernelGGL(scan_rows_kernel, dim3(2 * B), dim3(1024), 0, s, cnt, nt, tot);
+  hipLaunchKernelGGL(recon_compact_kernel, dim3((unsigned)nt, B), dim3(64), 0, s, conf, pred, gt, valid, seg, thr, V, L, nt, cnt, pred_c, gticp_c, w_c,
+                     gt_out);
+  hipLaunchKernelGGL(recon_register_kernel, dim3(B), dim3(PNT), 0, s, pred_c, gticp_c, w_c, tot, L, rts);
+  hipLaunchKernelGGL(recon_apply_kernel, dim3(blocks_of((int64_t)BL, 256)), dim3(256), 0, s, pred_c, rts, tot, L, B, pred_out);
+  hipLaunchKernelGGL(to_i32_kernel, dim3(blocks_of(2 * B, 64)), dim3(64), 0, s, tot, 2 * B, counts);
+  return f3r_check_launch("f3r_recon_prepare");
+}

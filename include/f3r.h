@@ -46,7 +46,7 @@ typedef enum { F3R_F16 = 0, F3R_BF16 = 1 } f3r_dtype;
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -421,6 +421,47 @@ size_t f3r_focal_workspace_bytes(int n_views, int H, int W);
 int f3r_estimate_focal(const float* pts3d, const float* conf, float* focal, float* thr_out, void* workspace, size_t ws_bytes,
                        int n_views, int H, int W, float quantile, float ppx, float ppy, int n_iter, float min_focal, float max_focal,
                        f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Reconstruction metrics (ABI 360): MultiViewDUSt3RLitModule.evaluate_reconstruction (fast3r/models/multiview_dust3r_module.py:551-735)
+ * and accuracy / completion / completion_ratio (fast3r/eval/recon_metric.py:14-49).  Synchronous with the host where noted (they
+ * read small results back), so they are not for graph capture.
+ * f3r_nn_build: exact nearest-neighbour index over m fp32 points [m][3] (a uniform grid, points sorted by cell); index:
+ *   f3r_nn_index_bytes(m) device bytes, 16-byte aligned; workspace: f3r_nn_workspace_bytes(m) bytes, 256-byte aligned.  The index
+ *   keeps no pointer to pts.  NaN / inf coordinates -> F3R_ERR_ARG (the buffer then holds an empty index).  Synchronises the stream.
+ * f3r_nn_query: for each of n fp32 query points, the nearest database point: dist [n] fp64 = sqrt(dx^2 + dy^2 + dz^2) of the
+ *   fp32 coordinates in fp64 (scipy cKDTree.query), idx [n] int32, ties to the smaller index; an empty database gives inf and 0.
+ *   workspace: f3r_nn_workspace_bytes(n).  NaN / inf query coordinates -> F3R_ERR_ARG.  Reads the index header back (synchronises
+ *   the stream).
+ * f3r_estimate_normals: the min(k, m) nearest database points of every database point (itself included; 1 <= k <= 64), in
+ *   (distance, index) order -> knn_idx / knn_dist [m][k] (either may be NULL), and the normal of Open3D's
+ *   PointCloud.estimate_normals() (fast_normal_computation) -> normals [m][3] fp64 (NULL = none): eigenvector of the smallest
+ *   eigenvalue of the fp64 cumulant covariance, (0, 0, 1) below 3 neighbours; the sign is arbitrary.  pts is the array the index
+ *   was built from.
+ * f3r_recon_stats: out[5] fp64 (device) = { mean dist, median dist, mean dot, median dot, completion ratio } with
+ *   dot[i] = |normals_q[i] . normals_db[idx[i]]| (NaN without normals; normals_db has m_db rows), medians as np.median, the ratio as
+ *   np.mean((dist < dist_th).astype(np.float32)); n = 0 gives NaN.  workspace: f3r_recon_stats_workspace_bytes(n).
+ * f3r_recon_prepare: the per-sample part of evaluate_reconstruction before the metrics.  Inputs are the views of every sample
+ *   concatenated sample-major: sample i, view j covers pixels seg[i*n_views + j] .. seg[i*n_views + j + 1] (seg: device int64,
+ *   n_samples*n_views + 1 entries, seg[i*n_views] = i*L) of conf [.] fp32, pred / gt [.][3] fp32, valid [.] bytes.  Per view:
+ *   thr_m = torch.quantile(conf, q_metric), thr_icp = torch.quantile(conf, q_icp); kept = valid & conf >= thr_m.  Per sample, in
+ *   view order: pred_out [i*L + r] = s (pred R^T) + t of the kept points, with (R, t, s) -> rts [i][13] the similarity
+ *   registration of kept pred onto kept gt weighted by conf >= thr_icp (identity below 3 weighted points); gt_out [i*L + r] = gt
+ *   of the valid points; counts [2][n_samples] int32 = { kept, valid }.  workspace: f3r_recon_prepare_workspace_bytes.
+ */
+size_t f3r_nn_index_bytes(int64_t m);
+size_t f3r_nn_workspace_bytes(int64_t n);
+int f3r_nn_build(const float* pts, int64_t m, void* index, size_t index_bytes, void* workspace, size_t ws_bytes, f3r_stream_t stream);
+int f3r_nn_query(const void* index, const float* query, int64_t n, double* dist, int32_t* idx, void* workspace, size_t ws_bytes,
+                 f3r_stream_t stream);
+int f3r_estimate_normals(const void* index, const float* pts, int k, double* normals, int32_t* knn_idx, double* knn_dist, f3r_stream_t stream);
+size_t f3r_recon_stats_workspace_bytes(int64_t n);
+int f3r_recon_stats(const double* dist, const int32_t* idx, const double* normals_q, const double* normals_db, int64_t n, int64_t m_db,
+                    double dist_th, double* out, void* workspace, size_t ws_bytes, f3r_stream_t stream);
+size_t f3r_recon_prepare_workspace_bytes(int n_samples, int n_views, int64_t L);
+int f3r_recon_prepare(const float* conf, const float* pred, const float* gt, const uint8_t* valid, const int64_t* seg, int n_samples,
+                      int n_views, int64_t L, float q_metric, float q_icp, float* pred_out, float* gt_out, int32_t* counts, float* rts,
+                      void* workspace, size_t ws_bytes, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_estimate_poses: camera pose (cam-to-world) and, when unknown, focal length of every view from its global pointmap.
