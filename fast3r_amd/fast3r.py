@@ -18,474 +18,65 @@ import time
 from collections import OrderedDict
 from copy import deepcopy
 
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import dpt_head, ops
 from ._lib import F3RError
 from .dist import ViewSharding, split_range
-
-
-# ======================================================================================= parameter containers
-class _Params(nn.Module):
-    """A module that only owns parameters; calling it is a bug (the compute lives in the HIP engine)."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise F3RError("fast3r_amd parameter containers are not callable; use Fast3R.forward")
-
-
-class _Attention(_Params):
-    def __init__(self, dim, qkv_bias=True):
-        super().__init__()
-        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)  # blocks.py:125
-        self.proj = nn.Linear(dim, dim)                    # blocks.py:128
-
-
-class _Mlp(_Params):
-    def __init__(self, dim, hidden):
-        super().__init__()
-        self.fc1 = nn.Linear(dim, hidden)  # blocks.py:94
-        self.fc2 = nn.Linear(hidden, dim)  # blocks.py:97
-
-
-class _Block(_Params):
-    def __init__(self, dim, mlp_ratio, eps, qkv_bias=True):
-        super().__init__()
-        self.norm1 = nn.LayerNorm(dim, eps=eps)  # blocks.py:214
-        self.attn = _Attention(dim, qkv_bias)
-        self.norm2 = nn.LayerNorm(dim, eps=eps)  # blocks.py:227
-        self.mlp = _Mlp(dim, int(dim * mlp_ratio))
-
-
-class _PatchEmbed(_Params):
-    def __init__(self, patch_size, dim):
-        super().__init__()
-        self.patch_size = (patch_size, patch_size)
-        self.proj = nn.Conv2d(3, dim, kernel_size=patch_size, stride=patch_size)  # blocks.py:412-414
-        self.norm = nn.Identity()
-
-
-class CroCoEncoder(_Params):
-    """fast3r.py:499-559.  RoPE-2D (freq from 'RoPE<freq>'), LayerNorm eps 1e-6."""
-
-    def __init__(self, img_size=512, patch_size=16, patch_embed_cls="ManyAR_PatchEmbed", embed_dim=768, num_heads=12,
-                 depth=12, mlp_ratio=4, pos_embed="RoPE100", attn_implementation="pytorch_naive"):
-        super().__init__()
-        assert patch_embed_cls in ["PatchEmbedDust3R", "ManyAR_PatchEmbed"]  # patch_embed.py:19
-        if not pos_embed.startswith("RoPE"):
-            raise NotImplementedError("Unknown pos_embed " + pos_embed)  # fast3r.py:533
-        if attn_implementation not in ("pytorch_naive", "flash_attention", "pytorch_auto"):
-            raise ValueError(f"Unknown attn_implementation: {attn_implementation}")  # blocks.py:192
-        if embed_dim % num_heads != 0 or embed_dim // num_heads != 64:
-            raise ValueError("fast3r_amd kernels are built for head_dim 64 (ViT-B/L/H family)")
-        self.patch_embed_cls = patch_embed_cls
-        self.patch_size, self.embed_dim, self.num_heads, self.depth = patch_size, embed_dim, num_heads, depth
-        self.pos_embed = pos_embed
-        self.rope_freq = float(pos_embed[len("RoPE"):])
-        self.patch_embed = _PatchEmbed(patch_size, embed_dim)
-        self.enc_blocks = nn.ModuleList([_Block(embed_dim, mlp_ratio, 1e-6) for _ in range(depth)])
-        self.enc_norm = nn.LayerNorm(embed_dim, eps=1e-6)
-
-
-class _LayerScale(_Params):
-    def __init__(self, dim, init_values=1.0):
-        super().__init__()
-        self.gamma = nn.Parameter(init_values * torch.ones(dim))
-
-
-class _DinoBlock(_Params):
-    """DINOv2 `Block` (dinov2/layers/block.py): x + ls1(attn(norm1(x))); x + ls2(mlp(norm2(x)))."""
-
-    def __init__(self, dim, mlp_ratio):
-        super().__init__()
-        self.norm1 = nn.LayerNorm(dim, eps=1e-6)
-        self.attn = _Attention(dim, qkv_bias=True)
-        self.ls1 = _LayerScale(dim)
-        self.norm2 = nn.LayerNorm(dim, eps=1e-6)
-        self.mlp = _Mlp(dim, int(dim * mlp_ratio))
-        self.ls2 = _LayerScale(dim)
-
-
-class _DinoViT(_Params):
-    """Parameter layout of DINOv2's `DinoVisionTransformer` as torch.hub's `dinov2_vitl14` builds it (facebookresearch/dinov2
-    models/vision_transformer.py: img_size 518, patch 14, no register tokens, LayerScale, MLP ffn, block_chunks = 0): the keys under
-    `encoder.model.` are the hub checkpoint's own."""
-
-    def __init__(self, embed_dim, depth, num_heads, mlp_ratio, patch_size, pos_grid):
-        super().__init__()
-        self.embed_dim, self.num_heads, self.patch_size, self.pos_grid = embed_dim, num_heads, patch_size, pos_grid
-        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
-        self.pos_embed = nn.Parameter(torch.zeros(1, 1 + pos_grid * pos_grid, embed_dim))
-        self.mask_token = nn.Parameter(torch.zeros(1, embed_dim))  # in the checkpoint; unused at inference
-        nn.init.trunc_normal_(self.pos_embed, std=0.02)
-        nn.init.normal_(self.cls_token, std=1e-6)
-        self.patch_embed = _PatchEmbed(patch_size, embed_dim)
-        self.blocks = nn.ModuleList([_DinoBlock(embed_dim, mlp_ratio) for _ in range(depth)])
-        self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
-
-
-class DinoEncoder(_Params):
-    """fast3r.py:561-651: DINOv2 ViT-L/14 patch tokens (`forward_features(...)['x_norm_patchtokens']`), portrait samples encoded upright
-    and their tokens put back in the stored (landscape) order.  The reference builds the backbone with torch.hub.load (network); here
-    the same architecture is built locally (random init; a checkpoint's `encoder.model.*` keys load as they are).  The size arguments
-    exist only so that tests can build a small one: the reference class is always ViT-L/14."""
-
-    def __init__(self, patch_size=14, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4, pos_grid=37, **kwargs):
-        super().__init__()
-        assert patch_size == 14, "DINOv2 model must have patch size 14"  # fast3r.py:570
-        if embed_dim // num_heads != 64:
-            raise ValueError("fast3r_amd kernels are built for head_dim 64")
-        self.patch_size, self.embed_dim, self.num_heads, self.depth = patch_size, embed_dim, num_heads, depth
-        self.patch_embed_cls = "dino"
-        self.model = _DinoViT(embed_dim, depth, num_heads, mlp_ratio, patch_size, pos_grid)
-
-
-def sincos_1d_table(embed_dim, n_pos):
-    """get_1d_sincos_pos_embed_from_grid (croco/models/pos_embed.py:58-76): [sin | cos], float64 -> float32."""
-    omega = np.arange(embed_dim // 2, dtype=float)
-    omega /= embed_dim / 2.0
-    omega = 1.0 / 10000 ** omega
-    out = np.einsum("m,d->md", np.arange(n_pos).reshape(-1).astype(float), omega)
-    return torch.from_numpy(np.concatenate([np.sin(out), np.cos(out)], axis=1)).float()
-
-
-class Fast3RDecoder(_Params):
-    """fast3r.py:654-808.  No RoPE; additive image-index embedding; block LayerNorm eps 1e-5, dec_norm 1e-6."""
-
-    def __init__(self, random_image_idx_embedding, enc_embed_dim, embed_dim=768, num_heads=12, depth=12, mlp_ratio=4.0,
-                 qkv_bias=True, drop=0.0, attn_drop=0.0, attn_implementation="pytorch_naive",
-                 attn_bias_for_inference_enabled=True, max_image_idx=1000):
-        super().__init__()
-        if attn_implementation not in ("pytorch_naive", "flash_attention", "pytorch_auto"):
-            raise ValueError(f"Unknown attn_implementation: {attn_implementation}")
-        hd = embed_dim // num_heads
-        if embed_dim % num_heads != 0 or hd % 16 != 0 or not 16 <= hd <= 128:
-            # the reference takes any dim // num_heads (blocks.py:113-143); 64 runs the tuned attention kernels, the other multiples of
-            # 16 up to 128 (model_scaling_huge.yaml: 1280 / 16 = 80) the generic one (f3r_attn_generic.hip)
-            raise ValueError(f"fast3r_amd attention kernels are built for head_dim = a multiple of 16 up to 128 (got {embed_dim} / {num_heads})")
-        if embed_dim % 64 != 0:
-            raise ValueError(f"fast3r_amd: the fused QKV epilogue splits q / k / v on 64-column groups: embed_dim must be a multiple of 64 (got {embed_dim})")
-        self.embed_dim, self.num_heads, self.depth = embed_dim, num_heads, depth
-        self.random_image_idx_embedding = random_image_idx_embedding
-        self.attn_bias_for_inference_enabled = attn_bias_for_inference_enabled
-        self.decoder_embed = nn.Linear(enc_embed_dim, embed_dim, bias=True)
-        self.dec_blocks = nn.ModuleList([_Block(embed_dim, mlp_ratio, 1e-5, qkv_bias) for _ in range(depth)])
-        # The reference table has 1000 rows (fast3r.py:691-697) and therefore fails for N > 1000 views
-        # (SURVEY.md section 0.7).  Same formula, more rows when asked for: ids < 1000 are bit-identical.
-        self.register_buffer("image_idx_emb", sincos_1d_table(embed_dim, max_image_idx), persistent=False)
-        self.dec_norm = nn.LayerNorm(embed_dim, eps=1e-6)
-
-    def attention_scale(self, training: bool) -> float:
-        """blocks.py:116-124,151-154."""
-        hd = self.embed_dim // self.num_heads
-        if (not training) and self.attn_bias_for_inference_enabled:
-            return hd ** -0.5 * (1.0 * math.log(137) / math.log(20)) ** 0.5
-        return hd ** -0.5
-
-    def draw_image_ids(self, batch_size, num_views, rank=0):
-        """fast3r.py:702-743 (_generate_per_rank_generator + _get_random_image_pos), or 0..N-1 (fast3r.py:339-348,794-796).
-        Consumes exactly one value of the global torch CPU RNG when random ids are on, like the reference."""
-        if not self.random_image_idx_embedding:
-            return torch.arange(num_views)[None].repeat(batch_size, 1)
-        max_image_idx = self.image_idx_emb.shape[0] - 1
-        if num_views - 1 > max_image_idx:
-            raise ValueError(f"{num_views} views need an image-index table of at least {num_views} rows "
-                             f"(have {max_image_idx + 1}); build the decoder with max_image_idx >= {num_views}")
-        seed = torch.randint(0, 2 ** 32, (1,)).item()
-        g = torch.Generator()
-        g.manual_seed(seed + rank)
-        ids = torch.zeros(batch_size, num_views, dtype=torch.long)
-        for b in range(batch_size):
-            ids[b, 1:] = torch.randperm(max_image_idx, generator=g)[: num_views - 1] + 1
-        return ids
-
-
-class _RMSNorm(_Params):
-    def __init__(self, dim, eps=1e-6):
-        super().__init__()
-        self.eps = eps
-        self.weight = nn.Parameter(torch.ones(dim))  # llama.py:150-153
-
-
-class _LlamaAttention(_Params):
-    def __init__(self, dim, n_heads, n_kv_heads):
-        super().__init__()
-        hd = dim // n_heads
-        self.wq = nn.Linear(dim, n_heads * hd, bias=False)     # llama.py:195-198
-        self.wk = nn.Linear(dim, n_kv_heads * hd, bias=False)
-        self.wv = nn.Linear(dim, n_kv_heads * hd, bias=False)
-        self.wo = nn.Linear(n_heads * hd, dim, bias=False)
-
-
-class _LlamaFeedForward(_Params):
-    def __init__(self, dim, hidden_dim, multiple_of, ffn_dim_multiplier):
-        super().__init__()
-        hidden_dim = int(2 * hidden_dim / 3)                   # llama.py:273-277
-        if ffn_dim_multiplier is not None:
-            hidden_dim = int(ffn_dim_multiplier * hidden_dim)
-        hidden_dim = multiple_of * ((hidden_dim + multiple_of - 1) // multiple_of)
-        self.w1 = nn.Linear(dim, hidden_dim, bias=False)
-        self.w2 = nn.Linear(hidden_dim, dim, bias=False)
-        self.w3 = nn.Linear(dim, hidden_dim, bias=False)
-
-
-class _LlamaBlock(_Params):
-    def __init__(self, dim, n_heads, n_kv_heads, multiple_of, ffn_dim_multiplier, norm_eps):
-        super().__init__()
-        self.attention = _LlamaAttention(dim, n_heads, n_kv_heads)                       # llama.py:323-326
-        self.feed_forward = _LlamaFeedForward(dim, 4 * dim, multiple_of, ffn_dim_multiplier)  # llama.py:327-332
-        self.attention_norm = _RMSNorm(dim, norm_eps)
-        self.ffn_norm = _RMSNorm(dim, norm_eps)
-
-
-class LlamaDecoder(_Params):
-    """fast3r.py:810-968 (the `llama_dec` experiment, configs/experiment/llama_dec/llama_dec.yaml): pre-norm RMSNorm blocks with SwiGLU,
-    bias-free projections, rotary embedding of q / k by the IMAGE id of a token's view (all patches of a view share one angle set), a
-    learnable embedding added to the tokens of view 0 before every layer, final RMSNorm.  Bidirectional (the released config) or
-    causal attention; grouped-query attention with any n_kv_heads that divides n_heads (incl. 1: multi-query); head_dim must be 64."""
-
-    def __init__(self, random_image_idx_embedding, enc_embed_dim, embed_dim=4096, n_layers=32, n_heads=32, n_kv_heads=None,
-                 multiple_of=256, ffn_dim_multiplier=None, norm_eps=1e-5, rope_theta=10000, max_seq_len=1000, is_causal=False,
-                 depth_init=True, **kwargs):
-        super().__init__()
-        if embed_dim % n_heads != 0 or embed_dim // n_heads != 64:
-            raise ValueError("fast3r_amd kernels are built for head_dim 64")
-        n_kv_heads = n_heads if n_kv_heads is None else int(n_kv_heads)
-        if n_heads % n_kv_heads != 0:
-            raise ValueError(f"n_heads ({n_heads}) must be a multiple of n_kv_heads ({n_kv_heads})")  # repeat_kv, llama.py:125-134,196
-        self.embed_dim, self.num_heads, self.depth = embed_dim, n_heads, n_layers
-        self.n_kv_heads, self.is_causal = n_kv_heads, bool(is_causal)
-        self.random_image_idx_embedding = random_image_idx_embedding
-        self.rope_theta, self.norm_eps = rope_theta, norm_eps
-        self.view0_embed = nn.Parameter(torch.zeros(embed_dim))                          # fast3r.py:841-842
-        nn.init.normal_(self.view0_embed, mean=0.0, std=0.02)
-        self.decoder_embed = nn.Linear(enc_embed_dim, embed_dim, bias=True)              # :845
-        self.layers = nn.ModuleList([_LlamaBlock(embed_dim, n_heads, n_kv_heads, multiple_of, ffn_dim_multiplier, norm_eps)
-                                     for _ in range(n_layers)])                          # :848-852
-        self.norm = _RMSNorm(embed_dim, norm_eps)                                        # :854
-        # precompute_freqs_cis (llama.py:41-60) as [cos (32) | sin (32)] per position instead of complex64; a plain attribute, not a
-        # buffer, like the reference's precomputed_freqs_cis (fast3r.py:837)
-        hd = embed_dim // n_heads
-        freqs = 1.0 / (rope_theta ** (torch.arange(0, hd, 2)[: hd // 2].float() / hd))
-        ang = torch.outer(torch.arange(max_seq_len).float(), freqs).float()
-        self.image_idx_emb = torch.cat([ang.cos(), ang.sin()], dim=1)
-
-    def attention_scale(self, training: bool) -> float:
-        return (self.embed_dim // self.num_heads) ** -0.5  # F.scaled_dot_product_attention default (llama.py:239)
-
-    draw_image_ids = Fast3RDecoder.draw_image_ids  # same RNG recipe (fast3r.py:856-897 == :702-743)
-
-
-# within a 64-wide head: destination position -> source dim, so that the reference's complex pairs (2j, 2j+1) land where the QKV
-# epilogue rotates (rope_mode 1: dims [0,32) pair i with i+16 using table columns 0-15, dims [32,64) likewise with columns 16-31).
-# The same permutation on q and k leaves every q . k unchanged.
-_ROPE_PERM = [2 * j for j in range(16)] + [2 * j + 1 for j in range(16)] + [2 * j for j in range(16, 32)] + [2 * j + 1 for j in range(16, 32)]
-
-
-class _RCU(_Params):
-    def __init__(self, f):
-        super().__init__()
-        self.conv1 = nn.Conv2d(f, f, 3, padding=1)  # dpt_block.py:105-123
-        self.conv2 = nn.Conv2d(f, f, 3, padding=1)
-
-
-class _Fusion(_Params):
-    def __init__(self, f):
-        super().__init__()
-        self.out_conv = nn.Conv2d(f, f, 1)  # dpt_block.py:180-188
-        self.resConfUnit1 = _RCU(f)
-        self.resConfUnit2 = _RCU(f)
-
-
-class _DPT(_Params):
-    """Parameter layout of DPTOutputAdapter_fix (heads/dpt_head.py:28-40; croco/models/dpt_block.py:315-490)."""
-
-    def __init__(self, num_channels, feature_dim, last_dim, hooks, dim_tokens, patch_size, layer_dims=(96, 192, 384, 768)):
-        super().__init__()
-        self.hooks, self.patch_size, self.num_channels = hooks, patch_size, num_channels
-        self.feature_dim, self.last_dim, self.layer_dims = feature_dim, last_dim, list(layer_dims)
-        ld = layer_dims
-        scratch = _Params()
-        for i in range(4):
-            setattr(scratch, f"layer{i + 1}_rn", nn.Conv2d(ld[i], feature_dim, 3, padding=1, bias=False))
-        scratch.layer_rn = nn.ModuleList([getattr(scratch, f"layer{i + 1}_rn") for i in range(4)])  # aliases
-        for i in range(1, 5):
-            setattr(scratch, f"refinenet{i}", _Fusion(feature_dim))
-        self.scratch = scratch
-        self.head = nn.Sequential(nn.Conv2d(feature_dim, feature_dim // 2, 3, padding=1), nn.Identity(),
-                                  nn.Conv2d(feature_dim // 2, last_dim, 3, padding=1), nn.Identity(),
-                                  nn.Conv2d(last_dim, num_channels, 1))
-        self.act_postprocess = nn.ModuleList([
-            nn.Sequential(nn.Conv2d(dim_tokens[0], ld[0], 1), nn.ConvTranspose2d(ld[0], ld[0], 4, stride=4)),
-            nn.Sequential(nn.Conv2d(dim_tokens[1], ld[1], 1), nn.ConvTranspose2d(ld[1], ld[1], 2, stride=2)),
-            nn.Sequential(nn.Conv2d(dim_tokens[2], ld[2], 1)),
-            nn.Sequential(nn.Conv2d(dim_tokens[3], ld[3], 1), nn.Conv2d(ld[3], ld[3], 3, stride=2, padding=1)),
-        ])
-
-
-class PixelwiseTaskWithDPT(_Params):
-    """heads/dpt_head.py:93-129 (parameters under `.dpt`)."""
-
-    def __init__(self, *, hooks_idx, dim_tokens, num_channels, feature_dim, last_dim, patch_size, depth_mode, conf_mode):
-        super().__init__()
-        self.depth_mode, self.conf_mode = depth_mode, conf_mode
-        self.dpt = _DPT(num_channels, feature_dim, last_dim, hooks_idx, dim_tokens, patch_size)
-
-
-# ======================================================================================= packed (device) weights
-class _PackedBlock:
-    __slots__ = ("n1w", "n1b", "n2w", "n2b", "eps", "qkv_w", "qkv_b", "proj_w", "proj_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b",
-                 "rms", "rope_mode", "swiglu_hidden", "q_dim", "kv_dim", "kv_group", "causal", "head_dim", "fc1_split",
-                 "fc1_w8", "fc1_ws", "fc2_w8", "fc2_ws",   # the MLP weights with their low plane in fp8 (Fast3R.low_plane = "fp8"), or None
-                 "qk_w8", "qk_ws", "v_w2")                 # ... and the q | k rows of the QKV weight; its v rows as two fp16 planes
-
-    def __init__(self):
-        self.fc1_w8 = self.fc1_ws = self.fc2_w8 = self.fc2_ws = self.qk_w8 = self.qk_ws = self.v_w2 = None
-        self.rms, self.rope_mode, self.swiglu_hidden = False, 0, 0
-        self.fc1_split = None  # None: like every other projection of the block
-        self.head_dim = 64  # the Fast3R fusion decoder may have another width (model_scaling_huge.yaml: 80)
-        self.q_dim, self.kv_dim, self.kv_group, self.causal = 0, None, 1, False  # grouped-query / causal attention (LlamaDecoder only)
-
-
-def _f32(t):
-    return None if t is None else t.detach().float().contiguous()
-
-
-def _pack_block(blk: _Block, lp, split=False, head_dim=64, fc1_split=None, f8=False):
-    p = _PackedBlock()
-    p.head_dim = head_dim
-    p.n1w, p.n1b, p.n2w, p.n2b = _f32(blk.norm1.weight), _f32(blk.norm1.bias), _f32(blk.norm2.weight), _f32(blk.norm2.bias)
-    p.eps = blk.norm1.eps
-    p.qkv_w, p.qkv_b = ops.pack_linear_weight(blk.attn.qkv.weight.detach().float(), lp, split), _f32(blk.attn.qkv.bias)
-    p.proj_w, p.proj_b = ops.pack_linear_weight(blk.attn.proj.weight.detach().float(), lp, split), _f32(blk.attn.proj.bias)
-    # fc1_split False = fc1 single-plane inside "high" (Fast3R.high_fc1_planes = False): measured +3.5 % views/s at N = 100 for TWICE the
-    # distance to the fp32 path on the real-size stress model (4.8e-4 / 6.1e-4 against 2.4e-4 / 2.8e-4), so it is an experiment knob, not
-    # the default (oracle/precision_study.py per-role run, DESIGN.md section 3 (Precision modes))
-    p.fc1_split = bool(split) if fc1_split is None else bool(fc1_split)
-    p.fc1_w, p.fc1_b = ops.pack_linear_weight(blk.mlp.fc1.weight.detach().float(), lp, p.fc1_split), _f32(blk.mlp.fc1.bias)
-    p.fc2_w, p.fc2_b = ops.pack_linear_weight(blk.mlp.fc2.weight.detach().float(), lp, split), _f32(blk.mlp.fc2.bias)
-    # Fast3R.low_plane = "fp8" (precision "high", fp16): fc1's weight a second time as rows [K fp16 hi | K fp8 low plane] + one scale per output
-    # channel (f3r.h F3R_SPLIT_W2F8); the block uses it whenever its token count is a multiple of 256, the two-fp16-plane pack otherwise
-    w1 = blk.mlp.fc1.weight.detach().float()
-    w2_ = blk.mlp.fc2.weight.detach().float()
-    if f8 and split and lp == torch.float16 and p.fc1_split and w1.shape[1] % 128 == 0 and w1.shape[0] % 256 == 0 and w2_.shape[0] % 256 == 0:
-        p.fc1_w8, p.fc1_ws = ops.pack_linear_weight_f8(w1)
-        p.fc2_w8, p.fc2_ws = ops.pack_linear_weight_f8(w2_)
-    wq = blk.attn.qkv.weight.detach().float()
-    Dm = wq.shape[0] // 3
-    if f8 and split and lp == torch.float16 and wq.shape[1] % 128 == 0 and Dm % 256 == 0 and head_dim == 64:
-        p.qk_w8, p.qk_ws = ops.pack_linear_weight_f8(wq[:2 * Dm])
-        p.v_w2 = ops.pack_linear_weight(wq[2 * Dm:], lp, True)
-    return p
-
-
-def _pack_dino_block(blk: _DinoBlock, lp, split=False):
-    """DINOv2 block -> the packed fields of a ViT block.  LayerScale is folded into the projection that precedes it:
-    gamma * (W a + b) = (gamma[:, None] * W) a + gamma * b -- exact in real arithmetic, no epilogue change."""
-    p = _PackedBlock()
-    p.n1w, p.n1b, p.n2w, p.n2b = _f32(blk.norm1.weight), _f32(blk.norm1.bias), _f32(blk.norm2.weight), _f32(blk.norm2.bias)
-    p.eps = blk.norm1.eps
-    g1, g2 = blk.ls1.gamma.detach().float(), blk.ls2.gamma.detach().float()
-    p.qkv_w, p.qkv_b = ops.pack_linear_weight(blk.attn.qkv.weight.detach().float(), lp, split), _f32(blk.attn.qkv.bias)
-    p.proj_w = ops.pack_linear_weight(g1[:, None] * blk.attn.proj.weight.detach().float(), lp, split)
-    p.proj_b = (g1 * blk.attn.proj.bias.detach().float()).contiguous()
-    p.fc1_w, p.fc1_b = ops.pack_linear_weight(blk.mlp.fc1.weight.detach().float(), lp, split), _f32(blk.mlp.fc1.bias)
-    p.fc2_w = ops.pack_linear_weight(g2[:, None] * blk.mlp.fc2.weight.detach().float(), lp, split)
-    p.fc2_b = (g2 * blk.mlp.fc2.bias.detach().float()).contiguous()
-    return p
-
-
-def _pack_llama_block(blk: _LlamaBlock, n_heads, lp, split=False, n_kv_heads=None, causal=False):
-    """LlamaDecoder layer -> the same packed fields as a ViT block: [wq; wk; wv] as one QKV matrix (q / k rows permuted per head, see
-    _ROPE_PERM), [w1; w3] stacked for one up-projection GEMM, no biases, RMSNorm weights."""
-    p = _PackedBlock()
-    p.rms, p.rope_mode = True, 1
-    p.n1w, p.n1b, p.n2w, p.n2b = _f32(blk.attention_norm.weight), None, _f32(blk.ffn_norm.weight), None
-    p.eps = blk.attention_norm.eps
-    n_kv_heads = n_heads if n_kv_heads is None else n_kv_heads
-    perm = torch.tensor([h * 64 + d for h in range(n_heads) for d in _ROPE_PERM])
-    perm_kv = torch.tensor([h * 64 + d for h in range(n_kv_heads) for d in _ROPE_PERM])
-    wq, wk, wv = (m.weight.detach().float() for m in (blk.attention.wq, blk.attention.wk, blk.attention.wv))
-    p.qkv_w, p.qkv_b = ops.pack_linear_weight(torch.cat([wq[perm], wk[perm_kv], wv], dim=0), lp, split), None
-    if n_kv_heads != n_heads:
-        p.q_dim, p.kv_dim, p.kv_group = n_heads * 64, n_kv_heads * 64, n_heads // n_kv_heads
-    p.causal = bool(causal)
-    p.proj_w, p.proj_b = ops.pack_linear_weight(blk.attention.wo.weight.detach().float(), lp, split), None
-    w1, w3 = blk.feed_forward.w1.weight.detach().float(), blk.feed_forward.w3.weight.detach().float()
-    p.swiglu_hidden = w1.shape[0]
-    p.fc1_w, p.fc1_b = ops.pack_linear_weight(torch.cat([w1, w3], dim=0), lp, split), None
-    p.fc2_w, p.fc2_b = ops.pack_linear_weight(blk.feed_forward.w2.weight.detach().float(), lp, split), None
-    return p
-
-
-class _PackedHead:
-    pass
-
-
-class _ConvW:
-    """A packed 3x3 convolution weight: `w` for split None / "x3" (ops.pack_conv3x3_weight) and, when the head runs its correction products on the
-    fp8 MFMA (Fast3R.head_corrections = "fp8") and Cin % 128 == 0, `w8` / `scale` for split "x3f8" (ops.pack_conv3x3_weight_f8)."""
-    __slots__ = ("w", "w8", "scale")
-
-    def __init__(self, w, w8=None, scale=None):
-        self.w, self.w8, self.scale = w, w8, scale
-
-
-def _pack_head(head: PixelwiseTaskWithDPT, lp, split=False, f8=False):
-    d = head.dpt
-    h = _PackedHead()
-    ap = d.act_postprocess
-    lin = lambda w: ops.pack_linear_weight(w.detach().float(), lp, split)
-
-    def c33(w):
-        w = w.detach().float()
-        if f8 and split and lp == torch.float16 and w.shape[1] % 128 == 0:
-            return _ConvW(ops.pack_conv3x3_weight(w, lp, split), *ops.pack_conv3x3_weight_f8(w))
-        return _ConvW(ops.pack_conv3x3_weight(w, lp, split))
-    h.a_w = [lin(ap[i][0].weight) for i in range(4)]
-    h.a_b = [_f32(ap[i][0].bias) for i in range(4)]
-    # The transposed convolutions write their output with the channel count rounded up to 64 (layer_dims[0] = 96 -> 128 zero-weight / zero-bias
-    # channels, matched by zero input channels in layer1_rn's weight: exact): the 3x3 convolution behind them then has a channel count the
-    # 256-tile kernel's LDS-DMA staging takes (a ragged one ran on the 128-tile kernel through registers: 13.8 of 126 ms of head convolutions at N = 100).
-    def convT_padded(m):
-        w, b = m.weight.detach().float(), m.bias.detach().float()
-        pad = ops.round_up(w.shape[1], 64) - w.shape[1]
-        if pad:
-            w, b = nn.functional.pad(w, (0, 0, 0, 0, 0, pad)), nn.functional.pad(b, (0, pad))
-        return ops.pack_convT_weight(w, b, lp, split) + (w.shape[1],)
-
-    def rn(i):
-        w = getattr(d.scratch, f"layer{i + 1}_rn").weight.detach().float()
-        pad = ops.round_up(w.shape[1], 64) - w.shape[1] if i < 2 else 0   # (levels 0 / 1 read the transposed convolutions' padded outputs)
-        return c33(nn.functional.pad(w, (0, 0, 0, 0, 0, pad)) if pad else w)
-    h.t0_w, h.t0_b, h.t0_cout = convT_padded(ap[0][1])
-    h.t1_w, h.t1_b, h.t1_cout = convT_padded(ap[1][1])
-    h.c3_w, h.c3_b = c33(ap[3][1].weight), _f32(ap[3][1].bias)
-    h.rn_w = [rn(i) for i in range(4)]
-    h.ref = []
-    for i in range(1, 5):
-        r = getattr(d.scratch, f"refinenet{i}")
-        h.ref.append(dict(
-            u1c1=(c33(r.resConfUnit1.conv1.weight), _f32(r.resConfUnit1.conv1.bias)),
-            u1c2=(c33(r.resConfUnit1.conv2.weight), _f32(r.resConfUnit1.conv2.bias)),
-            u2c1=(c33(r.resConfUnit2.conv1.weight), _f32(r.resConfUnit2.conv1.bias)),
-            u2c2=(c33(r.resConfUnit2.conv2.weight), _f32(r.resConfUnit2.conv2.bias)),
-            out=(lin(r.out_conv.weight), _f32(r.out_conv.bias))))
-    h.h0_w, h.h0_b = c33(d.head[0].weight), _f32(d.head[0].bias)
-    h.h2_w, h.h2_b = c33(d.head[2].weight), _f32(d.head[2].bias)
-    h.h4_w = d.head[4].weight.detach().float().reshape(d.num_channels, -1).contiguous()
-    h.h4_b = _f32(d.head[4].bias)
-    h.dims = d.layer_dims
-    h.feature_dim, h.last_dim, h.num_channels, h.patch_size = d.feature_dim, d.last_dim, d.num_channels, d.patch_size
-    h.depth_mode, h.conf_mode = head.depth_mode, head.conf_mode
-    h.fin = None
-    if d.last_dim == 128 and h.h4_w.shape[1] == 128:  # the fused tail (f3r_gemm_args.fin_w): head[4] as a zero-padded [4][128] matrix
-        try:
-            h.fin = ops.dpt_fin_args(h.h4_w, h.h4_b, h.conf_mode, tuple(h.depth_mode))
-        except (ValueError, AssertionError):
-            h.fin = None  # an unsupported mode raises where the reference raises: in the head's own call (ops.dpt_final)
-    return h
+from .packing import _f32, _pack_block, _pack_dino_block, _pack_llama_block
+from .params import (_ROPE_PERM, CroCoEncoder, DinoEncoder, Fast3RDecoder, LlamaDecoder, PixelwiseTaskWithDPT,  # noqa: F401  (re-exported)
+                     sincos_1d_table)
+
+
+# ======================================================================================= operand format
+class OperandFormat(NamedTuple):
+    """Which operand format every launch of a forward takes: derived from the model's knobs by Fast3R._format(), once per _pack / forward.
+    The first five fields decide the packed bytes (pack_part: the weight-pack key); the whole record is part of the graph key."""
+    lp: torch.dtype                  # compute_dtype: the 16-bit MFMA operand type
+    planes: bool                     # split (hi + lo) weight planes and head activations: "high", "robust" and "exact"
+    low_f8: bool                     # the MLP / QKV weights a second time with their low plane in fp8 (low_plane)
+    fc1_planes: bool                 # fc1's weight as hi + lo planes (high_fc1_planes)
+    head_f8: bool                    # the heads' 3x3 convolutions packed for, and run with, their corrections in fp8 (head_corrections)
+    linear_split: Optional[str]      # split mode of the transformer's linear layers: weights only ("w2") in "high", both operands ("x3") in "robust" / "exact"
+    x3: bool                         # both operands of every GEMM / conv as hi + lo planes (three MFMA products): "robust" and "exact"
+    qk3: bool                        # "robust": the three-product attention kernels where a block can take them (Fast3R._qk3_ok) ...
+    qk3_planes: int                  # ... with 3 (robust_corrections "fp8") or 2 planes per q / k row ...
+    qk3_encoder: bool                # ... and also in the encoder's per-view attention (robust_encoder_attention "planes")
+    head_f8_min_rows: int
+    head_tail_fused_min_rows: int
+
+    @property
+    def pack_part(self):
+        return self[:5]
+
+
+def _fills_chip(rows, cols):
+    """Do the 256 x 256 output tiles of a [rows][cols] GEMM fill the chip (256 CUs) at least once?"""
+    return (rows // 256) * (cols // 256) >= 256
+
+
+def _planes(fmt, x_f32):
+    """fp32 -> (hi, lo) planes of the operand format; (lowp, None) in the formats without low planes."""
+    if fmt.planes:
+        return ops.cast_lp(x_f32, fmt.lp, want_lo=True)
+    return ops.cast_lp(x_f32, fmt.lp), None
+
+
+def _f8_gemms(pb, T, seq_len):
+    """Which GEMMs of a block over T tokens take their low plane in fp8 (Fast3R.low_plane) -> (q | k, fc1, fc2)."""
+    # the q | k launch with its low plane in fp8 (Fast3R.low_plane) where its 256 x 256 tiles fill the chip (from 8192 tokens on; the encoder's
+    # RoPE-2D rides in that launch's epilogue since round 5), V^T on two fp16 planes; sequences must be multiples of 256 tokens for the V^T tiles
+    qk = (pb.qk_w8 is not None and T % 256 == 0 and seq_len % 256 == 0 and pb.rope_mode == 0 and pb.q_dim == 0
+          and _fills_chip(T, pb.qk_w8.shape[0]))
+    # low plane in fp8 (Fast3R.low_plane): only the hand-scheduled 256 x 256-tile kernels read the [fp16 | fp8] rows, so a GEMM takes that form
+    # when its tiles fill the chip at least once (256 CUs): fc1 (4 D wide) from 4096 tokens on, fc2 from 16 384; below that the scene is
+    # launch- and occupancy-bound and the compiler-scheduled small-tile kernels win (N = 3: 118 us against 36 us per fc2, round-5 profile)
+    fc1 = pb.fc1_w8 is not None and T % 256 == 0 and not pb.swiglu_hidden and _fills_chip(T, pb.fc1_w8.shape[0])
+    return qk, fc1, fc1 and _fills_chip(T, pb.fc2_w8.shape[0])
 
 
 # ======================================================================================= the model
@@ -511,11 +102,9 @@ class _GraphCache:
             return None
         if model._orientation_plan(views)["any_portrait"]:  # also the eager path's argument checks (utils/misc.py:69), done on the host
             return None
-        # (the operand-format knobs are part of the key: a graph captured with another low_plane / high_fc1_planes would keep replaying the old
+        # (the whole operand format is part of the key: a graph captured with another low_plane / high_fc1_planes would keep replaying the old
         # packed weights after the model re-packed)
-        key = (len(views), tuple(imgs[0].shape), str(dev), model.compute_dtype, model.precision, model.max_parallel_views_for_head,
-               model.training, model._params_version(), model.low_plane, model.high_fc1_planes, model.head_corrections,
-               model.head_f8_min_rows, model.head_tail_fused_min_rows)
+        key = (len(views), tuple(imgs[0].shape), str(dev), model.max_parallel_views_for_head, model.training, model._params_version(), model._format())
         dec = model.decoder
         B = imgs[0].shape[0]
         if key not in self.entries:
@@ -664,30 +253,21 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
 
     # ---------------------------------------------------------------- construction (fast3r.py:72-157)
     def build_encoder(self, encoder_args):
-        if encoder_args["encoder_type"] == "croco":
-            a = deepcopy(dict(encoder_args))
-            a.pop("encoder_type")
-            self.encoder = CroCoEncoder(**a)
-        elif encoder_args["encoder_type"] == "dino_v2":
-            a = deepcopy(dict(encoder_args))
-            a.pop("encoder_type")
-            self.encoder = DinoEncoder(**a)  # fast3r.py:80-83
-        else:
+        a = deepcopy(dict(encoder_args))
+        kinds = {"croco": CroCoEncoder, "dino_v2": DinoEncoder}  # fast3r.py:80-83
+        if a.pop("encoder_type") not in kinds:
             raise ValueError(f"Unsupported encoder type: {encoder_args['encoder_type']}")
+        self.encoder = kinds[encoder_args["encoder_type"]](**a)
 
     def build_decoder(self, decoder_args):
         dt = decoder_args.get("decoder_type", "fast3r")
         self.decoder_args["decoder_type"] = dt
-        if dt == "fast3r":
-            a = deepcopy(dict(decoder_args))
-            a.pop("decoder_type", None)
-            self.decoder = Fast3RDecoder(**a)
-        elif dt == "llama":
-            a = deepcopy(dict(decoder_args))
-            a.pop("decoder_type", None)
-            self.decoder = LlamaDecoder(**a)
-        else:
+        kinds = {"fast3r": Fast3RDecoder, "llama": LlamaDecoder}
+        if dt not in kinds:
             raise ValueError(f"Unsupported decoder type: {dt}")
+        a = deepcopy(dict(decoder_args))
+        a.pop("decoder_type", None)
+        self.decoder = kinds[dt](**a)
 
     def build_head(self, head_args):
         self.output_mode, self.head_type = head_args["output_mode"], head_args["head_type"]
@@ -873,16 +453,6 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         version): call `invalidate_packed_weights()` after them."""
         return sum(p._version for p in self.parameters())
 
-    @property
-    def _hp(self):
-        """split (hi + lo) weight planes and head activations: "high", "robust" and "exact"."""
-        return self.precision in ("high", "robust", "exact")
-
-    @property
-    def _x3(self):
-        """both operands of every GEMM / conv as hi + lo planes (three MFMA products): "robust" and "exact"."""
-        return self.precision in ("robust", "exact")
-
     # "fp8" (the default; precision "high" with fp16 operands): the correction products A W_lo of the transformer's MLPs (fc1, fc2) run on the
     # block-scaled fp8 MFMA (f3r.h F3R_SPLIT_W2F8: 1.4x the matrix-pipe rate of a second fp16 plane; LayerNorm and fc1's GELU epilogue write the
     # fp8 copies beside their fp16 outputs) for every pass whose token count is a multiple of 256; "fp16": two fp16 planes everywhere.  Measured
@@ -913,54 +483,47 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
     head_tail_fused_min_rows = 4096
     high_fc1_planes = True   # False: fc1 weights single-plane in precision "high" (see _pack_block); changing it needs invalidate_packed_weights()
 
+    def _format(self):
+        """The knobs above + precision + compute_dtype -> the OperandFormat of the next _pack / forward (the ONE place that reads them)."""
+        p, lp = self.precision, self.compute_dtype
+        high_f16 = p == "high" and lp == torch.float16   # the fp8 correction products exist beside fp16 planes in "high" only
+        return OperandFormat(
+            lp=lp, planes=p != "fast", low_f8=high_f16 and self.low_plane == "fp8", fc1_planes=p != "fast" and (p != "high" or bool(self.high_fc1_planes)),
+            head_f8=high_f16 and self.head_corrections == "fp8", linear_split={"fast": None, "high": "w2", "robust": "x3", "exact": "x3"}[p], x3=p in ("robust", "exact"),
+            qk3=p == "robust", qk3_planes=3 if self.robust_corrections == "fp8" else 2, qk3_encoder=self.robust_encoder_attention == "planes",
+            head_f8_min_rows=self.head_f8_min_rows, head_tail_fused_min_rows=self.head_tail_fused_min_rows)
+
     @property
     def _head_f8(self):
-        return self.head_corrections == "fp8" and self.precision == "high" and self.compute_dtype == torch.float16
+        return self._format().head_f8
 
-    @property
-    def _fc1_split(self):
-        return None if (self.high_fc1_planes or self.precision != "high") else False
-
-    @property
-    def _sp(self):
-        """split mode of the transformer's linear layers: weights only ("w2") in "high", both operands ("x3") in "exact"."""
-        return {"fast": None, "high": "w2", "robust": "x3", "exact": "x3"}[self.precision]
-
-    def _pair(self, x_f32):
-        """fp32 -> (hi, lo) lowp planes."""
-        return ops.cast_lp(x_f32, self.compute_dtype, want_lo=True)
-
-    def _pack(self, device):
-        lp = self.compute_dtype
-        f8 = self.low_plane == "fp8" and self.precision == "high" and lp == torch.float16
-        key = (lp, self.precision, str(device), self._params_version(), f8, bool(self.high_fc1_planes), self._head_f8)
+    def _pack(self, device, fmt=None):
+        fmt = fmt or self._format()
+        lp, hp = fmt.lp, fmt.planes
+        key = (str(device), self._params_version(), fmt.pack_part)
         if self._packed is not None and self._packed["key"] == key:
             return self._packed
         alt = getattr(self, "_packed_alt", None)
         if alt is not None and alt["key"] == key:  # two packs are kept, so alternating inference(dtype=...) calls do not re-pack
             self._packed, self._packed_alt = alt, self._packed
             return self._packed
-        if self._packed is not None and self._packed["key"][3] != key[3]:  # parameters changed: both packs are stale
+        if self._packed is not None and self._packed["key"][1] != key[1]:  # parameters changed: both packs are stale
             self._packed = self._packed_alt = None
             self._graphs.clear()
         if alt is not None:  # a third format evicts the older pack: captured graphs may hold pointers into its weight tensors
             self._graphs.clear()
         self._packed_alt = self._packed
         enc, dec = self.encoder, self.decoder
-        hp = self._hp
         pk = dict(key=key)
-        if isinstance(enc, DinoEncoder):
-            vit = enc.model
-            pk["pe_w"] = ops.pack_linear_weight(vit.patch_embed.proj.weight.detach().float(), lp, hp)  # (D, 3*14*14 = 588) -> Kpad 640
-            pk["pe_b"] = _f32(vit.patch_embed.proj.bias)
-            pk["enc"] = [_pack_dino_block(b, lp, hp) for b in vit.blocks]
-            pk["enc_norm"] = (_f32(vit.norm.weight), _f32(vit.norm.bias), vit.norm.eps)
+        dino = isinstance(enc, DinoEncoder)
+        vit = enc.model if dino else enc
+        norm = vit.norm if dino else enc.enc_norm
+        pk["pe_w"] = ops.pack_linear_weight(vit.patch_embed.proj.weight.detach().float(), lp, hp)  # (DINOv2: (D, 3*14*14 = 588) -> Kpad 640)
+        pk["pe_b"] = _f32(vit.patch_embed.proj.bias)
+        pk["enc"] = [_pack_dino_block(b, lp, hp) for b in vit.blocks] if dino else [_pack_block(b, fmt) for b in enc.enc_blocks]
+        pk["enc_norm"] = (_f32(norm.weight), _f32(norm.bias), norm.eps)
+        if dino:
             pk["dino_pos"] = {}  # (h, w) -> interpolated position rows, filled on demand (_dino_pos)
-        else:
-            pk["pe_w"] = ops.pack_linear_weight(enc.patch_embed.proj.weight.detach().float(), lp, hp)
-            pk["pe_b"] = _f32(enc.patch_embed.proj.bias)
-            pk["enc"] = [_pack_block(b, lp, hp, fc1_split=self._fc1_split, f8=f8) for b in enc.enc_blocks]
-            pk["enc_norm"] = (_f32(enc.enc_norm.weight), _f32(enc.enc_norm.bias), enc.enc_norm.eps)
         pk["de_w"] = ops.pack_linear_weight(dec.decoder_embed.weight.detach().float(), lp, hp)
         pk["de_b"] = _f32(dec.decoder_embed.bias)
         if isinstance(dec, LlamaDecoder):
@@ -968,10 +531,10 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
             pk["dec_norm"] = (_f32(dec.norm.weight), None, dec.norm.eps)
             pk["view0"] = _f32(dec.view0_embed)
         else:
-            pk["dec"] = [_pack_block(b, lp, hp, dec.embed_dim // dec.num_heads, fc1_split=self._fc1_split, f8=f8) for b in dec.dec_blocks]
+            pk["dec"] = [_pack_block(b, fmt, dec.embed_dim // dec.num_heads) for b in dec.dec_blocks]
             pk["dec_norm"] = (_f32(dec.dec_norm.weight), _f32(dec.dec_norm.bias), dec.dec_norm.eps)
-        pk["head"] = _pack_head(self.downstream_head, lp, hp, self._head_f8)
-        pk["head_local"] = _pack_head(self.downstream_head_local, lp, hp, self._head_f8) if self.downstream_head_local is not None else None
+        pk["head"] = dpt_head._pack_head(self.downstream_head, fmt)
+        pk["head_local"] = dpt_head._pack_head(self.downstream_head_local, fmt) if self.downstream_head_local is not None else None
         self._packed = pk
         return pk
 
@@ -982,35 +545,31 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         return self._rope_cache[key]
 
     # ---------------------------------------------------------------- transformer block on the HIP kernels
-    def _block_ws(self, pb, T, D, n_seq, seq_len, dev, external_kv=False):
+    def _block_ws(self, fmt, pb, T, D, n_seq, seq_len, dev, external_kv=False):
         """Workspace of the blocks of one encoder pass / decoder sample: ONE allocation shared by all of its layers.  external_kv: K / V^T
         are written into the buffers of a KVExchange (view-sharded path), the workspace keeps no room for them."""
         hidden = pb.fc1_w.shape[0]  # rows of the (possibly stacked [w1; w3]) up-projection
-        f8_rows = (pb.fc1_w8 is not None or pb.qk_w8 is not None) and T % 256 == 0   # the pass may take the fp8-low-plane GEMMs (_block decides per GEMM)
-        return ops.BlockWorkspace(T, D, hidden, n_seq, seq_len, self.compute_dtype, dev, kv_dim=0 if external_kv else pb.kv_dim, f8_rows=f8_rows)
+        f8_rows = any(_f8_gemms(pb, T, seq_len))   # the pass takes fp8-low-plane GEMMs
+        return ops.BlockWorkspace(T, D, hidden, n_seq, seq_len, fmt.lp, dev, kv_dim=0 if external_kv else pb.kv_dim, f8_rows=f8_rows)
 
-    def _block(self, x, pb, n_heads, scale, seq_len, n_seq, rope, kv_exchange=None, ws=None, kv_tap=None):
+    def _block(self, fmt, x, pb, n_heads, scale, seq_len, n_seq, rope, kv_exchange=None, ws=None, kv_tap=None):
         """x: fp32 residual stream [n_seq*seq_len][D], updated in place.  blocks.py:236-239.  precision "high": every projection runs
         with split weights (hi + lo planes, split="w2"); the activations (LN output, attention output, MLP hidden) stay single.
         ws: the pass's BlockWorkspace (made here when absent): no per-layer allocation."""
-        lp = self.compute_dtype
-        if self._x3:
-            return self._block_exact(x, pb, n_heads, scale, seq_len, n_seq, rope, kv_exchange)
-        sp = "w2" if self.precision == "high" else None
+        lp, sp = fmt.lp, fmt.linear_split
+        if fmt.x3:
+            return self._block_exact(fmt, x, pb, n_heads, scale, seq_len, n_seq, rope, kv_exchange)
         D = x.shape[1]
         T = x.shape[0]
         if ws is None:
-            ws = self._block_ws(pb, T, D, n_seq, seq_len, x.device)
+            ws = self._block_ws(fmt, pb, T, D, n_seq, seq_len, x.device)
         q = ws.q
         if kv_exchange is None:
             k, vt = ws.k, ws.vt
             ldvt = vt.shape[-1]
         else:  # view-sharded: write K / V^T straight into the (padded, persistent) send buffers of the exchange
             k, vt = kv_exchange.k_loc, kv_exchange.vt_loc
-        # the q | k launch with its low plane in fp8 (Fast3R.low_plane) where its 256 x 256 tiles fill the chip (from 8192 tokens on; the encoder's
-        # RoPE-2D rides in that launch's epilogue since round 5), V^T on two fp16 planes; sequences must be multiples of 256 tokens for the V^T tiles
-        f8_qkv = (pb.qk_w8 is not None and T % 256 == 0 and seq_len % 256 == 0 and pb.rope_mode == 0 and pb.q_dim == 0
-                  and (T // 256) * (pb.qk_w8.shape[0] // 256) >= 256)
+        f8_qkv, f8_fc1, f8_fc2 = _f8_gemms(pb, T, seq_len)
         if f8_qkv:
             rows1 = ops.layernorm_f8(x, pb.n1w, pb.n1b, pb.eps, out_rows=ws.rows8(D), rms=pb.rms)
             ops.gemm_qkv(rows1, pb.qk_w8, pb.qkv_b, q, k, vt, seq_len, rope, q_scale=scale * ops.LOG2E, split="w2f8", w_scale=pb.qk_ws, w_aux=pb.v_w2)
@@ -1058,12 +617,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
                 ops.attention(q, o, n_heads, scale, [kv_exchange.local_segment()], tq=seq_len, q_prescaled=True, **gqa)
             sharding.end_layer(kv_exchange)
         ops.gemm(o, pb.proj_w, bias=pb.proj_b, res_f32=x, out_f32=x, split=sp)
-        # low plane in fp8 (Fast3R.low_plane): only the hand-scheduled 256 x 256-tile kernels read the [fp16 | fp8] rows, so a GEMM takes that form
-        # when its tiles fill the chip at least once (256 CUs): fc1 (4 D wide) from 4096 tokens on, fc2 from 16 384; below that the scene is
-        # launch- and occupancy-bound and the compiler-scheduled small-tile kernels win (N = 3: 118 us against 36 us per fc2, round-5 profile)
-        f8_fc1 = pb.fc1_w8 is not None and T % 256 == 0 and not pb.swiglu_hidden and (T // 256) * (pb.fc1_w8.shape[0] // 256) >= 256
         if f8_fc1:
-            f8_fc2 = (T // 256) * (pb.fc2_w8.shape[0] // 256) >= 256
             rows = ops.layernorm_f8(x, pb.n2w, pb.n2b, pb.eps, out_rows=ws.rows8(D), rms=pb.rms)
             if f8_fc2:   # fc1's GELU epilogue writes rows [4 D fp16 | 4 D fp8], fc2 runs on them
                 _, hid = ops.gemm(rows, pb.fc1_w8, bias=pb.fc1_b, act="gelu", out_lp=ws.hid8(), split="w2f8", w_scale=pb.fc1_ws, out_f8_rows=True)
@@ -1081,27 +635,26 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         ops.gemm(hid, pb.fc2_w, bias=pb.fc2_b, res_f32=x, out_f32=x, split=sp)
         return x
 
-    def _block_exact(self, x, pb, n_heads, scale, seq_len, n_seq, rope, kv_exchange):
+    def _block_exact(self, fmt, x, pb, n_heads, scale, seq_len, n_seq, rope, kv_exchange):
         """precision "exact": the same block with every operand as hi + lo planes and fp32 attention.  LayerNorm / RMSNorm -> fp32 -> planes;
         QKV through the generic epilogue into an fp32 [T][Dq + 2 Dkv] buffer (+ rotary embedding in place, 2-D or per-view); f3r_attn_f32_ex
         (grouped-query heads, causal by absolute position) -> planes; proj / fc1 (+GELU | SwiGLU gate, planes out) / fc2 as X3 GEMMs with the
         fp32 residual epilogue.  View-sharded: the fp32 K and V rows of all ranks are all-gathered (blocking: this is the validation mode)
         and the rank's queries attend over them in one launch."""
-        lp = self.compute_dtype
+        lp = fmt.lp
         T = x.shape[0]
         _, hf = ops.layernorm(x, pb.n1w, pb.n1b, pb.eps, lp, want_lp=False, want_f32=True, rms=pb.rms)
-        h, hl = self._pair(hf)
+        h, hl = _planes(fmt, hf)
         qkv, _ = ops.gemm(h, pb.qkv_w, bias=pb.qkv_b, want_f32=True, split="x3", a_lo=hl)
         n_kv = n_heads // pb.kv_group
         if rope is not None and T:
             ops.rope_f32(qkv, n_heads + n_kv, max(1, seq_len), rope, pb.rope_mode)
         gqa = dict(head_dim=pb.head_dim, kv_group=pb.kv_group, causal=pb.causal)
-        if (kv_exchange is None and self.precision == "robust" and self._qk3_ok(pb, n_seq, seq_len)
-                and (n_seq == 1 or self.robust_encoder_attention == "planes")):
+        if kv_exchange is None and fmt.qk3 and self._qk3_ok(fmt, pb, n_seq, seq_len) and (n_seq == 1 or fmt.qk3_encoder):
             # precision "robust": Q and K as hi + lo fp16 planes, three products per score block on the hand-scheduled kernel (f3r_attn_args.qk_planes),
             # P and V single fp16; the launch parks its softmax state and a small pass turns it into the planes of the attention output
             # (robust_corrections "fp8": the two correction products on the block-scaled fp8 MFMA -- rows [hi fp16 | e4m3(hi) | e4m3(lo 2^12)])
-            planes = 3 if self.robust_corrections == "fp8" else 2
+            planes = fmt.qk3_planes
             qp, kp, vt = ops.qkv_planes(qkv, n_heads, n_kv, n_seq, seq_len, scale * ops.LOG2E, lp, planes=planes)
             state = ops.attention_state(T, n_heads, x.device, pb.head_dim)
             ldvt_ = vt.shape[-1]
@@ -1121,7 +674,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
                 o = ol = torch.empty((0, Dq), dtype=lp, device=x.device)
         ops.gemm(o, pb.proj_w, bias=pb.proj_b, res_f32=x, out_f32=x, split="x3", a_lo=ol)
         _, hf = ops.layernorm(x, pb.n2w, pb.n2b, pb.eps, lp, want_lp=False, want_f32=True, out_f32=hf, rms=pb.rms)
-        h, hl = self._pair(hf)
+        h, hl = _planes(fmt, hf)
         if pb.swiglu_hidden:  # LlamaDecoder FeedForward: w2(silu(w1 x) * w3 x) (llama.py:284)
             ab, _ = ops.gemm(h, pb.fc1_w, want_f32=True, split="x3", a_lo=hl)
             hid, hid_lo = ops.silu_mul_f32(ab, pb.swiglu_hidden, lp)
@@ -1130,20 +683,24 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         ops.gemm(hid, pb.fc2_w, bias=pb.fc2_b, res_f32=x, out_f32=x, split="x3", a_lo=hid_lo)
         return x
 
-    def _qk3_ok(self, pb, n_seq, seq_len):
+    def _qk3_ok(self, fmt, pb, n_seq, seq_len):
         """can this block's attention take the three-product kernels (f3r_attn_asm_qk3{,f8}_f16)?  head_dim 64, fp16, no causal mask, whole 64-key
         tiles per sequence, at least one wave of queries, a power-of-two head group; any number of sequences (the fusion decoder's one, the
         encoder's one per view: the kernels park their softmax state per sequence).  Everything else in precision "robust" -- odd token counts
         (DINOv2's class token), causal Llama decoders, sharded models -- runs the fp32 attention of precision "exact" (more exact, slower)."""
         g = pb.kv_group
-        return (self.compute_dtype == torch.float16 and pb.head_dim == 64 and not pb.causal and n_seq >= 1 and seq_len >= 64 and seq_len % 64 == 0
+        return (fmt.lp == torch.float16 and pb.head_dim == 64 and not pb.causal and n_seq >= 1 and seq_len >= 64 and seq_len % 64 == 0
                 and n_seq < 65536 and g >= 1 and (g & (g - 1)) == 0)
 
-    def _planes(self, x_f32):
-        """fp32 -> the operand format of the DPT heads: (hi, lo) planes in "high" precision, (lowp, None) otherwise."""
-        if self._hp:
-            return ops.cast_lp(x_f32, self.compute_dtype, want_lo=True)
-        return ops.cast_lp(x_f32, self.compute_dtype), None
+    @staticmethod
+    def _norm_planes(fmt, x, norm, rms=False, out_lp=None, f32=False):
+        """The final LayerNorm / RMSNorm of a pass (norm = its packed (weight, bias, eps)) -> the (hi, lo) planes the heads read; (lowp, None),
+        written to out_lp when given, in the formats without low planes.  f32: (the fp32 rows, None) instead, i.e. before that rounding."""
+        w_, b_, eps = norm
+        if fmt.planes or f32:
+            _, y = ops.layernorm(x, w_, b_, eps, fmt.lp, want_lp=False, want_f32=True, rms=rms)
+            return (y.clone(), None) if f32 else _planes(fmt, y)
+        return ops.layernorm(x, w_, b_, eps, fmt.lp, out_lp=out_lp, rms=rms)[0], None
 
     def _dino_pos(self, pk, h, w, dev):
         """DINOv2 `interpolate_pos_encoding` (models/vision_transformer.py) for an h x w token grid -> (cls row + pos[0] (D,), patch rows
@@ -1164,101 +721,74 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
             pk["dino_pos"][key] = (cls_row, patch[0].contiguous())
         return pk["dino_pos"][key]
 
-    def _encode_dino(self, imgs, pk):
-        """DINOv2 forward_features -> x_norm_patchtokens (DinoEncoder._process_images, fast3r.py:636-651) for a batch of same-size,
+    def _patch_lo(self, fmt, imgs, ps, ld_out):
+        """precision "exact": the low plane of the im2col rows = the im2col rows of the image's low plane (patchify only moves and rounds:
+        its output is lowp(img), so lowp(img - lowp(img)) patchified is exactly the remainder plane); None otherwise."""
+        if not fmt.x3:
+            return None
+        _, lo = ops.cast_lp(imgs.contiguous(), fmt.lp, want_lo=True)
+        return ops.patchify(lo.float(), ps, fmt.lp, ld_out=ld_out)
+
+    def _encode(self, fmt, imgs, pk):
+        """CroCoEncoder.forward (fast3r.py:549-559) for a batch of same-size images -> enc_norm output [NV*P][D] as (lowp, low plane or
+        None).  The high plane alone feeds decoder_embed; both planes are hook 0 of the heads in "high" precision.
+        DinoEncoder: DINOv2 forward_features -> x_norm_patchtokens (DinoEncoder._process_images, fast3r.py:636-651) for a batch of same-size,
         upright images: patch embedding (k = s = 14) + [cls] + resized position table, the ViT blocks (no RoPE; LayerScale folded into
-        the packed weights), final LayerNorm, patch tokens only.  Same return convention as _encode."""
-        lp = self.compute_dtype
-        hp, sp = self._hp, self._sp
-        vit = self.encoder.model
+        the packed weights), final LayerNorm, patch tokens only."""
+        lp, hp, sp = fmt.lp, fmt.planes, fmt.linear_split
+        dino = isinstance(self.encoder, DinoEncoder)
+        enc = self.encoder.model if dino else self.encoder
         NV, _, H, W = imgs.shape
-        ps, D = vit.patch_size, vit.embed_dim
-        assert H % ps == 0 and W % ps == 0, f"Input image size ({H}, {W}) is not a multiple of the patch size ({ps})"
+        ps, D = enc.patch_size, enc.embed_dim
+        if dino:
+            assert H % ps == 0 and W % ps == 0, f"Input image size ({H}, {W}) is not a multiple of the patch size ({ps})"
+        else:
+            assert H % ps == 0, f"Input image height ({H}) is not a multiple of patch size ({ps})."  # patch_embed.py:27-32
+            assert W % ps == 0, f"Input image width ({W}) is not a multiple of patch size ({ps})."
         h, w = H // ps, W // ps
         P = h * w
-        cls_row, pos_rows = self._dino_pos(pk, h, w, imgs.device)
+        seq = P + dino  # DINOv2: [cls | patches] per image
+        if dino:
+            cls_row, pos_rows = self._dino_pos(pk, h, w, imgs.device)
+        rope = None if dino else self._rope(max(h, w), imgs.device) + (w,)
+        kpad = pk["pe_w"].shape[1] // (2 if hp else 1) if dino else 0
         out = torch.empty((NV * P, D), dtype=lp, device=imgs.device)
         out_lo = torch.empty_like(out) if hp else None
-        kpad = pk["pe_w"].shape[1] // (2 if hp else 1)
         step = max(1, self.max_parallel_views_for_encoder)
         for v0 in range(0, NV, step):
             v1 = min(NV, v0 + step)
             n = v1 - v0
             a = ops.patchify(imgs[v0:v1].contiguous(), ps, lp, ld_out=kpad)
-            tok, _ = ops.gemm(a, pk["pe_w"], bias=pk["pe_b"], res_f32=pos_rows.repeat(n, 1), want_f32=True, split=sp,
-                              a_lo=self._patch_lo(imgs[v0:v1], ps, kpad))
-            x = torch.empty((n, 1 + P, D), dtype=torch.float32, device=imgs.device)  # [cls | patches] per image
-            x[:, 0] = cls_row
-            x[:, 1:] = tok.view(n, P, D)
-            x = x.view(n * (1 + P), D)
-            ws = self._block_ws(pk["enc"][0], x.shape[0], D, n, 1 + P, imgs.device)
-            for pb in pk["enc"]:
-                self._block(x, pb, vit.num_heads, 64 ** -0.5, 1 + P, n, None, ws=ws)
-            w_, b_, eps = pk["enc_norm"]
-            if hp:
-                _, y = ops.layernorm(x, w_, b_, eps, lp, want_lp=False, want_f32=True)
-                hi, lo = ops.cast_lp(y, lp, want_lo=True)
-                out[v0 * P:v1 * P].view(n, P, D).copy_(hi.view(n, 1 + P, D)[:, 1:])
-                out_lo[v0 * P:v1 * P].view(n, P, D).copy_(lo.view(n, 1 + P, D)[:, 1:])
+            if dino:
+                tok, _ = ops.gemm(a, pk["pe_w"], bias=pk["pe_b"], res_f32=pos_rows.repeat(n, 1), want_f32=True, split=sp,
+                                  a_lo=self._patch_lo(fmt, imgs[v0:v1], ps, kpad))
+                x = torch.empty((n, seq, D), dtype=torch.float32, device=imgs.device)
+                x[:, 0] = cls_row
+                x[:, 1:] = tok.view(n, P, D)
+                x = x.view(n * seq, D)
             else:
-                y, _ = ops.layernorm(x, w_, b_, eps, lp)
-                out[v0 * P:v1 * P].view(n, P, D).copy_(y.view(n, 1 + P, D)[:, 1:])
-        return out, out_lo, P, (h, w)
-
-    def _patch_lo(self, imgs, ps, ld_out):
-        """precision "exact": the low plane of the im2col rows = the im2col rows of the image's low plane (patchify only moves and rounds:
-        its output is lowp(img), so lowp(img - lowp(img)) patchified is exactly the remainder plane); None otherwise."""
-        if not self._x3:
-            return None
-        _, lo = ops.cast_lp(imgs.contiguous(), self.compute_dtype, want_lo=True)
-        return ops.patchify(lo.float(), ps, self.compute_dtype, ld_out=ld_out)
-
-    def _encode(self, imgs, pk):
-        """CroCoEncoder.forward (fast3r.py:549-559) for a batch of same-size images -> enc_norm output [NV*P][D] as (lowp, low plane or
-        None).  The high plane alone feeds decoder_embed; both planes are hook 0 of the heads in "high" precision."""
-        if isinstance(self.encoder, DinoEncoder):
-            return self._encode_dino(imgs, pk)
-        lp = self.compute_dtype
-        hp, sp = self._hp, self._sp
-        enc = self.encoder
-        NV, _, H, W = imgs.shape
-        ps = enc.patch_size
-        assert H % ps == 0, f"Input image height ({H}) is not a multiple of patch size ({ps})."  # patch_embed.py:27-32
-        assert W % ps == 0, f"Input image width ({W}) is not a multiple of patch size ({ps})."
-        h, w = H // ps, W // ps
-        P = h * w
-        rope = self._rope(max(h, w), imgs.device) + (w,)
-        out = torch.empty((NV * P, enc.embed_dim), dtype=lp, device=imgs.device)
-        out_lo = torch.empty_like(out) if hp else None
-        step = max(1, self.max_parallel_views_for_encoder)
-        for v0 in range(0, NV, step):
-            v1 = min(NV, v0 + step)
-            a = ops.patchify(imgs[v0:v1].contiguous(), ps, lp)
-            x, _ = ops.gemm(a, pk["pe_w"], bias=pk["pe_b"], want_f32=True, split=sp, a_lo=self._patch_lo(imgs[v0:v1], ps, 0))
-            ws = self._block_ws(pk["enc"][0], x.shape[0], enc.embed_dim, v1 - v0, P, imgs.device)
+                x, _ = ops.gemm(a, pk["pe_w"], bias=pk["pe_b"], want_f32=True, split=sp, a_lo=self._patch_lo(fmt, imgs[v0:v1], ps, kpad))
+            ws = self._block_ws(fmt, pk["enc"][0], x.shape[0], D, n, seq, imgs.device)
             for pb in pk["enc"]:
-                self._block(x, pb, enc.num_heads, (enc.embed_dim // enc.num_heads) ** -0.5, P, v1 - v0, rope, ws=ws)
-            w_, b_, eps = pk["enc_norm"]
+                self._block(fmt, x, pb, enc.num_heads, (D // enc.num_heads) ** -0.5, seq, n, rope, ws=ws)
+            rows = slice(v0 * P, v1 * P)
+            hi, lo = self._norm_planes(fmt, x, pk["enc_norm"], out_lp=None if hp or dino else out[rows])
+            if hp or dino:  # (a single CroCo plane is already there); DINOv2: the patch tokens only
+                out[rows].view(n, P, D).copy_(hi.view(n, seq, D)[:, -P:])
             if hp:
-                _, y = ops.layernorm(x, w_, b_, eps, lp, want_lp=False, want_f32=True)
-                hi, lo = ops.cast_lp(y, lp, want_lo=True)
-                out[v0 * P:v1 * P].copy_(hi)
-                out_lo[v0 * P:v1 * P].copy_(lo)
-            else:
-                ops.layernorm(x, w_, b_, eps, lp, out_lp=out[v0 * P:v1 * P])
+                out_lo[rows].view(n, P, D).copy_(lo.view(n, seq, D)[:, -P:])
         return out, out_lo, P, (h, w)
 
     # ---------------------------------------------------------------- fusion decoder on the HIP kernels
-    def _decode_sample(self, pk, enc_hi, enc_lo, Ps, emb_rows, v_lo, kvx, f32_hooks=False):
+    def _decode_sample(self, fmt, pk, enc_hi, enc_lo, Ps, emb_rows, v_lo, kvx, f32_hooks=False):
         """Fast3RDecoder.forward / LlamaDecoder.forward (fast3r.py:768-808 / :924-966) for ONE sample: enc_hi [T_loc][Denc] lowp (the
         local views' encoder tokens, view after view; enc_lo = their low plane or None), Ps = tokens per local view, emb_rows
         (N_total, D) fp32 = the image-id rows of ALL views (this rank's are [v_lo, v_lo + len(Ps))).  Returns the 4 hooked
         outputs (fast3r.py:148) as (plane, low plane or None) pairs; f32_hooks: as (fp32 tensor, None) instead, i.e. before the rounding
         to the heads' operand format (decode_tokens: parity of the decoder alone)."""
         dec = self.decoder
-        lp = self.compute_dtype
-        sp = self._sp
-        a_lo = enc_lo if sp == "x3" else None  # "exact": decoder_embed reads both planes of the encoder tokens
+        sp = fmt.linear_split
+        a_lo = enc_lo if fmt.x3 else None  # "exact": decoder_embed reads both planes of the encoder tokens
         dev = enc_hi.device
         L = dec.depth
         llama = isinstance(dec, LlamaDecoder)
@@ -1268,9 +798,9 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         D = dec.embed_dim
         T_loc, n_loc = sum(Ps), len(Ps)
         x = torch.empty((T_loc, D), dtype=torch.float32, device=dev)
-        ws = self._block_ws(pk["dec"][0], T_loc, D, 1, T_loc, dev, external_kv=kvx is not None)  # one allocation for all L blocks
-        planes = (lambda t: (t.clone(), None)) if f32_hooks else self._planes
-        want_f32_norm = f32_hooks or self._hp
+        ws = self._block_ws(fmt, pk["dec"][0], T_loc, D, 1, T_loc, dev, external_kv=kvx is not None)  # one allocation for all L blocks
+        planes = (lambda t: (t.clone(), None)) if f32_hooks else (lambda t: _planes(fmt, t))
+        rope = None
         if llama:
             # embed; per layer add view0_embed to the tokens of view 0, then the block with the rotary angles of each token's view;
             # outputs[0] = embedded tokens, outputs[n_layers] = final RMSNorm
@@ -1282,21 +812,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
                 per_tok = rows.repeat_interleave(torch.tensor(Ps, device=dev), dim=0)
                 rope = (per_tok[:, :32].contiguous(), per_tok[:, 32:].contiguous(), 1)
             view0_rows = Ps[0] if v_lo == 0 else 0                          # view 0 lives on the rank that owns the first views
-            taps = {}
-            if 0 in hooks:
-                taps[0] = planes(x)
-            for li, pb in enumerate(pk["dec"]):
-                ops.rows_add(x, pk["view0"], view0_rows)
-                self._block(x, pb, dec.num_heads, scale, T_loc, 1, rope, kvx, ws=ws, kv_tap=self.kv_tap)
-                if (li + 1) in hooks and (li + 1) != L:
-                    taps[li + 1] = planes(x)
-            if L in hooks:
-                w_, b_, eps = pk["dec_norm"]
-                if want_f32_norm:
-                    _, y = ops.layernorm(x, w_, None, eps, lp, want_lp=False, want_f32=True, rms=True)
-                    taps[L] = planes(y)
-                else:
-                    taps[L] = (ops.layernorm(x, w_, None, eps, lp, rms=True)[0], None)
+            taps = {0: planes(x)}
         else:
             if len(set(Ps)) == 1:
                 ops.gemm(enc_hi, pk["de_w"], bias=pk["de_b"], rowadd=emb_rows[v_lo:v_lo + n_loc].contiguous(), rowadd_div=Ps[0], out_f32=x, split=sp,
@@ -1308,16 +824,14 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
                              rowadd_div=Ps[i], out_f32=x[r0:r0 + Ps[i]], split=sp, a_lo=None if a_lo is None else a_lo[r0:r0 + Ps[i]])
                     r0 += Ps[i]
             taps = {0: (enc_hi.float(), None) if f32_hooks else (enc_hi, enc_lo)}
-            for li, pb in enumerate(pk["dec"]):
-                self._block(x, pb, dec.num_heads, scale, T_loc, 1, None, kvx, ws=ws, kv_tap=self.kv_tap)
-                if (li + 1) in hooks[1:3]:
-                    taps[li + 1] = planes(x)
-            w_, b_, eps = pk["dec_norm"]
-            if want_f32_norm:
-                _, y = ops.layernorm(x, w_, b_, eps, lp, want_lp=False, want_f32=True)
-                taps[L] = planes(y)
-            else:
-                taps[L] = (ops.layernorm(x, w_, b_, eps, lp)[0], None)
+        for li, pb in enumerate(pk["dec"]):
+            if llama:
+                ops.rows_add(x, pk["view0"], view0_rows)
+            self._block(fmt, x, pb, dec.num_heads, scale, T_loc, 1, rope, kvx, ws=ws, kv_tap=self.kv_tap)
+            if (li + 1) in hooks and (li + 1) != L:
+                taps[li + 1] = planes(x)
+        if L in hooks:  # (always, but for a LlamaDecoder whose n_layers is not decoder_args["depth"])
+            taps[L] = self._norm_planes(fmt, x, pk["dec_norm"], rms=llama, f32=f32_hooks)
         return [taps[hk] for hk in hooks]
 
     @torch.no_grad()
@@ -1330,117 +844,19 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         if dev.type != "cuda":
             raise F3RError(f"fast3r_amd.Fast3R runs only on a ROCm GPU (tokens are on {dev}); there is no CPU fallback")
         with torch.cuda.device(dev):
-            pk = self._pack(dev)
+            fmt = self._format()
+            pk = self._pack(dev, fmt)
             ids = torch.as_tensor(image_ids).reshape(-1).to(dev)
             assert ids.numel() == len(tokens_per_view)
             emb_rows = self.decoder.image_idx_emb.to(dev)[ids]
             enc_lo = None
-            if self._hp and not isinstance(self.decoder, LlamaDecoder):
+            if fmt.planes and not isinstance(self.decoder, LlamaDecoder):
                 enc_lo = torch.zeros_like(enc_tokens) if enc_tokens_lo is None else enc_tokens_lo.contiguous()
             with ops.family("transformer_linears"):
-                out = self._decode_sample(pk, enc_tokens.contiguous(), enc_lo, list(tokens_per_view), emb_rows, 0, None, f32_hooks=return_f32)
+                out = self._decode_sample(fmt, pk, enc_tokens.contiguous(), enc_lo, list(tokens_per_view), emb_rows, 0, None, f32_hooks=return_f32)
             return [t[0] for t in out]
 
     # ---------------------------------------------------------------- DPT head on the HIP kernels
-    def _dpt(self, hk, toks, nv, gh, gw):
-        """DPTOutputAdapter_fix.forward + postprocess (heads/dpt_head.py:42-129) for nv same-size views.
-        toks: the 4 hooked token matrices as (lowp [nv*gh*gw][C], low plane or None) pairs.  Activations stay NHWC lowp (two planes
-        each in "high" precision, every conv then runs split="x3"); accumulation fp32.  A ResidualConvUnit reads relu(x) for its first
-        conv and x for its skip add (dpt_block.py:143-154): the PRODUCER of x writes both (f3r_gemm_args.out_relu), so no conv
-        pre-activates its operand while staging it and all of them can use LDS-DMA."""
-        hp = self._hp
-        sp = "x3" if hp else None
-        ld = hk.dims
-        # Activations are (hi, lo, f8) triples: the fp16 / bf16 high plane, the 16-bit low plane (None = not carried) and the fp8 planes (None = not
-        # carried).  Which of them a producer writes follows from its CONSUMERS: a residual add, a 1x1 conv or an upsample read hi + lo; a 3x3
-        # convolution that runs split "x3f8" reads hi + f8 and needs no lo.
-        f8_on = self._head_f8
-
-        def use_f8(rows, cin, w):
-            # decided by the pixels of ONE view (rows / nv), so that a forward computes the same numbers whatever max_parallel_views_for_head is;
-            # the operand of a launch must stay below 4 GiB (32-bit lane offsets of the 256-tile kernel: 63 views of 512 x 512 x 128 channels)
-            return bool(f8_on and w.w8 is not None and cin % 128 == 0 and rows // nv >= self.head_f8_min_rows and rows * cin * 2 < (1 << 32))
-
-        def c1(i):  # act_postprocess[i][0]: 1x1 conv on the tokens
-            r = ops.gemm(toks[i][0], hk.a_w[i], bias=hk.a_b[i], want_lp=True, want_lo=hp, split=sp, a_lo=toks[i][1])
-            return tuple(t.view(nv, gh, gw, ld[i]) for t in r[1:]) + (None,) if hp else (r[1].view(nv, gh, gw, ld[i]), None, None)
-
-        def convT(xp, w, b, s, cout):
-            r = ops.convT(xp[0], w, b, s, cout, split=sp, x_lo=xp[1], want_lo=hp)
-            return r + (None,) if hp else (r, None, None)
-
-        def conv(xp, w, bias=None, stride=1, act=None, res=None, res2=None, relu_copy=False, x_f8=False, relu_f8=False, x_lo=True, fin=None):
-            """-> {"x": (out, lo, f8), "relu": (relu(out), lo, f8)}; x_f8 / relu_f8: the consumer of that copy is an "x3f8" convolution (fp8 planes
-            instead of the low plane; x_lo=False drops the output's own low plane too).  fin: the fused head tail -> (pts3d, conf)."""
-            kw = dict(split=sp, x_lo=xp[1])
-            wt = w.w
-            if xp[2] is not None:  # the producer wrote fp8 planes because this launch takes them
-                kw = dict(split="x3f8", x_f8=xp[2], w_scale=w.scale)
-                wt = w.w8
-            r = ops.conv3x3(xp[0], wt, stride=stride, bias=bias, act=act,
-                            res_lp=None if res is None else res[0], res_lp_lo=None if res is None else res[1],
-                            res_lp2=None if res2 is None else res2[0], res_lp2_lo=None if res2 is None else res2[1],
-                            want_lo=hp and x_lo, want_relu=relu_copy, want_f8=x_f8, want_relu_lo=hp and not relu_f8, want_relu_f8=relu_f8, fin=fin, **kw)
-            if fin is not None:
-                return r
-            if not isinstance(r, dict):
-                return {"x": (r, None, None)}
-            return {"x": (r["out"], r.get("out_lo"), r.get("out_f8")), "relu": (r.get("relu"), r.get("relu_lo"), r.get("relu_f8"))}
-
-        def rows_of(t):
-            return t.shape[0] * t.shape[1] * t.shape[2]
-
-        l0 = convT(c1(0), hk.t0_w, hk.t0_b, 4, hk.t0_cout)                             # dpt_block.py:416-434 (channels padded to 64: _pack_head)
-        l1 = convT(c1(1), hk.t1_w, hk.t1_b, 2, hk.t1_cout)                             # :436-454
-        l2 = c1(2)                                                                      # :456-464
-        l3 = conv(c1(3), hk.c3_w, bias=hk.c3_b, stride=2)["x"]                          # :466-481
-        # scratch.layer_rn (no bias); the relu copy feeds the first RCU convolution of its level
-        ls = [conv(l, hk.rn_w[i], relu_copy=True, relu_f8=use_f8(rows_of(l[0]), hk.feature_dim, hk.ref[i]["u2c1" if i == 3 else "u1c1"][0]))
-              for i, l in enumerate((l0, l1, l2, l3))]
-        del l0, l1, l2, l3
-
-        def rcu(x, c1w, c2w, extra=None, relu_copy=False, relu_f8=False):
-            # x + conv2(relu(conv1(relu(x)))) (+ extra); x = {"x": planes, "relu": planes of relu(x)}
-            f8 = use_f8(rows_of(x["x"][0]), hk.feature_dim, c2w[0])
-            t = conv(x["relu"], c1w[0], bias=c1w[1], act="relu", x_f8=f8, x_lo=not f8)["x"]
-            return conv(t, c2w[0], bias=c2w[1], res=x["x"], res2=extra, relu_copy=relu_copy, relu_f8=relu_f8)
-
-        def fusion(r, path, skip=None, crop=None, out_f8=False):
-            # out_conv(up2(RCU2(path + RCU1(skip)))); the 1x1 out_conv commutes exactly with the bilinear
-            # interpolation (both linear, weights sum to 1), so it runs BEFORE the upsample on 4x fewer pixels.
-            if skip is not None:
-                path = rcu(skip, r["u1c1"], r["u1c2"], extra=path, relu_copy=True, relu_f8=use_f8(rows_of(skip["x"][0]), hk.feature_dim, r["u2c1"][0]))
-            y = rcu(path, r["u2c1"], r["u2c2"])["x"]
-            B, hh, ww, C = y[0].shape
-            g = ops.gemm(y[0].view(B * hh * ww, C), r["out"][0], bias=r["out"][1], want_lp=True, want_lo=hp, split=sp,
-                         a_lo=None if y[1] is None else y[1].view(B * hh * ww, C))
-            z = (g[1].view(B, hh, ww, C), g[2].view(B, hh, ww, C) if hp else None)
-            if out_f8:
-                return ops.upsample2x(z[0], crop, x_lo=z[1], want_lo=False, want_f8=True)
-            u = ops.upsample2x(z[0], crop, x_lo=z[1], want_lo=hp)
-            return u + (None,) if hp else (u, None, None)
-
-        p4 = fusion(hk.ref[3], ls[3], None, crop=(ls[2]["x"][0].shape[1], ls[2]["x"][0].shape[2]))  # dpt_head.py:69-71
-        p3 = fusion(hk.ref[2], p4, ls[2])
-        p2 = fusion(hk.ref[1], p3, ls[1])
-        B1, h1, w1 = ls[0]["x"][0].shape[:3]
-        p1 = fusion(hk.ref[0], p2, ls[0], out_f8=use_f8(B1 * 4 * h1 * w1, hk.feature_dim, hk.h0_w))
-        del ls, p4, p3, p2
-        y = conv(p1, hk.h0_w, bias=hk.h0_b)["x"]                                        # head[0]
-        # head[1]: Interpolate(scale_factor = patch_size / 8, bilinear, align_corners=True) (dpt_block.py:374): x2 for patch 16, x1.75 for 14
-        full = (y[0].shape[1] * hk.patch_size // 8, y[0].shape[2] * hk.patch_size // 8)
-        rows2 = y[0].shape[0] * full[0] * full[1]
-        if use_f8(rows2, hk.last_dim, hk.h2_w):
-            u = ops.interp_bilinear(y[0], full, x_lo=y[1], want_lo=False, want_f8=True)
-        else:
-            u = ops.interp_bilinear(y[0], full, x_lo=y[1], want_lo=hp)
-            u = u + (None,) if hp else (u, None, None)
-        # head[2], head[3] (+ head[4] and postprocess in the same launch when the 256 x 128 tile kernel takes it)
-        if (hk.fin is not None and rows2 // nv >= self.head_tail_fused_min_rows and hk.last_dim % 64 == 0 and rows2 * hk.last_dim * 2 < (1 << 32)):
-            return conv(u, hk.h2_w, bias=hk.h2_b, act="relu", fin=hk.fin)
-        y = conv(u, hk.h2_w, bias=hk.h2_b, act="relu")["x"]
-        return ops.dpt_final(y[0], hk.h4_w, hk.h4_b, hk.conf_mode, x_lo=y[1], depth_mode=tuple(hk.depth_mode))  # head[4] + postprocess
-
     # ---------------------------------------------------------------- forward
     def forward(self, views, profiling=False, host_outputs=False):
         """fast3r.py:302-497.  views: list[N] of dicts with 'img' (B,3,H,W) on a ROCm device.
@@ -1450,7 +866,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         if len(views) == 0:
             return ([], {}) if profiling else []
         if (self.use_graphs and not profiling and self.sharding is None and self.debug_taps is None and not isinstance(self.decoder, LlamaDecoder)
-                and not self._x3):  # (the plane modes allocate per layer: they always run eagerly)
+                and not self._format().x3):  # (the plane modes allocate per layer: they always run eagerly)
             dev = views[0]["img"].device
             if dev.type == "cuda":  # (anything else: the eager path raises its F3RError)
                 with torch.cuda.device(dev):  # capture and replay on the tensors' device, whatever the caller's current device is
@@ -1458,24 +874,6 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
                 if out is not None:
                     return out
         return self._forward_eager(views, profiling, host_outputs=host_outputs)
-
-    @staticmethod
-    def _head_chunk_views(limit, gh, gw, cus=256):
-        """Views per head launch: the count in (limit / 2, limit] whose convolution launches fill the chip's rounds best.  max_parallel_views_for_head
-        (the reference's 25, fast3r.py:68) bounds the head's memory; the results do not depend on the chunking (tested bit for bit), so inside that
-        bound the chunk is chosen for the 256-row output tiles of the big 3x3 convolutions: at 512 x 512, 25 views are 1 600 tiles = 6.25 rounds of 256
-        workgroups at the 128 x 128 level and 1.56 at 64 x 64 (11 % / 22 % of those launches idle), 16 views are 4 and 1 round exactly.  Cost model:
-        sum over the levels of (FLOPs per pixel) x rounds(c) / c."""
-        if limit <= 2:
-            return limit
-        t = gh * gw   # pixels per view at the token grid; levels at 1/4, 1, 4, 16 (RCU convolutions), 64 (head[0]), 256 (head[2]) times that
-        levels = [(t // 4, 2 * 256 * 256), (t, 4 * 256 * 256), (4 * t, 4 * 256 * 256), (16 * t, 4 * 256 * 256), (64 * t, 256 * 128), (256 * t, 128 * 128)]
-        best, best_cost = limit, None
-        for c in range(limit, max(1, limit // 2), -1):
-            cost = sum(w * (-(-(-(-c * max(px, 1) // 256)) // cus)) for px, w in levels) / c
-            if best_cost is None or cost < best_cost * 0.995:   # (ties and near-ties: the larger chunk = fewer launches)
-                best, best_cost = c, cost
-        return best
 
     def enable_graphs(self, on=True, max_views=64):
         """Opt-in hipGraph replay for launch-bound scenes (a forward of N <= max_views same-size views is a chain of
@@ -1531,8 +929,8 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
 
     def _forward_on_device(self, views, profiling, _emb_rows, dev, host_outputs=False):
         prof = {} if profiling else None
-        lp = self.compute_dtype
-        pk = self._pack(dev)
+        fmt = self._format()
+        pk = self._pack(dev, fmt)
         enc, dec = self.encoder, self.decoder
         ps = enc.patch_size
         sh = self.sharding
@@ -1551,7 +949,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
         if not plan["any_portrait"] and all(tuple(v["img"].shape[-2:]) == tuple(my_views[0]["img"].shape[-2:]) for v in my_views) and n_loc > 0:
             imgs = torch.cat([v["img"] for v in my_views], dim=0).float()
             with ops.family("transformer_linears"):   # (bench.py roofline.others: which family a GEMM-like launch is booked under)
-                f, flo, P, grid = self._encode(imgs, pk)
+                f, flo, P, grid = self._encode(fmt, imgs, pk)
             f = f.view(n_loc, B, P, -1)
             flo = None if flo is None else flo.view(n_loc, B, P, -1)
             for i in range(n_loc):
@@ -1581,7 +979,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
             untranspose = isinstance(enc, DinoEncoder)  # its portrait tokens go back to the stored (landscape) order (fast3r.py:601-622)
             for _, items in groups.items():
                 with ops.family("transformer_linears"):
-                    f, flo, P, (gh_, gw_) = self._encode(torch.stack([im for _, _, im in items]).contiguous(), pk)
+                    f, flo, P, (gh_, gw_) = self._encode(fmt, torch.stack([im for _, _, im in items]).contiguous(), pk)
                 f = f.view(len(items), P, -1)
                 flo = None if flo is None else flo.view(len(items), P, -1)
                 for j, (i, b, _) in enumerate(items):
@@ -1626,9 +1024,9 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
                 tok = [(v["img"].shape[-2] // ps) * (v["img"].shape[-1] // ps) for v in views]
                 t_all = [sum(tok[slice(*split_range(N_total, sh.world, r))]) for r in range(sh.world)]
                 assert t_all[sh.rank] == T_loc
-                kvx = sh.make_kv_exchange(T_loc, kv_dim, lp, dev, n_heads=dec.num_heads, q_dim=D, t_all=t_all)
+                kvx = sh.make_kv_exchange(T_loc, kv_dim, fmt.lp, dev, n_heads=dec.num_heads, q_dim=D, t_all=t_all)
             with ops.family("transformer_linears"):
-                hook_toks.append(self._decode_sample(pk, enc_hi, enc_lo, Ps, emb_rows[b], v_lo, kvx))
+                hook_toks.append(self._decode_sample(fmt, pk, enc_hi, enc_lo, Ps, emb_rows[b], v_lo, kvx))
             if self.debug_taps is not None:
                 self.debug_taps.setdefault("hooks", []).append([t[0].float().cpu() for t in hook_toks[-1]])
         del feats
@@ -1652,7 +1050,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
             while i0 < n_loc:
                 i1 = i0 + 1
                 gh, gw = head_grid[i0][b]
-                chunk = self._head_chunk_views(step, gh, gw)
+                chunk = dpt_head.chunk_views(step, gh, gw)
                 while i1 < n_loc and i1 - i0 < chunk and head_grid[i1][b] == head_grid[i0][b]:
                     i1 += 1
                 toks = [(t[0][offs[i0]:offs[i1]], None if t[1] is None else t[1][offs[i0]:offs[i1]]) for t in hook_toks[b]]
@@ -1660,7 +1058,7 @@ class Fast3R(nn.Module, _HubMixin, repo_url="https://github.com/facebookresearch
                     per_view[i][b] = {}
                 for pname, cname, hk in heads:
                     with ops.family("head_convs"):
-                        pts, conf = self._dpt(hk, toks, i1 - i0, gh, gw)
+                        pts, conf = dpt_head.dpt(fmt, hk, toks, i1 - i0, gh, gw)
                     for i in range(i0, i1):
                         sw = head_swap[i][b]
                         per_view[i][b][pname] = pts[i - i0].swapaxes(0, 1) if sw else pts[i - i0]  # transposed(): misc.py:105-106
