@@ -813,3 +813,64 @@ def cast_lp(x, lp, out=None, want_lo=False):
     with _timed(0.0, _nb(x, out, out_lo), "elementwise"):
         check(_lib.lib().f3r_cast_f32_to_lp(ptr(x), ptr(out), ptr(out_lo), x.numel(), dtype_id(lp), stream_ptr()), "f3r_cast_f32_to_lp")
     return (out, out_lo) if want_lo else out
+
+
+def _pose_metric_lib():
+    l = _lib.lib()
+    if l.f3r_version() < _lib.POSE_METRIC_ABI_VERSION:
+        raise _lib.F3RError(f"{_lib.LIB_PATH} is version {l.f3r_version()}; the camera-pose metrics need >= {_lib.POSE_METRIC_ABI_VERSION}: "
+                            "rebuild it (fast3r_amd/csrc/build.sh)")
+    return l
+
+
+def _thresholds(ts):
+    ts = [float(t) for t in ts]
+    return (ctypes.c_double * max(1, len(ts)))(*ts), len(ts)
+
+
+def _real_id(dt):
+    if dt == torch.float32:
+        return _lib.F3R_REAL_F32
+    if dt == torch.float64:
+        return _lib.F3R_REAL_F64
+    raise ValueError(f"fast3r_amd: camera-pose metrics take torch.float32 or torch.float64, got {dt}")
+
+
+def pose_pair_metrics(pred, gt, r_thresholds, t_thresholds, n_bins, max_threshold, want_pairs=False):
+    """Relative-pose errors of every view pair i < j of every sample (cam_pose_metric.py:17-40) and their counts.  pred, gt: (B, N, 4, 4)
+    cam-to-world, fp32 or fp64, same dtype, on the GPU.  -> (counts int64 (B, n_r + n_t + n_bins + 2) = thresholds passed | histc bins of
+    max(r, t) | pairs with a trace out of range | pairs with the 1e6 default, rel_r, rel_t): the per-pair errors in degrees, (B, N (N - 1) / 2)
+    in the input dtype in torch.combinations order, only with want_pairs (otherwise None: nothing per pair is allocated or written)."""
+    require_gpu(pred, "pred")
+    require_gpu(gt, "gt")
+    if pred.dim() != 4 or tuple(pred.shape[2:]) != (4, 4) or pred.shape != gt.shape or pred.dtype != gt.dtype:
+        raise ValueError(f"pred and gt must both be (B, N, 4, 4) of one dtype; got {tuple(pred.shape)} {pred.dtype} and {tuple(gt.shape)} {gt.dtype}")
+    B, N = pred.shape[:2]
+    pred, gt = pred.contiguous(), gt.contiguous()
+    rt, n_r = _thresholds(r_thresholds)
+    tt, n_t = _thresholds(t_thresholds)
+    counts = torch.empty((B, n_r + n_t + int(n_bins) + 2), dtype=torch.int64, device=pred.device)
+    rel_r = torch.empty((B, N * (N - 1) // 2), dtype=pred.dtype, device=pred.device) if want_pairs else None
+    rel_t = torch.empty_like(rel_r) if want_pairs else None
+    with torch.cuda.device(pred.device):
+        check(_pose_metric_lib().f3r_pose_pair_metrics(ptr(pred), ptr(gt), _real_id(pred.dtype), B, N, rt, n_r, tt, n_t, int(n_bins), float(max_threshold),
+                                                       ptr(rel_r), ptr(rel_t), ptr(counts), stream_ptr()), "f3r_pose_pair_metrics")
+    return counts, rel_r, rel_t
+
+
+def pose_error_stats(r_error, t_error, r_thresholds, t_thresholds, n_bins, max_threshold):
+    """The counts of pose_pair_metrics from given per-pair errors (1-D, same length and dtype, on the GPU): int64 (n_r + n_t + n_bins + 2)."""
+    require_gpu(r_error, "r_error")
+    require_gpu(t_error, "t_error")
+    if r_error.dim() != 1 or r_error.shape != t_error.shape or r_error.dtype != t_error.dtype:
+        raise ValueError(f"r_error and t_error must be 1-D, of one length and dtype; got {tuple(r_error.shape)} {r_error.dtype} and "
+                         f"{tuple(t_error.shape)} {t_error.dtype}")
+    r_error, t_error = r_error.contiguous(), t_error.contiguous()
+    n = r_error.numel()
+    rt, n_r = _thresholds(r_thresholds)
+    tt, n_t = _thresholds(t_thresholds)
+    counts = torch.empty(n_r + n_t + int(n_bins) + 2, dtype=torch.int64, device=r_error.device)
+    with torch.cuda.device(r_error.device):
+        check(_pose_metric_lib().f3r_pose_error_stats(ptr(r_error) if n else None, ptr(t_error) if n else None, n, _real_id(r_error.dtype), rt, n_r, tt, n_t,
+                                                      int(n_bins), float(max_threshold), ptr(counts), stream_ptr()), "f3r_pose_error_stats")
+    return counts

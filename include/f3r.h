@@ -42,11 +42,12 @@ typedef enum {
 } f3r_status;
 
 typedef enum { F3R_F16 = 0, F3R_BF16 = 1 } f3r_dtype;
+typedef enum { F3R_REAL_F32 = 0, F3R_REAL_F64 = 1 } f3r_real; /* element type of the pose-metric entry points */
 
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -478,6 +479,33 @@ int f3r_recon_prepare(const float* conf, const float* pred, const float* gt, con
  */
 int f3r_estimate_poses(const float* pts3d, const float* conf, const float* focal_in, float* focal_out, float* cam_to_world, int* inliers,
                        int n_views, int H, int W, float conf_thr, float ppx, float ppy, int n_focals, int n_iter, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Relative camera-pose metrics (ABI 370): RRA / RTA / mAA of MultiViewDUSt3RLitModule.evaluate_camera_poses
+ * (fast3r/models/multiview_dust3r_module.py:737-804) = camera_to_rel_deg + calculate_auc (fast3r/eval/cam_pose_metric.py:17-40,73-100)
+ * over all view pairs i < j, without the reference's (pairs, 4, 4) tensors.
+ * The pair-metrics entry point: pred / gt = cam-to-world matrices [n_samples][n_views][4][4] row-major, fp32 or fp64 (dtype: f3r_real).  Per pair,
+ *   in fp64 on the exactly widened inputs: relative poses inv(P_i) P_j with the closed-form inverse (R^T, -R^T t); rotation error from
+ *   cos = (trace(R_gt_rel R_pred_rel^T) - 1) / 2 with acos inside (-(1 - 1e-4), 1 - 1e-4) and its first-order extrapolation about the bound
+ *   outside (fast3r/utils/so3_utils.py: identical rotations score 0.4051 degrees, not 0); translation error acos(sqrt(1 - loss)) with both
+ *   vectors divided by (norm + 1e-15), loss = max(1 - dot^2, 1e-15), a NaN / inf error replaced by 1e6 rad (blind to sign: opposite
+ *   translations score 0); both in degrees.
+ *   counts [n_samples][n_r + n_t + n_bins + 2] int64 (device; cleared by the call) = { #(r < r_thresholds[k]) | #(t < t_thresholds[k]) |
+ *   torch.histc(max(r, t), bins = n_bins, min = 0, max = max_threshold): bin = (int64)(m / max_threshold * n_bins), m == max_threshold in the
+ *   last bin, m < 0, m > max_threshold and NaN dropped (the reference asks for 31 bins over [0, 30]: bin width 30 / 31) | #pairs whose trace
+ *   lies outside [-1 - 1e-4, 3 + 1e-4] (the reference raises ValueError) | #pairs that took the 1e6 default }.
+ *   rel_r / rel_t: optional (both or neither) per-pair errors [n_samples][n_views (n_views - 1) / 2] in the input dtype, pair (i, j) at
+ *   i (2 n_views - i - 1) / 2 + (j - i - 1) -- the order of torch.combinations; with NULL nothing of size O(pairs) is written.
+ *   r_thresholds / t_thresholds are HOST arrays (at most 8 each).  Integer atomics only: every output is deterministic.
+ *   F3R_ERR_ARG before any launch: n_views < 2, n_samples < 1, null pred / gt / counts, more than 8 thresholds per kind, n_bins outside 1..256.
+ * The error-stats entry point: the same counts [n_r + n_t + n_bins + 2] (the last two zero) from given per-pair errors r [n], t [n] (device, dtype as above):
+ *   the body of calculate_auc and of the (x < tau).float().mean() threshold means.
+ */
+int f3r_pose_pair_metrics(const void* pred, const void* gt, int dtype, int n_samples, int n_views, const double* r_thresholds, int n_r,
+                          const double* t_thresholds, int n_t, int n_bins, double max_threshold, void* rel_r, void* rel_t, int64_t* counts,
+                          f3r_stream_t stream);
+int f3r_pose_error_stats(const void* r, const void* t, int64_t n, int dtype, const double* r_thresholds, int n_r, const double* t_thresholds,
+                         int n_t, int n_bins, double max_threshold, int64_t* counts, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).

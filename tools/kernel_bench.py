@@ -360,6 +360,61 @@ def bench_pnp(n_views=320, H=512, W=512):
                           "cpu_restatement_ms_per_view": round(cpu_s * 1e3, 1)}), flush=True)
 
 
+def bench_posemetric(sizes=(320, 1500), H=512, W=512, out_path="profiles/r07_pose_metric_bench.jsonl"):
+    """camera_pose_metrics (RRA / RTA / mAA from f3r_pose_pair_metrics) at B = 1 next to estimate_poses at the same view count in the same
+    run: the metric stage is O(pairs) trigonometry on a few hundred kilobytes of poses and must stay below 5 % of the PnP stage.  Wall
+    clock per call, synchronised (the metric call ends with the counts on the host), median of 7 after a warm-up; one JSON line, also
+    appended to profiles/."""
+    import os
+    import statistics
+    import time
+    from fast3r_amd import camera_pose_metrics, estimate_poses
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import cam_pose_cases as C
+
+    def wall_ms(fn, reps=7):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts)
+
+    g = torch.Generator().manual_seed(0)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    z = 2 + 3 * torch.rand(H, W, generator=g)
+    Xc = torch.stack([(xs - W / 2) * z / 400.0, (ys - H / 2) * z / 400.0, z], -1)
+    c, s_ = math.cos(0.3), math.sin(0.3)
+    R = torch.tensor([[c, 0, s_], [0, 1, 0], [-s_, 0, c]])
+    Xw = (Xc - torch.tensor([0.2, -0.1, 0.5])) @ R + 0.003 * torch.randn(H, W, 3, generator=g)
+    conf1 = 1.001 + 4 * torch.rand(H, W, generator=g)
+    rec = {"what": "posemetric", "device": torch.cuda.get_device_name(0), "B": 1, "HW": [H, W], "sizes": {}}
+    ok = True
+    for n in sizes:
+        pred, gt = (x.cuda()[None] for x in C.pose_set(n, 0))
+        counts_ms = wall_ms(lambda: camera_pose_metrics(pred, gt))
+        pairs_ms = wall_ms(lambda: ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD), want_pairs=True)[0].cpu())
+        kernel_ms, _ = time_ms(lambda: ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD)), rounds=5, inner=10)
+        pts = Xw[None].cuda().expand(n, H, W, 3).contiguous()
+        conf = conf1[None].cuda().expand(n, H, W).contiguous()
+        pnp_ms = wall_ms(lambda: estimate_poses(pts, conf, 400.0), reps=3)
+        del pts, conf
+        ratio = counts_ms / pnp_ms
+        ok = ok and ratio < 0.05
+        rec["sizes"][str(n)] = {"pairs": n * (n - 1) // 2, "metrics_counts_only_ms": round(counts_ms, 4), "metrics_with_pairs_ms": round(pairs_ms, 4),
+                                "pair_kernel_launch_ms": round(kernel_ms, 4), "estimate_poses_focal_given_ms": round(pnp_ms, 3),
+                                "counts_only_over_estimate_poses": round(ratio, 5)}
+    rec["below_5_percent"] = ok
+    line = json.dumps(rec)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+
+
 def bench_image(H=3000, W=4000, size=512, n=16):
     """load_images' per-pixel work at a 12 MP camera frame: PIL LANCZOS resize + crop + ImgNorm on the host vs upload + GPU."""
     import time
@@ -587,6 +642,9 @@ if __name__ == "__main__":
         bench_dpt_final()
     if "focal" in args.what:
         bench_focal()
+    if args.what == "posemetric":  # RRA / RTA / mAA over all view pairs next to the PnP stage that feeds it
+        bench_posemetric()
+        sys.exit(0)
     if "pnp" in args.what:
         bench_pnp()
     if "image" in args.what:
