@@ -16,6 +16,7 @@ F3R_ACT_NONE, F3R_ACT_GELU, F3R_ACT_RELU = 0, 1, 2
 F3R_SPLIT_NONE, F3R_SPLIT_W2, F3R_SPLIT_X3, F3R_SPLIT_W2F8, F3R_SPLIT_X3F8 = 0, 1, 2, 3, 4
 F3R_MAX_SEG = 8
 F3R_REAL_F32, F3R_REAL_F64 = 0, 1
+F3R_LOSS_DIS, F3R_LOSS_LOG1P = 0, 1
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
 
@@ -136,6 +137,10 @@ SYMBOLS = {
                                              ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_vp, _c_vp, _c_vp, _c_vp]),
     "f3r_pose_error_stats": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_vp, _c_vp]),
+    "f3r_mv_conf_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "f3r_mv_conf_loss": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_vp, ctypes.c_size_t,
+                                        _c_vp, _c_vp]),
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")
@@ -151,6 +156,7 @@ class F3RError(RuntimeError):
 ABI_VERSION = 350  # f3r_version() of include/f3r.h this file mirrors (the reconstruction metrics need RECON_ABI_VERSION)
 RECON_ABI_VERSION = 360
 POSE_METRIC_ABI_VERSION = 370  # f3r_pose_pair_metrics / f3r_pose_error_stats (fast3r_amd/ops.py checks it where it calls them)
+LOSS_ABI_VERSION = 380  # f3r_mv_conf_loss (checked in fast3r_amd/ops.py too)
 
 
 def lib():

@@ -24,7 +24,7 @@ int f3r_check_launch(const char* what) {
   return F3R_OK;
 }
 
-extern "C" int f3r_version(void) { return 370; /* 0.3.7: + the relative camera-pose metrics (include/f3r.h f3r_version) */ }
+extern "C" int f3r_version(void) { return 380; /* 0.3.8: + the multi-view confidence loss (include/f3r.h f3r_version) */ }
 
 extern "C" int f3r_wall_clock_khz(void) {
   int dev = 0, khz = 0;

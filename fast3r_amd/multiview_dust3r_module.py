@@ -11,8 +11,12 @@ SURVEY.md section 8f rank 2; the PnP solver is not OpenCV's -- see pose.py); `ev
 and `correct_preds_orientation` (:871-938) run on the GPU too: the poses go from the PnP launch to the pairwise RRA / RTA / mAA counts
 (fast3r_amd/cam_pose_metric.py, f3r_pose_metric.hip) without leaving the device.  The torchmetrics / Lightning logging of the reference
 is replaced by plain per-epoch containers (`reconstruction_metrics_per_epoch`, `camera_pose_metrics_per_epoch`).
+The validation path is complete with `model_step` (:169-188), `validation_step` (:239-306) and `on_validation_epoch_end` (:308-319): the
+validation loss comes from the criterion's HIP kernels (fast3r_amd/losses.py, f3r_loss.hip) on the tensors the forward pass left on the
+device, and is kept in `val_losses` / `val_loss_details_per_epoch`.  There is no training step and no backward.
 """
 import logging
+import re
 
 import torch
 
@@ -38,6 +42,9 @@ class MultiViewDUSt3RLitModule(torch.nn.Module):
         self.RRA_thresholds = [5, 15, 30]  # :103-104
         self.RTA_thresholds = [5, 15, 30]
         self.camera_pose_metrics_per_epoch = []  # one dict per evaluated sample (the reference feeds torchmetrics MeanMetrics, :106-112)
+        self.current_epoch = 0  # Lightning's trainer sets it in the reference; here the caller's loop does
+        self.val_losses = []  # one float per validation_step (the reference's MeanMetric val_loss, :250)
+        self.val_loss_details_per_epoch = {}  # dataset name -> {logged key -> [one float per validation_step]}
 
     @classmethod
     def load_for_inference(cls, net):
@@ -47,6 +54,65 @@ class MultiViewDUSt3RLitModule(torch.nn.Module):
 
     def forward(self, views, **kw):
         return self.net(views, **kw)
+
+    @property
+    def device(self):
+        """Where the net lives (Lightning's `self.device`); the CPU for a net without parameters."""
+        params = self.net.parameters() if isinstance(self.net, torch.nn.Module) else iter(())
+        p = next(params, None)
+        return p.device if p is not None else torch.device("cpu")
+
+    def model_step(self, batch, criterion):
+        """Reference :169-188: move the batch's tensors to the net's device, run the forward pass and the criterion (any callable
+        `criterion(views, preds) -> (loss, details)`; fast3r_amd.losses provides the reference's validation criterion on the GPU).
+        -> (views, preds, loss, loss_details); loss and loss_details are None without a criterion (the reference fails to unpack there)."""
+        device = self.device
+        for view in batch:
+            for name in "img pts3d valid_mask camera_pose camera_intrinsics F_matrix corres".split():
+                if name in view:
+                    view[name] = view[name].to(device, non_blocking=True)
+        views = batch
+        preds = self.forward(views)
+        loss, loss_details = criterion(views, preds) if criterion is not None else (None, None)
+        return views, preds, loss, loss_details
+
+    def validation_step(self, batch, batch_idx, dataloader_idx=0):
+        """Reference :239-306: the validation loss of the batch as a float, kept in `self.val_losses`; its details are kept under
+        `self.val_loss_details_per_epoch[dataset_name]` with the reference's logged names, `val_detail_{dataset}_{key}` and the form
+        without the view number, `val/{dataset}_{stripped key}`; then the camera-pose metrics for "Co3d_v2" and, in epoch 0 and every
+        fifth epoch, the reconstruction metrics for dtu / 7scenes / nrgbd.  Raises ValueError without a validation criterion."""
+        if self.validation_criterion is None:
+            raise ValueError("validation_step needs a validation_criterion (fast3r_amd.losses.ConfLossMultiviewV2(...)); "
+                             "load_for_inference() builds the module without one")
+        views, preds, loss, loss_details = self.model_step(batch, self.validation_criterion)
+        dataset_name = views[0]["dataset"][0]
+        loss_value = float(loss.detach().cpu().item()) if torch.is_tensor(loss) else float(loss)
+        self.val_losses.append(loss_value)
+        if loss_details is not None:
+            store = self.val_loss_details_per_epoch.setdefault(dataset_name, {})
+            for key, value in loss_details.items():
+                store.setdefault(f"val_detail_{dataset_name}_{key}", []).append(float(value))
+                match = re.search(r"/(\d{1,2})$", key)
+                if match:
+                    store.setdefault(f"val/{dataset_name}_{key[:match.start()]}", []).append(float(value))
+        if dataset_name == "Co3d_v2":
+            self.evaluate_camera_poses(views, preds, niter_PnP=100, focal_length_estimation_method="first_view_from_global_head")
+        if dataset_name in ("dtu", "7scenes", "nrgbd") and (self.current_epoch % 5 == 4 or self.current_epoch == 0):
+            self.evaluate_reconstruction(views, preds, dataset_name=dataset_name, use_pts3d_from_local_head=self.eval_use_pts3d_from_local_head,
+                                         min_conf_thr_percentile_for_local_alignment_and_icp=85, min_conf_thr_percentile_for_metric_cacluation=0)
+        return loss_value
+
+    def on_validation_epoch_end(self):
+        """Reference :308-319 without a logger: -> {"val/loss": mean of the epoch's losses, every key of `val_loss_details_per_epoch`: its
+        mean}, and clears both containers (NaN for "val/loss" without any step).  The metric containers are left to their readers."""
+        mean = lambda xs: sum(xs) / len(xs) if xs else float("nan")  # noqa: E731
+        out = {"val/loss": mean(self.val_losses)}
+        for store in self.val_loss_details_per_epoch.values():
+            for key, values in store.items():
+                out[key] = mean(values)
+        self.val_losses = []
+        self.val_loss_details_per_epoch = {}
+        return out
 
     @staticmethod
     def estimate_camera_poses(preds, views=None, niter_PnP=10, focal_length_estimation_method="individual"):

@@ -874,3 +874,68 @@ def pose_error_stats(r_error, t_error, r_thresholds, t_thresholds, n_bins, max_t
         check(_pose_metric_lib().f3r_pose_error_stats(ptr(r_error) if n else None, ptr(t_error) if n else None, n, _real_id(r_error.dtype), rt, n_r, tt, n_t,
                                                       int(n_bins), float(max_threshold), ptr(counts), stream_ptr()), "f3r_pose_error_stats")
     return counts
+
+
+def _loss_lib():
+    l = _lib.lib()
+    if l.f3r_version() < _lib.LOSS_ABI_VERSION:
+        raise _lib.F3RError(f"{_lib.LIB_PATH} is version {l.f3r_version()}; the multi-view loss needs >= {_lib.LOSS_ABI_VERSION}: "
+                            "rebuild it (fast3r_amd/csrc/build.sh)")
+    return l
+
+
+def mv_conf_loss(gt_pts, valid_mask, camera_pose, pred_pts, pred_conf, pred_pts_local=None, pred_conf_local=None, *, version=4, dis_mode=0,
+                 gt_scale=False, local_scale_consistent=False, dist_clip=None, alpha=1.0):
+    """ConfLossMultiviewV2(Regr3DMultiviewV3 | V4(L21Loss, avg_dis | avg_log1p), alpha) on the device (f3r_mv_conf_loss, include/f3r.h).
+    Lists over views of GPU tensors: gt_pts / pred_pts / pred_pts_local (B, H, W, 3) fp32, valid_mask (B, H, W) bool or uint8, camera_pose
+    (B, 4, 4) fp32 or fp64, pred_conf / pred_conf_local (B, H, W) fp32; (H, W) may differ between views.  Nothing is concatenated: the
+    kernels read every tensor where it lies (a non-contiguous one is made contiguous first).  -> fp64 device tensor (1 + 4 V):
+    total | pts3d_loss_global | pts3d_loss_local | conf_loss_global | conf_loss_local (the local parts only with a local head)."""
+    V = len(gt_pts)
+    local = pred_pts_local is not None
+    lists = [gt_pts, valid_mask, camera_pose, pred_pts, pred_conf] + ([pred_pts_local, pred_conf_local] if local else [])
+    if V < 1 or any(x is None or len(x) != V for x in lists):
+        raise ValueError("mv_conf_loss: every per-view list must have one entry per view (at least one view); pred_pts_local and "
+                         "pred_conf_local are given together")
+    dev = gt_pts[0].device
+    B = gt_pts[0].shape[0]
+    keep, rows, npix = [], [[] for _ in range(7)], []
+    pose_dtype = camera_pose[0].dtype
+    for v in range(V):
+        g = gt_pts[v]
+        if g.dim() != 4 or g.shape[-1] != 3 or g.shape[0] != B:
+            raise ValueError(f"mv_conf_loss: view {v}: pts3d must be (B = {B}, H, W, 3), got {tuple(g.shape)}")
+        want = {0: (g.shape, torch.float32), 3: (g.shape, torch.float32), 5: (g.shape, torch.float32), 1: (g.shape[:3], None),
+                4: (g.shape[:3], torch.float32), 6: (g.shape[:3], torch.float32), 2: ((B, 4, 4), pose_dtype)}
+        for i, lst in enumerate(lists):
+            t = lst[v]
+            require_gpu(t, f"view {v} of input {i}")
+            shape, dt = want[i]
+            if i == 1:
+                if t.dtype not in (torch.bool, torch.uint8):
+                    raise ValueError(f"mv_conf_loss: view {v}: valid_mask must be bool or uint8, got {t.dtype}")
+            elif t.dtype != dt:
+                raise ValueError(f"mv_conf_loss: view {v}, input {i}: expected {dt}, got {t.dtype}")
+            if tuple(t.shape) != tuple(shape) or t.device != dev:
+                raise ValueError(f"mv_conf_loss: view {v}, input {i}: expected shape {tuple(shape)} on {dev}, got {tuple(t.shape)} on {t.device}")
+            t = t.contiguous()
+            keep.append(t)
+            rows[i].append(t.data_ptr())
+        npix.append(g.shape[1] * g.shape[2])
+    if not local:
+        rows[5] = rows[6] = [0] * V
+    table = torch.tensor(rows + [npix], dtype=torch.int64).to(dev)  # one small upload: 7 pointer tables and the pixel counts
+    l = _loss_lib()
+    ws_bytes = l.f3r_mv_conf_loss_workspace_bytes(V, B)
+    if ws_bytes == 0:
+        raise ValueError(f"mv_conf_loss: {V} views x {B} samples is not a supported shape")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(1 + 4 * V, dtype=torch.float64, device=dev)
+    row = lambda i: table[i].data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        check(l.f3r_mv_conf_loss(row(0), row(1), row(2), _real_id(pose_dtype), row(3), row(4), row(5) if local else None, row(6) if local else None,
+                                 row(7), V, B, int(version), int(dis_mode), int(bool(gt_scale)), int(bool(local_scale_consistent)),
+                                 int(dist_clip is not None), float(dist_clip) if dist_clip is not None else 0.0, float(alpha), ptr(ws), ws_bytes,
+                                 ptr(out), stream_ptr()), "f3r_mv_conf_loss")
+    del keep  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    return out

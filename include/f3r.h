@@ -42,12 +42,13 @@ typedef enum {
 } f3r_status;
 
 typedef enum { F3R_F16 = 0, F3R_BF16 = 1 } f3r_dtype;
-typedef enum { F3R_REAL_F32 = 0, F3R_REAL_F64 = 1 } f3r_real; /* element type of the pose-metric entry points */
+typedef enum { F3R_REAL_F32 = 0, F3R_REAL_F64 = 1 } f3r_real; /* element type of the pose-metric entry points and of the loss's camera poses */
+typedef enum { F3R_LOSS_DIS = 0, F3R_LOSS_LOG1P = 1 } f3r_loss_dis_mode; /* avg_dis / avg_log1p of the multi-view loss */
 
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -506,6 +507,35 @@ int f3r_pose_pair_metrics(const void* pred, const void* gt, int dtype, int n_sam
                           f3r_stream_t stream);
 int f3r_pose_error_stats(const void* r, const void* t, int64_t n, int dtype, const double* r_thresholds, int n_r, const double* t_thresholds,
                          int n_t, int n_bins, double max_threshold, int64_t* counts, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The multi-view confidence loss of validation (ABI 380): ConfLossMultiviewV2(Regr3DMultiviewV3 | V4(L21Loss, "avg_dis" | "avg_log1p"), alpha)
+ * (fast3r/dust3r/losses.py:404-848), forward only, as MultiViewDUSt3RLitModule.model_step calls it on a batch.
+ * Tables: DEVICE arrays of n_views device pointers, one per view; view v has n_pixels[v] (device int64 table) pixels per sample, and the
+ *   views may differ in that.  gt_pts [n_samples][n_pixels][3] fp32, valid_mask [n_samples][n_pixels] bytes (0 / 1), camera_pose
+ *   [n_samples][4][4] cam-to-world in pose_dtype (f3r_real; fp64 is rounded to fp32 first, as the reference's .float() does), pred_pts /
+ *   pred_conf = pts3d_in_other_view / conf, pred_pts_local / pred_conf_local = pts3d_local / conf_local (both NULL: no local head).
+ *   Nothing is stacked, concatenated, compacted or written to; 16-byte loads are used where a sample's base addresses allow them.
+ * Per pixel, in fp64 on the exactly widened inputs: g_glob = inv(P_view 0, b) x and g_loc = inv(P_v, b) x (general 4 x 4 inverse, top
+ *   three rows, as geotrf applies them); with use_dist_clip the global set drops |g_glob| > dist_clip and the local set |g_loc| > dist_clip.
+ *   Factors (each clipped to >= 1e-8, NaN kept): version 4 = per sample over all views the NaN-excluding mean of f(|.|) (global) and per
+ *   (sample, view) (local; with local_scale_consistent the global ones); version 3 = one NaN-propagating mean over the whole batch (global)
+ *   and one per view (local); f = identity (F3R_LOSS_DIS) or log1p (F3R_LOSS_LOG1P); gt_scale sets the ground truth's factors to 1.
+ *   L = |pred / n_pred - gt / n_gt|; per view and set pts3d_loss = mean of L over the valid pixels of all samples (NaN without any) and
+ *   conf_loss = mean of L conf - alpha log conf (exactly 0 without any); total = sum of the conf_losses / (number of them).
+ * out (device, fp64) [1 + 4 n_views] = { total | pts3d_loss_global [n_views] | pts3d_loss_local | conf_loss_global | conf_loss_local }; the
+ *   local parts are meaningless without a local head.  workspace: f3r_mv_conf_loss_workspace_bytes(n_views, n_samples) bytes, 8-byte
+ *   aligned: O(workgroups + n_views n_samples), never O(pixels) (0 for a bad shape).  No floating-point atomics: partial sums are added
+ *   in a fixed order, and two runs on one device give the same bits.
+ * F3R_ERR_ARG before any launch: a null table, workspace or out; n_views < 1; n_samples < 1; alpha <= 0; an unknown version / dis_mode /
+ *   pose_dtype; local_scale_consistent with version 3; one of the two local tables without the other; a workspace too small.
+ */
+size_t f3r_mv_conf_loss_workspace_bytes(int n_views, int n_samples);
+int f3r_mv_conf_loss(const void* const* gt_pts, const void* const* valid_mask, const void* const* camera_pose, int pose_dtype,
+                     const void* const* pred_pts, const void* const* pred_conf, const void* const* pred_pts_local,
+                     const void* const* pred_conf_local, const int64_t* n_pixels, int n_views, int n_samples, int version, int dis_mode,
+                     int gt_scale, int local_scale_consistent, int use_dist_clip, double dist_clip, double alpha, void* workspace,
+                     size_t workspace_bytes, double* out, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).

@@ -1,6 +1,6 @@
 """Kernel micro-benchmarks on the GPU box (interleaved rounds, random data, HIP events on the launch stream): the attention kernels
 f3r_attn_fwd can take (--what attnproduct / attnsel / attnhd) and the model's GEMM / conv shapes per f3r_gemm_args.kernel_sel, with the vendor
-library beside them (--what gemmref).  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
+library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement.  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
 F3R_LAB_LIB=tools/lab/libf3r_hip_lab.so.)"""
 import argparse
 import math
@@ -360,6 +360,100 @@ def bench_pnp(n_views=320, H=512, W=512):
                           "cpu_restatement_ms_per_view": round(cpu_s * 1e3, 1)}), flush=True)
 
 
+def bench_loss(sizes=(100, 320), H=512, W=512, alpha=0.2, out_path="profiles/r08_loss_bench.jsonl"):
+    """The validation criterion ConfLossMultiviewV2(Regr3DMultiviewV4(L21, "avg_dis"), alpha) at B = 1 with local heads, N views of H x W:
+    the device-side criterion (f3r_loss.hip: two streaming passes) against a torch-eager fp32 restatement of the reference's steps
+    (transform per view and frame, concatenate, NaN-fill, norm, nanmean, divide, boolean gathers, means) in the same run on the same GPU.
+    Wall clock per call, synchronised, median of 5 after a warm-up; the launches alone by stream events; achieved bytes/s against the
+    2 x 45 B per pixel the two passes must read.  One JSON line, also appended to profiles/."""
+    import os
+    import statistics
+    import time
+    from fast3r_amd import losses as L
+
+    def wall_ms(fn, reps=5):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts)
+
+    def eager(views, preds, inverses):
+        """fp32, the reference's order of work for V4 / avg_dis / B = 1 (the 4 x 4 inverses are handed in: they are not what is measured)"""
+        nan = float("nan")
+        terms = []
+        for local in (False, True):
+            gts, prs, masks = [], [], []
+            for v, (view, pred) in enumerate(zip(views, preds)):
+                m = inverses[v] if local else inverses[0]
+                gts.append(torch.einsum("bij,bhwj->bhwi", m[:, :3, :3], view["pts3d"]) + m[:, None, None, :3, 3])
+                prs.append(pred["pts3d_local" if local else "pts3d_in_other_view"])
+                masks.append(view["valid_mask"].clone())
+            normed = []
+            for pts_list in (prs, gts):
+                if local:  # one factor per (sample, view)
+                    out = []
+                    for pts, valid in zip(pts_list, masks):
+                        vp = pts.clone().view(pts.shape[0], -1, 3)
+                        vp[valid.view(valid.shape[0], -1) == 0] = nan
+                        f = vp.norm(dim=-1).nanmean(dim=-1).clip(min=1e-8)
+                        out.append(pts / f[:, None, None, None])
+                    normed.append(out)
+                else:  # one factor per sample over all views
+                    allp = torch.cat(pts_list, dim=1)
+                    allp = allp.view(allp.shape[0], -1, 3)
+                    allv = torch.cat(masks, dim=1).view(allp.shape[0], -1)
+                    allp[allv == 0] = nan
+                    f = allp.norm(dim=-1).nanmean(dim=-1).clip(min=1e-8)
+                    normed.append([pts / f[:, None, None, None] for pts in pts_list])
+            for v, (pr, gt, valid) in enumerate(zip(normed[0], normed[1], masks)):
+                l = torch.norm(pr[valid] - gt[valid], dim=-1)
+                c = preds[v]["conf_local" if local else "conf"][valid]
+                terms.append((l * c - alpha * torch.log(c)).mean())
+        return torch.stack(terms).sum() / len(terms)
+
+    crit = L.ConfLossMultiviewV2(L.Regr3DMultiviewV4(L.L21, norm_mode="avg_dis"), alpha=alpha)
+    rec = {"what": "loss", "device": torch.cuda.get_device_name(0), "B": 1, "HW": [H, W], "criterion": repr(crit), "alpha": alpha, "sizes": {}}
+    g = torch.Generator(device=DEV).manual_seed(0)
+    rnd = lambda *s: torch.rand(*s, generator=g, device=DEV)  # noqa: E731
+    for n in sizes:
+        views, preds = [], []
+        for v in range(n):
+            z = 1.0 + 3.0 * rnd(1, H, W)
+            cam = torch.cat([(rnd(1, H, W, 2) - 0.5) * 1.2 * z[..., None], z[..., None]], dim=-1)
+            a = 0.02 * v
+            P = torch.tensor([[[math.cos(a), 0, math.sin(a), 0.01 * v], [0, 1, 0, 0], [-math.sin(a), 0, math.cos(a), 0], [0, 0, 0, 1]]], device=DEV)
+            world = cam @ P[0, :3, :3].T + P[0, :3, 3]
+            views.append({"pts3d": world, "valid_mask": rnd(1, H, W) >= 0.1, "camera_pose": P})
+            preds.append({"pts3d_in_other_view": 1.4 * world + 0.02 * (rnd(1, H, W, 3) - 0.5), "conf": 1.0 + 4.0 * rnd(1, H, W) ** 2,
+                          "pts3d_local": 0.7 * cam + 0.02 * (rnd(1, H, W, 3) - 0.5), "conf_local": 1.0 + 4.0 * rnd(1, H, W) ** 2})
+        inverses = [torch.linalg.inv(view["camera_pose"].cpu()).to(DEV) for view in views]
+        loss, _ = crit(views, preds)
+        ref = eager(views, preds, inverses)
+        crit_ms = wall_ms(lambda: crit(views, preds))
+        eager_ms = wall_ms(lambda: float(eager(views, preds, inverses)), reps=3)
+        lists = ([v["pts3d"] for v in views], [v["valid_mask"] for v in views], [v["camera_pose"] for v in views],
+                 [p["pts3d_in_other_view"] for p in preds], [p["conf"] for p in preds], [p["pts3d_local"] for p in preds], [p["conf_local"] for p in preds])
+        kernel_ms, kernel_best = time_ms(lambda: ops.mv_conf_loss(*lists, version=4, alpha=alpha), rounds=5, inner=3)
+        must_read = 2 * 45 * n * H * W
+        rec["sizes"][str(n)] = {"pixels_per_set": n * H * W, "criterion_call_ms": round(crit_ms, 3), "wrapper_and_launches_stream_ms": round(kernel_ms, 3),
+                                "wrapper_and_launches_stream_best_ms": round(kernel_best, 3), "eager_fp32_restatement_ms": round(eager_ms, 3),
+                                "eager_over_criterion": round(eager_ms / crit_ms, 2), "bytes_2x45_per_pixel": must_read,
+                                "achieved_TB_per_s_of_stream_time": round(must_read / (kernel_ms * 1e-3) / 1e12, 3),
+                                "loss": float(loss), "eager_loss": float(ref), "rel_diff_vs_eager_fp32": abs(float(loss) - float(ref)) / abs(float(ref))}
+        del views, preds, lists, inverses
+        torch.cuda.empty_cache()
+    line = json.dumps(rec)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+
+
 def bench_posemetric(sizes=(320, 1500), H=512, W=512, out_path="profiles/r07_pose_metric_bench.jsonl"):
     """camera_pose_metrics (RRA / RTA / mAA from f3r_pose_pair_metrics) at B = 1 next to estimate_poses at the same view count in the same
     run: the metric stage is O(pairs) trigonometry on a few hundred kilobytes of poses and must stay below 5 % of the PnP stage.  Wall
@@ -642,6 +736,8 @@ if __name__ == "__main__":
         bench_dpt_final()
     if "focal" in args.what:
         bench_focal()
+    if args.what == "loss":  # the validation criterion on the device next to a torch-eager restatement of the reference's steps
+        bench_loss()
     if args.what == "posemetric":  # RRA / RTA / mAA over all view pairs next to the PnP stage that feeds it
         bench_posemetric()
         sys.exit(0)
