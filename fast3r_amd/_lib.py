@@ -141,6 +141,16 @@ SYMBOLS = {
     "f3r_mv_conf_loss": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_vp, ctypes.c_size_t,
                                         _c_vp, _c_vp]),
+    "f3r_scene_sort_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i64]),
+    "f3r_scene_sort": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_i64, _c_vp, _c_vp, ctypes.c_size_t, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                      _c_vp, _c_vp]),
+    "f3r_scene_extent_workspace_bytes": (ctypes.c_size_t, []),
+    "f3r_scene_extent": (ctypes.c_int, [_c_vp, _c_i64, ctypes.POINTER(_c_i64), _c_vp, ctypes.c_size_t, _c_vp, _c_vp]),
+    "f3r_scene_collect_count": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_vp, _c_vp]),
+    "f3r_scene_collect_write": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "f3r_ply_pack": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_vp]),
+    "f3r_color_range": (ctypes.c_int, [_c_vp, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
+    "f3r_color_to_u8": (ctypes.c_int, [_c_vp, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp]),
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")
@@ -157,6 +167,9 @@ ABI_VERSION = 350  # f3r_version() of include/f3r.h this file mirrors (the recon
 RECON_ABI_VERSION = 360
 POSE_METRIC_ABI_VERSION = 370  # f3r_pose_pair_metrics / f3r_pose_error_stats (fast3r_amd/ops.py checks it where it calls them)
 LOSS_ABI_VERSION = 380  # f3r_mv_conf_loss (checked in fast3r_amd/ops.py too)
+SCENE_ABI_VERSION = 390  # f3r_scene_*, f3r_ply_pack, f3r_color_* (checked in fast3r_amd/ops.py too)
+SCENE_TILE = 4096  # F3R_SCENE_TILE: keys per tile of the segmented sort; COLLECT_TILE: entries per tile of collect_points
+COLLECT_TILE = 1024
 
 
 def lib():

@@ -939,3 +939,167 @@ def mv_conf_loss(gt_pts, valid_mask, camera_pose, pred_pts, pred_conf, pred_pts_
                                  ptr(out), stream_ptr()), "f3r_mv_conf_loss")
     del keep  # the launches are stream-ordered before the caching allocator can hand these blocks out again
     return out
+
+
+def _scene_lib():
+    l = _lib.lib()
+    if l.f3r_version() < _lib.SCENE_ABI_VERSION:
+        raise _lib.F3RError(f"{_lib.LIB_PATH} is version {l.f3r_version()}; scene assembly needs >= {_lib.SCENE_ABI_VERSION}: "
+                            "rebuild it (fast3r_amd/csrc/build.sh)")
+    return l
+
+
+def _tile_table(rows, lengths, tile, dev):
+    """rows (one list of int64 per segment) followed by the n + 1 running tile counts, as one device int64 tensor: one small upload"""
+    starts = [0]
+    for n in lengths:
+        starts.append(starts[-1] + (n + tile - 1) // tile)
+    flat = [x for r in rows for x in r] + starts
+    return torch.tensor(flat, dtype=torch.int64).to(dev), starts[-1]
+
+
+def scene_sort(conf, pts, img, mask, lut):
+    """The segmented stable confidence sort with its fused gathers (f3r_scene_sort, include/f3r.h).  Lists over segments of GPU tensors:
+    conf (L,) fp32, pts (L, 3) fp32, img (3, L) fp32 planes, mask (L,) int8 or None; lut (256, 3) uint8 on the device.
+    -> dict(order int32, pts, conf, rgb uint8, conf_rgb uint8, mask int8: concatenated over segments; offsets: the segments' first slots;
+    stats (S, 4) int32 bit patterns of the uint32 words)."""
+    S = len(conf)
+    if S < 1 or len(pts) != S or len(img) != S or len(mask) != S:
+        raise ValueError("scene_sort: need one conf, pts, img and mask entry per segment, and at least one segment")
+    dev = conf[0].device
+    require_gpu(lut, "lut")
+    if lut.dtype != torch.uint8 or lut.numel() != 768:
+        raise ValueError("scene_sort: lut must be 256 x 3 uint8")
+    rows, lengths, keep, off = [], [], [lut.contiguous()], 0
+    f32, i8 = torch.float32, torch.int8
+    for s in range(S):
+        c, p, g, m = conf[s], pts[s], img[s], mask[s]
+        L = c.numel()
+        for t in (c, p, g, m):
+            if t is not None and not t.is_cuda:
+                require_gpu(t, f"segment {s}")
+        if (c.dtype != f32 or p.dtype != f32 or g.dtype != f32 or c.dim() != 1 or p.shape != (L, 3) or g.shape != (3, L)
+                or p.device != dev or g.device != dev or c.device != dev):
+            raise ValueError(f"scene_sort: segment {s}: conf (L,), pts (L, 3), img (3, L), all fp32 on {dev}; got {tuple(c.shape)} {c.dtype}, "
+                             f"{tuple(p.shape)} {p.dtype}, {tuple(g.shape)} {g.dtype}")
+        if m is not None and (m.dtype != i8 or m.shape != (L,) or m.device != dev):
+            raise ValueError(f"scene_sort: segment {s}: mask must be ({L},) int8 on {dev}, got {tuple(m.shape)} {m.dtype} on {m.device}")
+        if not 1 <= L < 2 ** 31:
+            raise ValueError(f"scene_sort: segment {s} has {L} keys; need 1 <= L < 2^31")
+        c, p, g = c.contiguous(), p.contiguous(), g.contiguous()
+        m = None if m is None else m.contiguous()
+        keep += [c, p, g, m]
+        rows.append([c.data_ptr(), p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), L, off])
+        lengths.append(L)
+        off += L
+    total = off
+    table, n_tiles = _tile_table(rows, lengths, _lib.SCENE_TILE, dev)
+    l = _scene_lib()
+    ws_bytes = l.f3r_scene_sort_workspace_bytes(total, n_tiles)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = {"order": torch.empty(total, dtype=torch.int32, device=dev), "pts": torch.empty((total, 3), dtype=torch.float32, device=dev),
+           "conf": torch.empty(total, dtype=torch.float32, device=dev), "rgb": torch.empty((total, 3), dtype=torch.uint8, device=dev),
+           "conf_rgb": torch.empty((total, 3), dtype=torch.uint8, device=dev), "mask": torch.empty(total, dtype=torch.int8, device=dev),
+           "stats": torch.empty((S, 4), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        check(l.f3r_scene_sort(ptr(table), S, n_tiles, total, ptr(keep[0]), ptr(ws), ws_bytes, ptr(out["order"]), ptr(out["pts"]), ptr(out["conf"]),
+                               ptr(out["rgb"]), ptr(out["conf_rgb"]), ptr(out["mask"]), ptr(out["stats"]), stream_ptr()), "f3r_scene_sort")
+    del keep, ws  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    out["offsets"] = [r[5] for r in rows]
+    return out
+
+
+def scene_extent_stats(pts, ranks):
+    """Order statistics `ranks` (four 0-based ranks in ascending order) of each axis of pts (M, 3) fp32 on the GPU (f3r_scene_extent).
+    -> int32 (15,) on the device: 12 fp32 bit patterns [axis][rank], then the NaN count of each axis."""
+    require_gpu(pts, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.shape[0] < 1:
+        raise ValueError(f"scene_extent_stats: pts must be a contiguous (M >= 1, 3) fp32 tensor, got {tuple(pts.shape)} {pts.dtype}")
+    if len(ranks) != 4:
+        raise ValueError("scene_extent_stats: four ranks")
+    l = _scene_lib()
+    ws_bytes = l.f3r_scene_extent_workspace_bytes()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device)
+    out = torch.empty(15, dtype=torch.int32, device=pts.device)
+    rk = (ctypes.c_int64 * 4)(*[int(r) for r in ranks])
+    with torch.cuda.device(pts.device):
+        check(l.f3r_scene_extent(ptr(pts), pts.shape[0], rk, ptr(ws), ws_bytes, ptr(out), stream_ptr()), "f3r_scene_extent")
+    return out
+
+
+def scene_collect(pts, colors, masks, nums, const_colors):
+    """The prefix cut and stable mask compaction of collect_points (f3r_scene_collect_count / _write).  Lists over segments: pts (L, 3) fp32
+    sorted points, colors (L, 3) uint8 or None (then const_colors[s] = (r, g, b) is used), masks (L,) int8 or None (keep all), nums = how
+    many entries to take from the front (1 <= num <= L).  -> (points (M, 3) fp32, colors (M, 3) uint8) on the device, or (None, None) when
+    nothing is kept.  The host reads back one word: the total."""
+    S = len(pts)
+    if S < 1:
+        return None, None
+    dev = pts[0].device
+    rows, keep = [], []
+    for s in range(S):
+        p, c, m, n = pts[s], colors[s], masks[s], int(nums[s])
+        require_gpu(p, f"segment {s} pts")
+        L = p.shape[0]
+        if p.dim() != 2 or p.shape[1] != 3 or p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError(f"scene_collect: segment {s}: pts must be contiguous (L, 3) fp32")
+        if not 1 <= n <= L:
+            raise ValueError(f"scene_collect: segment {s}: num = {n} outside [1, {L}]")
+        if c is not None and (tuple(c.shape) != (L, 3) or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != dev):
+            raise ValueError(f"scene_collect: segment {s}: colors must be contiguous ({L}, 3) uint8 on {dev}")
+        if m is not None and (tuple(m.shape) != (L,) or m.dtype != torch.int8 or not m.is_contiguous() or m.device != dev):
+            raise ValueError(f"scene_collect: segment {s}: mask must be contiguous ({L},) int8 on {dev}")
+        cc = (0, 0, 0) if const_colors[s] is None else const_colors[s]
+        rows.append([p.data_ptr(), 0 if c is None else c.data_ptr(), 0 if m is None else m.data_ptr(), n,
+                     int(cc[0]) | int(cc[1]) << 8 | int(cc[2]) << 16])
+        keep += [p, c, m]
+    table, n_tiles = _tile_table(rows, [r[3] for r in rows], _lib.COLLECT_TILE, dev)
+    l = _scene_lib()
+    scan = torch.empty(n_tiles + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(l.f3r_scene_collect_count(ptr(table), S, n_tiles, ptr(scan), stream_ptr()), "f3r_scene_collect_count")
+        total = int(scan[n_tiles].item()) & 0xffffffff
+        if total == 0:
+            return None, None
+        out_p = torch.empty((total, 3), dtype=torch.float32, device=dev)
+        out_c = torch.empty((total, 3), dtype=torch.uint8, device=dev)
+        check(l.f3r_scene_collect_write(ptr(table), S, n_tiles, ptr(scan), ptr(out_p), ptr(out_c), stream_ptr()), "f3r_scene_collect_write")
+    del keep
+    return out_p, out_c
+
+
+def ply_pack(points, colors_u8):
+    """(M, 3) fp32 points and (M, 3) uint8 colours on the GPU -> uint8 device tensor of the 15 M record bytes (f3r_ply_pack)"""
+    require_gpu(points, "points")
+    require_gpu(colors_u8, "colors")
+    n = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or tuple(colors_u8.shape) != (n, 3) or colors_u8.dtype != torch.uint8:
+        raise ValueError(f"ply_pack: points (M, 3) fp32 and colors (M, 3) uint8, got {tuple(points.shape)} {points.dtype}, "
+                         f"{tuple(colors_u8.shape)} {colors_u8.dtype}")
+    points, colors_u8 = points.contiguous(), colors_u8.contiguous()
+    out = torch.empty((n * 15 + 3) // 4, dtype=torch.int32, device=points.device)
+    with torch.cuda.device(points.device):
+        check(_scene_lib().f3r_ply_pack(ptr(points), ptr(colors_u8), n, ptr(out), stream_ptr()), "f3r_ply_pack")
+    return out.view(torch.uint8)[:n * 15]
+
+
+def color_range(colors):
+    """int64 (3,) on the device: the bit patterns of {key of the minimum, key of the maximum, NaN count} of a float32 / float64 GPU tensor
+    (f3r_color_range; fast3r_amd/scene.py decodes the keys)"""
+    require_gpu(colors, "colors")
+    colors = colors.contiguous()
+    out = torch.empty(3, dtype=torch.int64, device=colors.device)
+    with torch.cuda.device(colors.device):
+        check(_scene_lib().f3r_color_range(ptr(colors), colors.numel(), _real_id(colors.dtype), ptr(out), stream_ptr()), "f3r_color_range")
+    return out
+
+
+def color_to_u8(colors, rule, lo=0.0, hi=1.0):
+    """safe_color_conversion's rule 0 / 1 / 2 in the tensor's own dtype (f3r_color_to_u8) -> uint8 tensor of the same shape"""
+    require_gpu(colors, "colors")
+    colors = colors.contiguous()
+    out = torch.empty(colors.shape, dtype=torch.uint8, device=colors.device)
+    with torch.cuda.device(colors.device):
+        check(_scene_lib().f3r_color_to_u8(ptr(colors), colors.numel(), _real_id(colors.dtype), int(rule), float(lo), float(hi), ptr(out),
+                                           stream_ptr()), "f3r_color_to_u8")
+    return out

@@ -48,7 +48,7 @@ typedef enum { F3R_LOSS_DIS = 0, F3R_LOSS_LOG1P = 1 } f3r_loss_dis_mode; /* avg_
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -536,6 +536,51 @@ int f3r_mv_conf_loss(const void* const* gt_pts, const void* const* valid_mask, c
                      const void* const* pred_conf_local, const int64_t* n_pixels, int n_views, int n_samples, int version, int dis_mode,
                      int gt_scale, int local_scale_consistent, int use_dist_clip, double dist_clip, double alpha, void* workspace,
                      size_t workspace_bytes, double* out, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Scene assembly and PLY export (ABI 390): the per-view body of the reference's viser visualizer (fast3r/viz/viser_visualizer.py:343-427,
+ * :115-165, :168-254) -- np.argsort(-conf) with four gathers, the colourings, the extrema, the percentile scene extent, the prefix cut with
+ * the sky mask and generate_ply_bytes -- on the device.  Python: fast3r_amd/scene.py.
+ *
+ * f3r_scene_sort: a segmented stable sort with fused gathers.  Every (view, head) is a segment.  `table` is a DEVICE int64 array:
+ *   n_segments rows of 6 { conf pointer (len fp32), points pointer (len x 3 fp32), image pointer (3 planes of len fp32, values in [-1, 1]),
+ *   mask pointer (len int8; 0 = no mask: all ones), len (1 <= len < 2^31), off (the segment's first slot in the outputs: the running sum of
+ *   the lengths) }, then n_segments + 1 tile starts (the running sum of ceil(len / F3R_SCENE_TILE)); n_tiles and total_keys are the two totals.
+ *   order[off + j] = np.argsort(-conf, kind='stable')[j]: descending confidence, equal values in pixel order, -0.0 == +0.0, +inf first, NaN
+ *   last in pixel order.  pts / conf / mask = the inputs gathered by that order; rgb = trunc((img + 1) * 127.5) per plane, fp32 with one
+ *   rounding per operation, packed to 3 bytes, saturated outside [0, 255]; conf_rgb = lut[index] with lut the 256 x 3 byte colour table on
+ *   the device and index as matplotlib's Colormap.__call__ gives it for t = (c - min) / (max - min + 1e-8) in fp32 (t * 256 truncated, 256 ->
+ *   255, NaN -> (0, 0, 0); a NaN anywhere in the segment makes every colour (0, 0, 0)).
+ *   stats (device uint32 [n_segments][4]) = { key of the largest conf, key of the smallest, NaN count, count of mask > 0 } where
+ *   key(c) = ~k(c), k the usual order-preserving map (sign bit set: ~bits, else bits | 2^31) of c with -0.0 read as +0.0; no non-NaN value:
+ *   { 0xffffffff, 0 }.  Integer atomics only: two runs give the same bits.  Inputs are not written to.
+ * f3r_scene_extent: the order statistics ranks[0..3] (HOST array, 0-based, ascending order) of each axis of pts [m][3] by exact radix
+ *   select; out (device uint32 [15]) = 12 fp32 bit patterns [axis][rank] and the NaN count of each axis (-0.0 orders below +0.0; NaN
+ *   orders by its bits and is for the caller to act on, as np.percentile returns NaN then).
+ * f3r_scene_collect_count / f3r_scene_collect_write: `table` = n_segments rows of 5 { sorted points pointer, sorted colour pointer (3 bytes
+ *   each; 0 = use the constant colour), sorted mask pointer (0 = keep all), num (entries taken from the front, >= 1), constant colour
+ *   r | g << 8 | b << 16 }, then n_segments + 1 tile starts (running sum of ceil(num / 1024)).  _count writes the exclusive scan of the
+ *   kept counts per tile to scan[0 .. n_tiles) and the total to scan[n_tiles]; _write places the kept entries, in order, at those slots
+ *   of out_pts [total][3] fp32 and out_rgb [total][3] bytes.
+ * f3r_ply_pack: n records of 15 bytes (xyz little-endian fp32, rgb) into out (4-byte aligned, 15 n rounded up to 4 bytes).
+ * f3r_color_range: out (device uint64 [3]) = { key of the minimum, key of the maximum, NaN count } of n fp32 / fp64 (f3r_real) values
+ *   widened to fp64, key = the 64-bit order-preserving map.  f3r_color_to_u8: safe_color_conversion's three rules in the input's own type
+ *   (0: c * 255; 1: (c + 1) * 127.5; 2: ((c - lo) / (hi - lo)) * 255; clipped to [0, 255], truncated; F3R_ERR_ARG for rule 2 with hi == lo).
+ */
+#define F3R_SCENE_TILE 4096
+size_t f3r_scene_sort_workspace_bytes(int64_t total_keys, int64_t n_tiles);
+int f3r_scene_sort(const int64_t* table, int n_segments, int64_t n_tiles, int64_t total_keys, const uint8_t* lut, void* workspace,
+                   size_t workspace_bytes, int32_t* order, float* pts, float* conf, uint8_t* rgb, uint8_t* conf_rgb, int8_t* mask,
+                   uint32_t* stats, f3r_stream_t stream);
+size_t f3r_scene_extent_workspace_bytes(void);
+int f3r_scene_extent(const float* pts, int64_t m, const int64_t* ranks, void* workspace, size_t workspace_bytes, uint32_t* out,
+                     f3r_stream_t stream);
+int f3r_scene_collect_count(const int64_t* table, int n_segments, int64_t n_tiles, uint32_t* scan, f3r_stream_t stream);
+int f3r_scene_collect_write(const int64_t* table, int n_segments, int64_t n_tiles, const uint32_t* scan, float* out_pts, uint8_t* out_rgb,
+                            f3r_stream_t stream);
+int f3r_ply_pack(const float* pts, const uint8_t* rgb, int64_t n, void* out, f3r_stream_t stream);
+int f3r_color_range(const void* colors, int64_t n, int dtype, uint64_t* out, f3r_stream_t stream);
+int f3r_color_to_u8(const void* colors, int64_t n, int dtype, int rule, double lo, double hi, uint8_t* out, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).

@@ -1,6 +1,6 @@
 """Kernel micro-benchmarks on the GPU box (interleaved rounds, random data, HIP events on the launch stream): the attention kernels
 f3r_attn_fwd can take (--what attnproduct / attnsel / attnhd) and the model's GEMM / conv shapes per f3r_gemm_args.kernel_sel, with the vendor
-library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement.  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
+library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement; --what scene: scene assembly and PLY export likewise.  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
 F3R_LAB_LIB=tools/lab/libf3r_hip_lab.so.)"""
 import argparse
 import math
@@ -454,6 +454,143 @@ def bench_loss(sizes=(100, 320), H=512, W=512, alpha=0.2, out_path="profiles/r08
         f.write(line + "\n")
 
 
+def bench_scene(sizes=(100, 320), H=512, W=512, out_path="profiles/r09_scene_bench.jsonl", sort_only=False):
+    """Scene assembly (fast3r_amd/scene.py, f3r_scene.hip) at N views of H x W, both heads, B = 1, poses=False (the pose solve is an
+    existing stage and is timed elsewhere).  Wall clock, synchronised, every shape warmed up, medians with min / max:
+    * `assemble_scene` on device-resident inputs, alternating call by call with a torch-eager restatement of the same steps on the same GPU
+      (one batched torch.sort(stable, descending) over the (2 N, H W) confidences, batched gathers, the colour arithmetic, the extrema, and
+      one torch.sort per axis for the extent's order statistics): the library composition at its best, since the views here share one size;
+    * `assemble_scene` on host inputs as `inference()` returns them (uploads included);
+    * `collect_points` (both heads, 10th percentile, sky mask on) and `generate_ply_bytes` (packing + one pinned copy) separately;
+    * f3r_scene_sort alone by stream events, with the bytes per key it must move (29 B read + 27 B written) over that time;
+    * tests/scene_ref.py (numpy, this machine's CPU) on 8 views, scaled to N: a CPU time, reported as such.
+    sort_only: just a few f3r_scene_sort calls at the first size, for a profiler run of its own.  One JSON line, appended to profiles/."""
+    import os
+    import statistics
+    import time
+    import numpy as np
+    import fast3r_amd
+    from fast3r_amd import scene as S
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import scene_ref as R
+
+    def once_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def stats(ts):
+        return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "n": len(ts)}
+
+    lut = torch.from_numpy(S.turbo_lut_u8().copy()).to(DEV)
+
+    def eager(preds, views, masks):
+        n, L = len(preds), H * W
+        conf = torch.stack([p["conf"].reshape(L) for p in preds] + [p["conf_local"].reshape(L) for p in preds])
+        pts = torch.stack([p["pts3d_in_other_view"].reshape(L, 3) for p in preds] + [p["pts3d_local_aligned_to_global"].reshape(L, 3) for p in preds])
+        img = torch.stack([v["img"].reshape(3, L) for v in views])
+        mask = torch.stack([m.reshape(L) for m in masks])
+        sconf, order = torch.sort(conf, dim=1, descending=True, stable=True)
+        spts = torch.gather(pts, 1, order[:, :, None].expand(-1, -1, 3))
+        order_v = order.view(2, n, L)
+        rgb = torch.stack([((torch.gather(img, 2, order_v[h][:, None, :].expand(-1, 3, -1)) + 1) * 127.5).to(torch.uint8).transpose(1, 2) for h in range(2)])
+        smask = torch.stack([torch.gather(mask, 1, order_v[h]) for h in range(2)])
+        lo, hi = sconf[:, -1:], sconf[:, :1]
+        x = (sconf - lo) / (hi - lo + 1e-8) * 256
+        ccol = lut[torch.where(x >= 256, torch.full_like(x, 255), x).long().clamp_(0, 255)]
+        max_conf = conf[:n].amax(dim=1).cpu()
+        sky = smask[0].float().mean(dim=1).cpu()
+        allp = pts[:n].reshape(-1, 3)
+        m = allp.shape[0]
+        ks = sorted({k for pct in (20, 80) for k in S.percentile_indexes(m, pct)[:2]})
+        ext = torch.sort(allp, dim=0).values[ks].cpu()   # one sort per axis (torch.kthvalue takes 137 ms per call at 26 M values: 40 x this)
+        return order.to(torch.int32), sconf, spts, rgb, smask, ccol, max_conf, sky, ext
+
+    rec = {"what": "scene", "device": torch.cuda.get_device_name(0), "B": 1, "HW": [H, W], "tile": _lib.SCENE_TILE, "sizes": {}}
+    g = torch.Generator(device=DEV).manual_seed(0)
+    rnd = lambda *s: torch.rand(*s, generator=g, device=DEV)  # noqa: E731
+    for n in sizes:
+        preds, views, masks = [], [], []
+        for v in range(n):
+            preds.append({"pts3d_in_other_view": rnd(1, H, W, 3) * 4 - 2, "pts3d_local_aligned_to_global": rnd(1, H, W, 3) * 4 - 2,
+                          "conf": 1.0 + 20.0 * rnd(1, H, W) ** 2, "conf_local": 1.0 + 20.0 * rnd(1, H, W) ** 2})
+            views.append({"img": rnd(1, 3, H, W) * 2 - 1})
+            masks.append((rnd(H, W) < 0.8).to(torch.int8))
+        keys = 2 * n * H * W
+        flat = lambda k, tail: [p[k].reshape(*tail) for p in preds]  # noqa: E731
+        seg = (flat("conf", (H * W,)) + flat("conf_local", (H * W,)), flat("pts3d_in_other_view", (H * W, 3)) + flat("pts3d_local_aligned_to_global", (H * W, 3)),
+               [v["img"].reshape(3, H * W) for v in views] * 2, [m.reshape(-1) for m in masks] * 2)
+        if sort_only:
+            for _ in range(3):
+                ops.scene_sort(*seg, lut)
+            torch.cuda.synchronize()
+            return
+        product = lambda: fast3r_amd.assemble_scene(preds, views, not_sky=masks, poses=False)  # noqa: E731
+        once_ms(product)
+        once_ms(lambda: eager(preds, views, masks))
+        tp, te = [], []
+        for _ in range(5):   # alternating
+            tp.append(once_ms(product)[0])
+            te.append(once_ms(lambda: eager(preds, views, masks))[0])
+            torch.cuda.empty_cache()
+        sort_ms, sort_best = time_ms(lambda: ops.scene_sort(*seg, lut), rounds=5, inner=1)
+        conf_all = torch.stack(seg[0])
+        torch_sort_ms, _ = time_ms(lambda: torch.sort(conf_all, dim=1, descending=True, stable=True), rounds=5, inner=1)
+        del conf_all
+        gpts = torch.cat(seg[1][:n])
+        ranks = sorted({k for pct in (20, 80) for k in S.percentile_indexes(gpts.shape[0], pct)[:2]})
+        extent_ms, _ = time_ms(lambda: ops.scene_extent_stats(gpts, (ranks * 4)[:4]), rounds=5, inner=1)
+        del gpts
+        sc = product()
+        tc, tply = [], []
+        collect = lambda: sc.collect_points(min_conf_thr_percentile=10, mask_sky=True, show_global=True, show_local=True)  # noqa: E731
+        once_ms(collect)
+        for _ in range(3):
+            ms, (p, c) = once_ms(collect)
+            tc.append(ms)
+        once_ms(lambda: fast3r_amd.generate_ply_bytes(p, c))
+        for _ in range(3):
+            ms, ply = once_ms(lambda: fast3r_amd.generate_ply_bytes(p, c))
+            tply.append(ms)
+        n_points, ply_len = int(p.shape[0]), len(ply)
+        del sc, p, c, ply
+        torch.cuda.empty_cache()
+        host = {"preds": [{k: v.cpu() for k, v in pr.items()} for pr in preds], "views": [{k: v.cpu() for k, v in vw.items()} for vw in views]}
+        host_masks = [m.cpu() for m in masks]
+        th = []
+        once_ms(lambda: fast3r_amd.assemble_scene(host, not_sky=host_masks, poses=False))
+        for _ in range(2):
+            th.append(once_ms(lambda: fast3r_amd.assemble_scene(host, not_sky=host_masks, poses=False))[0])
+        # the numpy restatement on this machine's CPU: 8 views, scaled to n
+        lut_np = S.turbo_lut_u8()
+        t0 = time.perf_counter()
+        frames = []
+        for i in range(8):
+            pred = {k: v[0].numpy() for k, v in host["preds"][i].items()}
+            frames.append(R.frame_data(pred, {"img": host["views"][i]["img"][0].numpy()}, host_masks[i].numpy(), i, 8, 1.5, lut_np))
+        R.scene_extent([f["sorted_pts3d_global"] for f in frames])
+        cpu8_ms = (time.perf_counter() - t0) * 1e3
+        must = 56 * keys
+        p_med, e_med = statistics.median(tp), statistics.median(te)
+        rec["sizes"][str(n)] = {
+            "keys": keys, "assemble_scene_device_inputs": stats(tp), "eager_torch_restatement": stats(te), "eager_over_product": round(e_med / p_med, 3),
+            "f3r_scene_sort_stream_ms": round(sort_ms, 3), "f3r_scene_sort_stream_best_ms": round(sort_best, 3), "torch_sort_alone_stream_ms": round(torch_sort_ms, 3),
+            "f3r_scene_extent_stream_ms": round(extent_ms, 3), "bytes_must_move_per_key": 56,
+            "sort_TB_per_s_of_must_move_bytes": round(must / (sort_ms * 1e-3) / 1e12, 3), "assemble_scene_host_inputs": stats(th),
+            "collect_points": stats(tc), "collected_points": n_points, "generate_ply_bytes": stats(tply), "ply_bytes": ply_len,
+            "cpu_numpy_restatement_8_views_ms": round(cpu8_ms, 1), "cpu_numpy_restatement_scaled_to_n_ms": round(cpu8_ms * n / 8, 1),
+            "cpu_scaled_over_product": round(cpu8_ms * n / 8 / p_med, 1)}
+        del preds, views, masks, host, host_masks, seg, frames
+        torch.cuda.empty_cache()
+    line = json.dumps(rec)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+
+
 def bench_posemetric(sizes=(320, 1500), H=512, W=512, out_path="profiles/r07_pose_metric_bench.jsonl"):
     """camera_pose_metrics (RRA / RTA / mAA from f3r_pose_pair_metrics) at B = 1 next to estimate_poses at the same view count in the same
     run: the metric stage is O(pairs) trigonometry on a few hundred kilobytes of poses and must stay below 5 % of the PnP stage.  Wall
@@ -738,6 +875,12 @@ if __name__ == "__main__":
         bench_focal()
     if args.what == "loss":  # the validation criterion on the device next to a torch-eager restatement of the reference's steps
         bench_loss()
+    if args.what == "scene":  # scene assembly and PLY export next to a torch-eager restatement and the numpy restatement on the CPU
+        bench_scene()
+        sys.exit(0)
+    if args.what == "scenesort":  # f3r_scene_sort alone at N = 100, for a profiler run of its own
+        bench_scene(sizes=(100,), sort_only=True)
+        sys.exit(0)
     if args.what == "posemetric":  # RRA / RTA / mAA over all view pairs next to the PnP stage that feeds it
         bench_posemetric()
         sys.exit(0)
