@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "f3r_common.h"
+#include "f3r_prims.h"
 
 namespace {
 
@@ -138,34 +139,6 @@ __device__ inline int block_of_tile(long long t, long long T, int nb) {
   return (int)k;
 }
 
-// the segment s with tile0[s] <= t < tile0[s + 1] (segments without pixels own no tile)
-__device__ inline int segment_of_tile(const long long* tile0, int nseg, long long t) {
-  int lo = 0, hi = nseg;  // first index with tile0[index] > t lies in (lo, hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) / 2;
-    if (tile0[mid] <= t) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-template <int N>
-__device__ inline void block_sum_store(double (&a)[N], double* dst) {
-  __shared__ double red[WAVES][N];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = 0; i < N; ++i) {
-    double x = a[i];
-    for (int off = 32; off; off >>= 1) x += __shfl_down(x, off);
-    if (lane == 0) red[wave][i] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    double x = red[0][threadIdx.x];
-    for (int k = 1; k < WAVES; ++k) x += red[k][threadIdx.x];
-    dst[threadIdx.x] = x;
-  }
-  __syncthreads();
-}
-
 struct Segment {
   const float *gt, *pred, *conf, *pred_l, *conf_l;
   const uint8_t* valid;
@@ -244,15 +217,16 @@ __global__ __launch_bounds__(THREADS) void loss_pass_kernel(Tables tab, Work w, 
   const long long ta = first_tile(k, T, nb), tb = first_tile(k + 1, T, nb);
   if (ta >= tb) return;
   double* part = PASS_B ? w.part_b : w.part_a;
+  __shared__ double red[WAVES][N];
   double acc[N];
   for (int i = 0; i < N; ++i) acc[i] = 0.0;
-  int s = segment_of_tile(w.tile0, p.nseg, ta);
+  int s = last_le(w.tile0, 0, p.nseg, ta);  // tile0[s] <= ta < tile0[s + 1] (segments without pixels own no tile)
   Segment g;
   load_segment<PASS_B>(g, tab, w, p, s);
   const bool local = tab.pred_l != nullptr;
   for (long long t = ta; t < tb; ++t) {
     if (t >= w.tile0[s + 1]) {
-      block_sum_store<N>(acc, part + (long long)(k + s) * N);
+      block_sum<N, THREADS>(acc, red, part + (long long)(k + s) * N);
       for (int i = 0; i < N; ++i) acc[i] = 0.0;
       do ++s; while (t >= w.tile0[s + 1]);
       load_segment<PASS_B>(g, tab, w, p, s);
@@ -307,7 +281,7 @@ __global__ __launch_bounds__(THREADS) void loss_pass_kernel(Tables tab, Work w, 
       if (local) pixel_set<PASS_B>(g.ml, x + e * 3, ok[e] != 0, pl + e * 3, PASS_B ? cl[e] : 1.f, p, g.fac[2], g.fac[3], acc + PER_SET);
     }
   }
-  block_sum_store<N>(acc, part + (long long)(k + s) * N);
+  block_sum<N, THREADS>(acc, red, part + (long long)(k + s) * N);
 }
 
 // sums the partials of every segment in slot order: the workgroups from block_of_tile(first tile) to block_of_tile(last tile) that own a tile met it
@@ -341,10 +315,8 @@ __device__ inline void group_factors(const double* mom, int set, int n_groups, i
       const long long s = (long long)grp * base_mul + (long long)j * stride;
       for (int i = 0; i < 5; ++i) m[i] += mom[s * NA + set * 5 + i];
     }
-    for (int i = 0; i < 5; ++i) {
-      for (int off = 32; off; off >>= 1) m[i] += __shfl_down(m[i], off);
-      m[i] = __shfl(m[i], 0);
-    }
+    for (int i = 0; i < 5; ++i)
+      m[i] = __shfl(wave_sum(m[i]), 0);  // lane 0's sum, for every lane
     // V4: nanmean, the sum and the count of what is not NaN (0 / 0 = NaN for a sample without valid pixels); V3: mean over the valid pixels,
     // NaN as soon as one of them is NaN.  clip(min = 1e-8) leaves NaN as it is.
     double f_gt = p.version == 4 ? m[2] / m[1] : (m[1] != m[0] ? (double)NAN : m[2] / m[0]);

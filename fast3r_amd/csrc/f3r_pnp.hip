@@ -18,6 +18,7 @@
 // Same algorithm, independently written on torch.linalg: oracle/pnp_oracle.py.  All passes re-read the view's 4 MB from L2.
 #include "f3r_common.h"
 #include "f3r_linalg.h"
+#include "f3r_prims.h"
 #include "f3r_sqpnp.h"
 
 namespace {
@@ -38,26 +39,6 @@ struct Pose {  // world -> camera
   double f;
   int ok;
 };
-
-// block sum of K doubles held per thread in v[]; result broadcast to every thread through out[]
-template <int K>
-__device__ void block_sum(double* v, double (*red)[48], double* out) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    double a = v[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-    if (lane == 0) red[wv][k] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double s = 0.0;
-    for (int w = 0; w < NW_; ++w) s += red[w][threadIdx.x];
-    out[threadIdx.x] = s;
-  }
-  __syncthreads();
-}
 
 // moments layout (40): S0 (10 upper-triangular entries of sum P P^T), S1x (10), S1y (10), S2 (10); P = [xn yn zn 1]
 __device__ __forceinline__ void add_moments(double* m, const double P[4], double px, double py) {
@@ -204,7 +185,7 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
       const double x = pt[i * 3], y = pt[i * 3 + 1], z = pt[i * 3 + 2];
       acc[0] += 1.0; acc[1] += x; acc[2] += y; acc[3] += z; acc[4] += x * x + y * y + z * z;
     }
-  block_sum<5>(acc, red, sums);
+  block_sum<5, PT>(acc, red, sums);
   const double n_mask = sums[0];
   if (n_mask < 4.0) {  // init_im_poses.py:302-303
     fail();
@@ -275,7 +256,7 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
           acc[2 * q + 1] += inl ? e2 : (double)THR2;
         }
       }
-      block_sum<16>(acc, red, sums);
+      block_sum<16, PT>(acc, red, sums);
       for (int q = 0; q < 8; ++q)
         if (hyp[h0 + q].ok && (sums[2 * q] > best_cnt || (sums[2 * q] == best_cnt && sums[2 * q] > 0 && sums[2 * q + 1] < best_cost))) {
           best_cnt = sums[2 * q];
@@ -306,7 +287,7 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
       const double Pn[4] = {(x - cen[0]) * isig, (y - cen[1]) * isig, (z - cen[2]) * isig, 1.0};
       add_moments(acc, Pn, px, py);
     }
-    block_sum<40>(acc, red, sums);
+    block_sum<40, PT>(acc, red, sums);
   }
   if (tid == 0) {
     double m[40], a[4], b[4], c[4];
@@ -367,7 +348,7 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
           acc[21 + r] += Jx[r] * ex + Jy[r] * ey;
         }
       }
-      block_sum<30>(acc, red, sums);
+      block_sum<30, PT>(acc, red, sums);
       if (it == N_GN) break;
       if (tid == 0 && sums[28] >= 4.0) {
         double Hm[6][6], g[6], d[6];
@@ -434,7 +415,7 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
       const double Mn[3] = {(X - cen[0]) * isig, (Y - cen[1]) * isig, (Z - cen[2]) * isig};
       f3r_sqpnp::accumulate(acc, Mn, px * inv_f, py * inv_f);
     }
-    block_sum<f3r_sqpnp::N_SUMS>(acc, red, sums);
+    block_sum<f3r_sqpnp::N_SUMS, PT>(acc, red, sums);
     if (tid == 0) {
       f3r_sqpnp::Result r;
       cur = P;

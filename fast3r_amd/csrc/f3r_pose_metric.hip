@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "f3r_common.h"
+#include "f3r_prims.h"
 
 namespace {
 
@@ -34,18 +35,10 @@ __device__ inline double acos_extrapolated(double x) {
 // One pair's contribution to its workgroup's counters.  Every thread of the workgroup calls this the same number of times (`live`
 // false for the padding of a tile), because the threshold counts are wave ballots.  cnt: LDS, p.stride() entries.
 __device__ inline void accumulate(const MetricParams& p, bool live, double r, double t, bool bad_trace, bool defaulted, int* cnt) {
-  const int lane = threadIdx.x & 63;
-  for (int k = 0; k < p.n_r; ++k) {
-    unsigned long long m = __ballot(live && r < p.r_thr[k]);
-    if (lane == 0 && m) atomicAdd(&cnt[k], __popcll(m));
-  }
-  for (int k = 0; k < p.n_t; ++k) {
-    unsigned long long m = __ballot(live && t < p.t_thr[k]);
-    if (lane == 0 && m) atomicAdd(&cnt[p.n_r + k], __popcll(m));
-  }
-  unsigned long long mb = __ballot(live && bad_trace), md = __ballot(live && defaulted);
-  if (lane == 0 && mb) atomicAdd(&cnt[p.n_r + p.n_t + p.n_bins], __popcll(mb));
-  if (lane == 0 && md) atomicAdd(&cnt[p.n_r + p.n_t + p.n_bins + 1], __popcll(md));
+  for (int k = 0; k < p.n_r; ++k) wave_count_add(live && r < p.r_thr[k], &cnt[k]);
+  for (int k = 0; k < p.n_t; ++k) wave_count_add(live && t < p.t_thr[k], &cnt[p.n_r + k]);
+  wave_count_add(live && bad_trace, &cnt[p.n_r + p.n_t + p.n_bins]);
+  wave_count_add(live && defaulted, &cnt[p.n_r + p.n_t + p.n_bins + 1]);
   if (!live) return;
   // torch.max propagates NaN; torch.histc(bins, 0, max) drops NaN and what lies outside [0, max], and puts max itself into the last bin
   const double m = (r != r || t != t) ? NAN : (r > t ? r : t);

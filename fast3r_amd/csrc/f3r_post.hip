@@ -25,7 +25,7 @@ __global__ __launch_bounds__(PNT) void align_stats_kernel(const float* __restric
                                                           double* __restrict__ ws, int64_t npix, float q) {
   __shared__ uint32_t hist[2048];
   __shared__ int64_t sh_i64[2];
-  __shared__ double red[16][34];
+  __shared__ double red[PNT / 64][34];
   __shared__ float sh_thr;
   const int64_t prob = blockIdx.x;
   const float* cf = conf + prob * npix;
@@ -37,9 +37,9 @@ __global__ __launch_bounds__(PNT) void align_stats_kernel(const float* __restric
   const float thr = block_quantile<PNT>(cf, npix, q, hist, sh_i64, &sh_thr);
 
   // ---- 2./3. masked raw moments in fp64: n, sum x(3), sum y(3), sum y_i x_j (9), sum |x|^2   for both masks
-  double mA[17], mB[17];
+  double m[34];  // [0..16] mask A, [17..33] mask B
 #pragma unroll
-  for (int i = 0; i < 17; ++i) { mA[i] = 0.0; mB[i] = 0.0; }
+  for (int i = 0; i < 34; ++i) m[i] = 0.0;
   for (int64_t i = threadIdx.x; i < npix; i += PNT) {
     const bool v = vm ? (vm[i] != 0) : true;
     if (!v) continue;
@@ -50,27 +50,11 @@ __global__ __launch_bounds__(PNT) void align_stats_kernel(const float* __restric
                           x0 * x0 + x1 * x1 + x2 * x2};
 #pragma unroll
     for (int j = 0; j < 17; ++j) {
-      mB[j] += t[j];
-      if (a) mA[j] += t[j];
+      m[17 + j] += t[j];
+      if (a) m[j] += t[j];
     }
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 17; ++j) {
-    double a = mA[j], b = mB[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      a += __shfl_xor(a, off, 64);
-      b += __shfl_xor(b, off, 64);
-    }
-    if (lane == 0) { red[wv][j] = a; red[wv][17 + j] = b; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 34) {
-    double s = 0.0;
-    for (int w = 0; w < PNT / 64; ++w) s += red[w][threadIdx.x];
-    ws[prob * WS_PER + threadIdx.x] = s;
-  }
+  block_sum<34, PNT>(m, red, ws + prob * WS_PER);
   if (threadIdx.x == 0) ws[prob * WS_PER + 34] = (double)thr;
 }
 
@@ -113,25 +97,12 @@ __global__ void align_thr_kernel(const double* __restrict__ ws, float* __restric
 // workgroup per view: pass 0 writes (px, py, x/z, y/z) of the points above the threshold into the workspace (zeros elsewhere:
 // such a point weighs 1e8 on two zero terms), every iteration is then one pass over that 16-byte-per-pixel image (it stays in L2)
 // with fp32 per-point arithmetic in the reference's operation order (no fma contraction) and fp64 block sums.
+// a, b <- their block sums, in every thread (the next call writes out2 after its first barrier, which every thread reaches after these reads)
 __device__ __forceinline__ void block_sum2(double& a, double& b, double (*red)[2], double* out2) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_xor(a, off, 64);
-    b += __shfl_xor(b, off, 64);
-  }
-  if (lane == 0) { red[wv][0] = a; red[wv][1] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int w = 0; w < PNT / 64; ++w) { s0 += red[w][0]; s1 += red[w][1]; }
-    out2[0] = s0;
-    out2[1] = s1;
-  }
-  __syncthreads();
+  const double v[2] = {a, b};
+  block_sum<2, PNT>(v, red, out2);
   a = out2[0];
   b = out2[1];
-  __syncthreads();
 }
 
 __global__ __launch_bounds__(PNT) void focal_kernel(const float* __restrict__ pts, const float* __restrict__ conf, float4v* __restrict__ work,

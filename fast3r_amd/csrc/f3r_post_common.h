@@ -1,19 +1,11 @@
-// Device pieces shared by the post-processing kernels (f3r_post.hip: align / focal; f3r_recon.hip: evaluate_reconstruction):
-// the exact torch.quantile of a block's values by radix select over order-preserving 32-bit keys, and the Umeyama similarity
-// solve from fp64 raw moments.  Header-only (inline device functions and templates).
+// The two solvers shared by the post-processing kernels (f3r_post.hip: align / focal; f3r_recon.hip: evaluate_reconstruction):
+// the exact torch.quantile of a block's values by radix select over the order-preserving 32-bit keys of f3r_prims.h, and the
+// Umeyama similarity solve from fp64 raw moments.  The wave and block primitives (keys, ballots, sums, the scan kernel) live in
+// f3r_prims.h, which this header brings along.  Header-only (inline device functions and templates).
 #pragma once
 
 #include "f3r_linalg.h"
-
-// float -> unsigned key with the same ordering (handles negatives too; conf is >= vmin > 0 in practice)
-__device__ __forceinline__ uint32_t fkey(float f) {
-  const uint32_t u = __builtin_bit_cast(uint32_t, f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __builtin_bit_cast(float, u);
-}
+#include "f3r_prims.h"
 
 // k-th smallest key (0-based) of conf[0..n) by radix select over 11 + 11 + 10 bits; all NT threads return the same value.
 template <int NT>

@@ -18,7 +18,6 @@
 #include <algorithm>
 #include <cstddef>
 #include <cmath>
-#include <cstring>
 
 #include "f3r_linalg.h"
 #include "f3r_post_common.h"
@@ -58,7 +57,6 @@ static_assert(sizeof(NNHeader) <= HDR_BYTES && 64 + sizeof(NNHeader) <= MISC_BYT
 static_assert(sizeof(Grid) == 88 && offsetof(NNHeader, ngrid) == 176, "tests/test_recon_metric_gpu.py reads ngrid at byte 176");
 
 inline int64_t tiles_of(int64_t n) { return (n + TILE - 1) / TILE; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int64_t dense_cap(int64_t m) { return 2 * m + DENSE_EXTRA; }
 
 __device__ __forceinline__ const float4v* hdr_recs(const uint8_t* ix) { return (const float4v*)(ix + HDR_BYTES); }
@@ -139,33 +137,6 @@ __global__ __launch_bounds__(64) void radix_hist_kernel(const uint32_t* __restri
   for (int d = threadIdx.x; d < 256; d += 64) hist[(int64_t)d * ntiles + blockIdx.x] = cnt[d];  // digit-major: the scan gives slot bases
 }
 
-// exclusive scan of each row (blockIdx.x) of `len` uint32 in place; totals[row] = the row's sum (if totals)
-__global__ __launch_bounds__(1024) void scan_rows_kernel(uint32_t* __restrict__ a, int64_t len, uint32_t* __restrict__ totals) {
-  __shared__ uint32_t sh[1024];
-  uint32_t* r = a + (int64_t)blockIdx.x * len;
-  const int64_t per = (len + 1023) / 1024;
-  const int64_t b0 = min((int64_t)threadIdx.x * per, len), b1 = min(b0 + per, len);
-  uint32_t s = 0;
-  for (int64_t i = b0; i < b1; ++i) s += r[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const uint32_t t = threadIdx.x >= (unsigned)off ? sh[threadIdx.x - off] : 0u;
-    __syncthreads();
-    sh[threadIdx.x] += t;
-    __syncthreads();
-  }
-  uint32_t run = sh[threadIdx.x] - s;
-  for (int64_t i = b0; i < b1; ++i) {
-    const uint32_t v = r[i];
-    r[i] = run;
-    run += v;
-  }
-  if (threadIdx.x == 1023 && totals) totals[blockIdx.x] = sh[1023];
-}
-
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-
 __global__ __launch_bounds__(64) void radix_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, int64_t n, int shift,
                                                            const uint32_t* __restrict__ hist, int64_t ntiles, uint32_t* __restrict__ kout,
                                                            uint32_t* __restrict__ vout) {
@@ -179,13 +150,7 @@ __global__ __launch_bounds__(64) void radix_scatter_kernel(const uint32_t* __res
     const bool ok = i < end;
     const uint32_t k = ok ? kin[i] : 0u;
     const uint32_t d = (k >> shift) & 255u;
-    uint64_t peers = __ballot(ok);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t bal = __ballot(bit);
-      peers &= bit ? bal : ~bal;
-    }
+    const uint64_t peers = digit_peers(d, ok);
     const uint32_t slot = run[d] + (uint32_t)__popcll(peers & lanes_below());  // lanes of the same digit keep their order
     __syncthreads();
     if (ok) {
@@ -204,7 +169,7 @@ int radix_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t*
   for (int shift = 0; shift < key_bits; shift += 8) {
     uint32_t *ki = cur ? k1 : k0, *vi = cur ? v1 : v0, *ko = cur ? k0 : k1, *vo = cur ? v0 : v1;
     hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)nt), dim3(64), 0, s, ki, n, shift, hist, nt);
-    hipLaunchKernelGGL(scan_rows_kernel, dim3(1), dim3(1024), 0, s, hist, 256 * nt, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(1), dim3(SCAN_NT), 0, s, hist, (const int64_t*)nullptr, 256 * nt, (uint32_t*)nullptr);
     hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)nt), dim3(64), 0, s, ki, vi, n, shift, hist, nt, ko, vo);
     cur ^= 1;
   }
@@ -213,9 +178,7 @@ int radix_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t*
 
 __global__ void count_heads_kernel(const uint32_t* __restrict__ keys, int64_t n, uint32_t* __restrict__ count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool head = i < n && (i == 0 || keys[i] != keys[i - 1]);
-  const uint64_t b = __ballot(head);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+  wave_count_add(i < n && (i == 0 || keys[i] != keys[i - 1]), count);
 }
 
 __global__ void dense_start_kernel(const uint32_t* __restrict__ keys, int64_t m, int64_t ncells, uint32_t* __restrict__ start) {
@@ -452,15 +415,6 @@ __global__ __launch_bounds__(KNT) void knn_normals_kernel(const uint8_t* __restr
 // statistics
 constexpr int RED_BLOCKS = 256, RED_NT = 256;
 
-__device__ __forceinline__ uint64_t dkey(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dkey_inv(uint64_t k) {
-  const uint64_t u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __builtin_bit_cast(double, u);
-}
-
 // dots[i] = |nq[i] . ndb[idx[i]]|, numpy's ((a0 b0 + a1 b1) + a2 b2)
 __global__ void dots_kernel(const int32_t* __restrict__ idx, const double* __restrict__ nq, const double* __restrict__ ndb, int64_t n,
                             int64_t m_db, double* __restrict__ dots) {
@@ -486,19 +440,8 @@ __global__ __launch_bounds__(RED_NT) void reduce_kernel(const double* __restrict
     if (dots) b += dots[i];
     c += (dist[i] < th) ? 1.0 : 0.0;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_xor(a, off, 64);
-    b += __shfl_xor(b, off, 64);
-    c += __shfl_xor(c, off, 64);
-  }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) { red[wv][0] = a; red[wv][1] = b; red[wv][2] = c; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = 0.0;
-    for (int w = 0; w < RED_NT / 64; ++w) s += red[w][threadIdx.x];
-    partial[blockIdx.x * 3 + threadIdx.x] = s;
-  }
+  const double v[3] = {a, b, c};
+  block_sum<3, RED_NT>(v, red, partial + blockIdx.x * 3);
 }
 
 // out[0] = mean dist, out[2] = mean dots, out[4] = completion ratio as np.mean(float32 (d < th)) computes it (exact counts below 2^24)
@@ -602,14 +545,6 @@ __global__ __launch_bounds__(PNT) void recon_thr_kernel(const float* __restrict_
   }
 }
 
-__device__ __forceinline__ int seg_of(const int64_t* __restrict__ seg, int lo, int hi, int64_t g) {  // last s in [lo, hi) with seg[s] <= g
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (seg[mid] <= g) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // masks of pixel g: bit 0 = pred / ICP-GT (valid & conf >= thr_metric), bit 1 = metrics GT (valid), bit 2 = ICP weight (conf >= thr_icp)
 __device__ __forceinline__ uint32_t pix_mask(const float* conf, const uint8_t* valid, const float* thr, int s, int64_t g) {
   const float c = conf[g];
@@ -624,14 +559,12 @@ __global__ __launch_bounds__(64) void recon_count_kernel(const float* __restrict
   uint32_t a = 0, b = 0;
   for (int64_t p = base + threadIdx.x; p < end; p += 64) {
     const int64_t g = (int64_t)i * L + p;
-    const uint32_t mk = pix_mask(conf, valid, thr, seg_of(seg, i * V, (i + 1) * V, g), g);
+    const uint32_t mk = pix_mask(conf, valid, thr, last_le(seg, i * V, (i + 1) * V, g), g);
     a += mk & 1u;
     b += (mk >> 1) & 1u;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_xor(a, off, 64);
-    b += __shfl_xor(b, off, 64);
-  }
+  a = wave_sum(a);
+  b = wave_sum(b);
   if (threadIdx.x == 0) {
     cnt[(int64_t)i * ntiles + blockIdx.x] = a;
     cnt[((int64_t)gridDim.y + i) * ntiles + blockIdx.x] = b;
@@ -649,10 +582,11 @@ __global__ __launch_bounds__(64) void recon_compact_kernel(const float* __restri
   for (int64_t c = base; c < end; c += 64) {
     const int64_t p = c + threadIdx.x;
     const int64_t g = (int64_t)i * L + p;
-    const uint32_t mk = p < end ? pix_mask(conf, valid, thr, seg_of(seg, i * V, (i + 1) * V, g), g) : 0u;
-    const uint64_t ba = __ballot(mk & 1u), bb = __ballot(mk & 2u);
+    const uint32_t mk = p < end ? pix_mask(conf, valid, thr, last_le(seg, i * V, (i + 1) * V, g), g) : 0u;
+    uint64_t ba, bb;
+    const uint32_t ka = compact_rank(mk & 1u, ba), kb = compact_rank(mk & 2u, bb);
     if (mk & 1u) {
-      const int64_t o = (int64_t)i * L + ra + __popcll(ba & lanes_below());
+      const int64_t o = (int64_t)i * L + ra + ka;
       for (int a = 0; a < 3; ++a) {
         pred_c[o * 3 + a] = pred[g * 3 + a];
         gticp_c[o * 3 + a] = gt[g * 3 + a];
@@ -660,7 +594,7 @@ __global__ __launch_bounds__(64) void recon_compact_kernel(const float* __restri
       w_c[o] = (mk & 4u) ? 1 : 0;
     }
     if (mk & 2u) {
-      const int64_t o = (int64_t)i * L + rb + __popcll(bb & lanes_below());
+      const int64_t o = (int64_t)i * L + rb + kb;
       for (int a = 0; a < 3; ++a) gt_c[o * 3 + a] = gt[g * 3 + a];
     }
     ra += (uint32_t)__popcll(ba);
@@ -690,21 +624,7 @@ __global__ __launch_bounds__(PNT) void recon_register_kernel(const float* __rest
 #pragma unroll
     for (int j = 0; j < 17; ++j) m[j] += t[j];
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 17; ++j) {
-    double a = m[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
-    if (lane == 0) red[wv][j] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x < 17) {
-    double s = 0.0;
-    for (int w = 0; w < PNT / 64; ++w) s += red[w][threadIdx.x];
-    mm[threadIdx.x] = s;
-  }
-  __syncthreads();
+  block_sum<17, PNT>(m, red, mm);
   if (threadIdx.x == 0) {
     if (mm[0] < 3.0) identity_rts(rts + i * 13);
     else similarity_from_moments(mm, rts + i * 13);
@@ -728,9 +648,7 @@ __global__ void recon_apply_kernel(const float* __restrict__ x_c, const float* _
 // count of non-finite coordinates (integer atomics)
 __global__ void nonfinite_kernel(const float* __restrict__ p, int64_t n3, uint32_t* __restrict__ count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool bad = i < n3 && !isfinite(p[i]);
-  const uint64_t b = __ballot(bad);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+  wave_count_add(i < n3 && !isfinite(p[i]), count);
 }
 
 __global__ void deinterleave_kernel(const float* __restrict__ p, int64_t m, float* __restrict__ x, float* __restrict__ y, float* __restrict__ z) {
@@ -754,17 +672,13 @@ __global__ __launch_bounds__(PNT) void axis_quantiles_kernel(const float* __rest
 // count of points outside the box g
 __global__ void outside_kernel(const float* __restrict__ p, int64_t m, Grid g, uint32_t* __restrict__ count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool out = i < m && !in_box(g, p[i * 3 + 0], p[i * 3 + 1], p[i * 3 + 2]);
-  const uint64_t b = __ballot(out);
-  if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (uint32_t)__popcll(b));
+  wave_count_add(i < m && !in_box(g, p[i * 3 + 0], p[i * 3 + 1], p[i * 3 + 2]), count);
 }
 
 __global__ void to_i32_kernel(const uint32_t* __restrict__ a, int n, int32_t* __restrict__ o) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) o[t] = (int32_t)a[t];
 }
-
-inline unsigned blocks_of(int64_t n, int nt) { return (unsigned)((n + nt - 1) / nt); }
 
 // the sort buffers of f3r_nn_workspace_bytes(n), carved from ws
 struct SortWs {
@@ -857,15 +771,9 @@ extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t ind
   (void)hipMemcpyAsync(bb, w.misc, sizeof(bb), hipMemcpyDeviceToHost, s);
   if (hipStreamSynchronize(s) != hipSuccess) return f3r_check_launch("f3r_nn_build");
   double lo[3], hi[3];
-  auto kinv = [](uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    float f;
-    memcpy(&f, &u, 4);
-    return (double)f;
-  };
   for (int a = 0; a < 3; ++a) {
-    lo[a] = kinv(bb[a]);
-    hi[a] = kinv(bb[3 + a]);
+    lo[a] = (double)fkey_inv(bb[a]);
+    hi[a] = (double)fkey_inv(bb[3 + a]);
     F3R_REQUIRE(std::isfinite(lo[a]) && std::isfinite(hi[a]), "f3r_nn_build: non-finite coordinates (NaN or inf)");
   }
   double ext = 0.0;
@@ -1055,7 +963,7 @@ extern "C" int f3r_recon_prepare(const float* conf, const float* pred, const flo
   uint8_t* w_c = (uint8_t*)p;
   hipLaunchKernelGGL(recon_thr_kernel, dim3(B * V), dim3(PNT), 0, s, conf, seg, q_metric, q_icp, thr);
   hipLaunchKernelGGL(recon_count_kernel, dim3((unsigned)nt, B), dim3(64), 0, s, conf, valid, seg, thr, V, L, nt, cnt);
-  hipLaunchKernelGGL(scan_rows_kernel, dim3(2 * B), dim3(1024), 0, s, cnt, nt, tot);
+  hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(2 * B), dim3(SCAN_NT), 0, s, cnt, (const int64_t*)nullptr, nt, tot);
   hipLaunchKernelGGL(recon_compact_kernel, dim3((unsigned)nt, B), dim3(64), 0, s, conf, pred, gt, valid, seg, thr, V, L, nt, cnt, pred_c, gticp_c, w_c,
                      gt_out);
   hipLaunchKernelGGL(recon_register_kernel, dim3(B), dim3(PNT), 0, s, pred_c, gticp_c, w_c, tot, L, rts);

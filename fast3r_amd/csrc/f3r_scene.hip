@@ -54,17 +54,8 @@ __device__ __forceinline__ uint32_t conf_key(float c) {
 }
 __device__ __forceinline__ float conf_of_key(uint32_t k) { return fkey_inv(~k); }
 
-// the segment that owns tile `tile`: ts[s] <= tile < ts[s + 1] (every segment has at least one tile)
-__device__ __forceinline__ int find_seg(const int64_t* __restrict__ ts, int S, int64_t tile) {
-  int lo = 0, hi = S;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ts[mid] <= tile) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+// the segment that owns this workgroup's tile: ts[s] <= blockIdx.x < ts[s + 1] (every segment has at least one tile)
+__device__ __forceinline__ int find_seg(const int64_t* __restrict__ ts, int S) { return last_le(ts, 0, S, blockIdx.x); }
 
 // stats[seg * 4 + {0: smallest key = largest conf, 1: largest non-NaN key = smallest conf, 2: NaN count, 3: count of mask > 0}]
 __global__ void scene_stats_init_kernel(uint32_t* __restrict__ stats, int S) {
@@ -84,7 +75,7 @@ __global__ __launch_bounds__(SCENE_NT) void scene_hist_kernel(const SegRow* __re
                                                               uint32_t* __restrict__ stats, u32x4* __restrict__ recs) {
   __shared__ uint32_t cnt[256];
   __shared__ uint32_t red[4];
-  const int seg = find_seg(ts, S, blockIdx.x);
+  const int seg = find_seg(ts, S);
   const SegRow r = rows[seg];
   const int64_t t = blockIdx.x - ts[seg], nt = ts[seg + 1] - ts[seg];
   const int64_t base = t * SCENE_TILE, end = min(base + (int64_t)SCENE_TILE, r.len);
@@ -136,35 +127,6 @@ __global__ __launch_bounds__(SCENE_NT) void scene_hist_kernel(const SegRow* __re
   }
 }
 
-// exclusive scan, in place, of row blockIdx.x: uint32 a[start(row) .. start(row) + len(row)); totals[row] = its sum (if totals).
-// With ts: row = segment, start = 256 ts[row], len = 256 (ts[row + 1] - ts[row]); without: one row of `len0` from 0.
-__global__ __launch_bounds__(1024) void scene_scan_kernel(uint32_t* __restrict__ a, const int64_t* __restrict__ ts, int64_t len0,
-                                                          uint32_t* __restrict__ totals) {
-  __shared__ uint32_t sh[1024];
-  const int64_t start = ts ? ts[blockIdx.x] * 256 : 0;
-  const int64_t len = ts ? (ts[blockIdx.x + 1] - ts[blockIdx.x]) * 256 : len0;
-  uint32_t* r = a + start;
-  const int64_t per = (len + 1023) / 1024;
-  const int64_t b0 = min((int64_t)threadIdx.x * per, len), b1 = min(b0 + per, len);
-  uint32_t s = 0;
-  for (int64_t i = b0; i < b1; ++i) s += r[i];
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const uint32_t t = threadIdx.x >= (unsigned)off ? sh[threadIdx.x - off] : 0u;
-    __syncthreads();
-    sh[threadIdx.x] += t;
-    __syncthreads();
-  }
-  uint32_t run = sh[threadIdx.x] - s;
-  for (int64_t i = b0; i < b1; ++i) {
-    const uint32_t v = r[i];
-    r[i] = run;
-    run += v;
-  }
-  if (threadIdx.x == 1023 && totals) totals[blockIdx.x] = sh[1023];
-}
-
 template <bool FIRST, bool FINAL>
 __global__ __launch_bounds__(SCENE_NT) void scene_scatter_kernel(const SegRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                                  const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, int shift,
@@ -175,7 +137,7 @@ __global__ __launch_bounds__(SCENE_NT) void scene_scatter_kernel(const SegRow* _
   __shared__ uint32_t cnt[4][256];
   __shared__ uint32_t lbase[256], gbase[256], wsum[4];
   __shared__ uint8_t slut[FINAL ? 768 : 4];
-  const int seg = find_seg(ts, S, blockIdx.x);
+  const int seg = find_seg(ts, S);
   const SegRow r = rows[seg];
   const int64_t t = blockIdx.x - ts[seg], nt = ts[seg + 1] - ts[seg];
   const int64_t base = t * SCENE_TILE, end = min(base + (int64_t)SCENE_TILE, r.len);
@@ -205,13 +167,7 @@ __global__ __launch_bounds__(SCENE_NT) void scene_scatter_kernel(const SegRow* _
   for (int s = 0; s < SCENE_PER; ++s) {
     const bool ok = sub + s * 64 + lane < end;
     const uint32_t d = (k[s] >> shift) & 255u;
-    uint64_t peers = __ballot(ok);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t bal = __ballot(bit);
-      peers &= bit ? bal : ~bal;
-    }
+    const uint64_t peers = digit_peers(d, ok);
     const uint32_t below = (uint32_t)__popcll(peers & lanes_below());
     // cnt[w] belongs to this wave alone; a wave's LDS accesses execute in program order, so every lane has read before the leader writes
     const uint32_t c = cnt[w][d];
@@ -381,29 +337,29 @@ struct ColRow {  // 5 x 8 bytes
 
 __global__ __launch_bounds__(64) void collect_count_kernel(const ColRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                            uint32_t* __restrict__ counts) {
-  const int seg = find_seg(ts, S, blockIdx.x);
+  const int seg = find_seg(ts, S);
   const ColRow r = rows[seg];
   const int64_t base = (blockIdx.x - ts[seg]) * COL_TILE, end = min(base + (int64_t)COL_TILE, r.num);
   uint32_t c = 0;
   for (int64_t i = base + threadIdx.x; i < end; i += 64) c += r.mask ? (r.mask[i] > 0 ? 1u : 0u) : 1u;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+  c = wave_sum(c);
   if (threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(64) void collect_write_kernel(const ColRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                            const uint32_t* __restrict__ scan, float* __restrict__ out_pts,
                                                            uint8_t* __restrict__ out_col) {
-  const int seg = find_seg(ts, S, blockIdx.x);
+  const int seg = find_seg(ts, S);
   const ColRow r = rows[seg];
   const int64_t base = (blockIdx.x - ts[seg]) * COL_TILE, end = min(base + (int64_t)COL_TILE, r.num);
   int64_t run = scan[blockIdx.x];
   for (int64_t c0 = base; c0 < end; c0 += 64) {
     const int64_t i = c0 + threadIdx.x;
     const bool keep = i < end && (r.mask ? r.mask[i] > 0 : true);
-    const uint64_t bal = __ballot(keep);
+    uint64_t bal;
+    const uint32_t rank = compact_rank(keep, bal);
     if (keep) {
-      const int64_t q = run + __popcll(bal & lanes_below());
+      const int64_t q = run + rank;
       out_pts[q * 3 + 0] = r.pts[i * 3 + 0];
       out_pts[q * 3 + 1] = r.pts[i * 3 + 1];
       out_pts[q * 3 + 2] = r.pts[i * 3 + 2];
@@ -432,11 +388,6 @@ __global__ void ply_pack_kernel(const uint8_t* __restrict__ pts, const uint8_t* 
     }
   }
   out[wi] = word;
-}
-
-__device__ __forceinline__ uint64_t dkey(double f) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, f);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
 __global__ void color_range_init_kernel(unsigned long long* out) {
@@ -479,7 +430,6 @@ __global__ void color_to_u8_kernel(const T* __restrict__ c, int64_t n, int rule,
   out[i] = !(y > (T)0) ? (uint8_t)0 : (y >= (T)255 ? (uint8_t)255 : (uint8_t)(int)y);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 constexpr size_t EXT_HIST_BYTES = 3 * 4 * 2048 * sizeof(uint32_t);
 
 }  // namespace
@@ -510,19 +460,19 @@ extern "C" int f3r_scene_sort(const int64_t* table, int n_segments, int64_t n_ti
   hipLaunchKernelGGL(scene_stats_init_kernel, dim3((n_segments * 4 + 255) / 256), dim3(256), 0, s, stats, n_segments);
   // pass 0: conf -> (k0, v0)
   hipLaunchKernelGGL(scene_hist_kernel<true>, g, b, 0, s, rows, ts, n_segments, (const uint32_t*)nullptr, 0, hist, stats, recs);
-  hipLaunchKernelGGL(scene_scan_kernel, dim3(n_segments), dim3(1024), 0, s, hist, ts, (int64_t)0, (uint32_t*)nullptr);
+  hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(n_segments), dim3(SCAN_NT), 0, s, hist, ts, (int64_t)0, (uint32_t*)nullptr);
   hipLaunchKernelGGL((scene_scatter_kernel<true, false>), g, b, 0, s, rows, ts, n_segments, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0,
                      hist, k0, v0, o, stats, lut, recs);
   // passes 1, 2: (k0, v0) -> (k1, v1) -> (k0, v0)
   for (int pass = 1; pass <= 2; ++pass) {
     uint32_t *ki = pass == 1 ? k0 : k1, *vi = pass == 1 ? v0 : v1, *ko = pass == 1 ? k1 : k0, *vo = pass == 1 ? v1 : v0;
     hipLaunchKernelGGL(scene_hist_kernel<false>, g, b, 0, s, rows, ts, n_segments, ki, 8 * pass, hist, stats, recs);
-    hipLaunchKernelGGL(scene_scan_kernel, dim3(n_segments), dim3(1024), 0, s, hist, ts, (int64_t)0, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(n_segments), dim3(SCAN_NT), 0, s, hist, ts, (int64_t)0, (uint32_t*)nullptr);
     hipLaunchKernelGGL((scene_scatter_kernel<false, false>), g, b, 0, s, rows, ts, n_segments, ki, vi, 8 * pass, hist, ko, vo, o, stats, lut, recs);
   }
   // pass 3: (k0, v0) -> the order and every gathered output
   hipLaunchKernelGGL(scene_hist_kernel<false>, g, b, 0, s, rows, ts, n_segments, k0, 24, hist, stats, recs);
-  hipLaunchKernelGGL(scene_scan_kernel, dim3(n_segments), dim3(1024), 0, s, hist, ts, (int64_t)0, (uint32_t*)nullptr);
+  hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(n_segments), dim3(SCAN_NT), 0, s, hist, ts, (int64_t)0, (uint32_t*)nullptr);
   hipLaunchKernelGGL((scene_scatter_kernel<false, true>), g, b, 0, s, rows, ts, n_segments, k0, v0, 24, hist, (uint32_t*)nullptr,
                      (uint32_t*)nullptr, o, stats, lut, recs);
   return f3r_check_launch("f3r_scene_sort");
@@ -566,7 +516,7 @@ extern "C" int f3r_scene_collect_count(const int64_t* table, int n_segments, int
   hipStream_t s = (hipStream_t)stream;
   const int64_t* ts = table + (int64_t)n_segments * 5;
   hipLaunchKernelGGL(collect_count_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, (const ColRow*)table, ts, n_segments, scan);
-  hipLaunchKernelGGL(scene_scan_kernel, dim3(1), dim3(1024), 0, s, scan, (const int64_t*)nullptr, n_tiles, scan + n_tiles);
+  hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(1), dim3(SCAN_NT), 0, s, scan, (const int64_t*)nullptr, n_tiles, scan + n_tiles);
   return f3r_check_launch("f3r_scene_collect_count");
 }
 

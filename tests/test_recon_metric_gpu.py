@@ -79,6 +79,14 @@ def test_nn_exact_vs_brute_force(dev, name):
     check_nn(db, db)  # every point finds itself (or an exact duplicate with a smaller index)
 
 
+@pytest.mark.parametrize("m", [63, 64, 65, 2047, 2048, 2049])
+def test_nn_database_sizes_at_wave_and_tile_boundaries(dev, m):
+    """the sort of the index walks its 2048-element tiles in 64-element steps: one short of, at and one over each"""
+    q = torch.from_numpy(recon_ref.make_cloud("uniform", 200, 61)).to(dev)
+    db = torch.from_numpy(recon_ref.make_cloud("uniform", m, 62 + m)).to(dev)
+    check_nn(q, db)
+
+
 def test_nn_small_and_degenerate(dev):
     from fast3r_amd import nearest_neighbors
     one = torch.tensor([[1.0, 2.0, 3.0]], device=dev)
@@ -283,6 +291,54 @@ def test_evaluate_reconstruction_vs_reference(dev, golden, case):
             else:
                 worst["dist"] = max(worst["dist"], _rel(got[scene][k], v))
     print(f"{case}: worst rel dist {worst['dist']:.3e}, worst abs nc {worst['nc']:.3e}")
+    assert worst["dist"] <= EVAL_REL_DIST and worst["nc"] <= EVAL_ABS_NC, worst
+
+
+def _restated_eval(views, preds, i, p_icp, p_metric):
+    """evaluate_reconstruction of sample i on the CPU from the pieces of tests/recon_ref.py, global head: per view the two
+    torch.quantile thresholds, the masks, torch.cat over the views, the weighted registration, normals, accuracy / completion"""
+    x, y, w, gt_all = [], [], [], []
+    for view, pred in zip(views, preds):
+        conf, valid = pred["conf"][i].cpu(), view["valid_mask"][i].cpu()
+        keep = valid & (conf >= torch.quantile(conf.reshape(-1), p_metric / 100.0))
+        x.append(pred["pts3d_in_other_view"][i].cpu()[keep])
+        y.append(view["pts3d"][i].cpu()[keep])
+        w.append(conf[keep] >= torch.quantile(conf.reshape(-1), p_icp / 100.0))
+        gt_all.append(view["pts3d"][i].cpu()[valid])
+    x, y, w, gt_all = torch.cat(x), torch.cat(y), torch.cat(w), torch.cat(gt_all)
+    R, t, s = recon_ref.rigid_points_registration(x, y, weights=w, compute_scaling=True)
+    rec = (s * (x @ R.T) + t).numpy().astype(np.float64)
+    gt = gt_all.numpy().astype(np.float64)
+    n_rec, n_gt = recon_ref.estimate_normals(rec), recon_ref.estimate_normals(gt)
+    acc = recon_ref.accuracy(gt, rec, n_gt, n_rec)
+    comp = recon_ref.completion(gt, rec, n_gt, n_rec)
+    return {"accuracy": acc[0], "accuracy_median": acc[1], "completion": comp[0], "completion_median": comp[1],
+            "nc1": acc[2], "nc1_median": acc[3], "nc2": comp[2], "nc2_median": comp[3]}, len(x), len(gt)
+
+
+def test_evaluate_reconstruction_at_wave_and_tile_boundaries(dev):
+    """Two views of 130 and 3072 pixels with exactly 65 and 2049 valid ones: the first segment ends inside a 64-pixel step of the first
+    2048-pixel compaction tile, the kept GT points run one past a wave and one past a tile.  The bounds are those of
+    test_evaluate_reconstruction_vs_reference: the same fp32 registration and transform against the same CPU method."""
+    views, preds = recon_ref.make_eval_case(1, [(5, 26), (48, 64)], 71)
+    g = torch.Generator().manual_seed(72)
+    for view, n_valid in zip(views, (65, 2049)):
+        vm = torch.zeros(view["valid_mask"].numel(), dtype=torch.bool)
+        vm[torch.randperm(vm.numel(), generator=g)[:n_valid]] = True
+        view["valid_mask"] = vm.reshape(view["valid_mask"].shape)
+    want, n_pred, n_gt = _restated_eval(views, preds, 0, 50, 10)
+    assert n_gt == 65 + 2049 and 0 < n_pred < n_gt
+    views = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in d.items()} for d in views]
+    preds = [{k: v.to(dev) for k, v in d.items()} for d in preds]
+    got = _Lit().m.evaluate_reconstruction(views, preds, "edge", 50, 10, use_pts3d_from_local_head=False)["scene71/view0"]
+    assert got.keys() == want.keys()
+    worst = {"dist": 0.0, "nc": 0.0}
+    for k, v in want.items():
+        if k.startswith("nc"):
+            worst["nc"] = max(worst["nc"], abs(float(got[k]) - v))
+        else:
+            worst["dist"] = max(worst["dist"], _rel(got[k], v))
+    print(f"edge: worst rel dist {worst['dist']:.3e}, worst abs nc {worst['nc']:.3e}")
     assert worst["dist"] <= EVAL_REL_DIST and worst["nc"] <= EVAL_ABS_NC, worst
 
 

@@ -151,6 +151,56 @@ def test_size_case_against_torch_sort_and_gather(built_lib):
     assert torch.equal(p, torch.cat(want_p)) and torch.equal(c, torch.cat(want_c))
 
 
+def boundary_segments(lengths, seed):
+    """one (conf, pts, img, mask) per length, generated on the device; confidences quantised to 1/16 so that ties cross tiles, a mask on
+    every other segment"""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    r = lambda *s: torch.rand(*s, generator=g, device="cuda")  # noqa: E731
+    conf = [1.0 + torch.floor(r(L) * 64.0) / 16.0 for L in lengths]
+    pts = [r(L, 3) * 4 - 2 for L in lengths]
+    img = [r(3, L) * 2 - 1 for L in lengths]
+    mask = [(r(L) < 0.8).to(torch.int8) if s % 2 == 0 else None for s, L in enumerate(lengths)]
+    return conf, pts, img, mask
+
+
+def test_scene_sort_at_wave_and_tile_boundaries(built_lib):
+    """segments of one key, of a wave's 64 keys and a tile's 4096 keys, and one short and one over each, in one call"""
+    import fast3r_amd
+    from fast3r_amd import ops
+    lengths = [1, 63, 64, 65, 4095, 4096, 4097]
+    conf, pts, img, mask = boundary_segments(lengths, 91)
+    out = ops.scene_sort(conf, pts, img, mask, torch.from_numpy(fast3r_amd.scene.turbo_lut_u8()).cuda())
+    assert out["offsets"] == [sum(lengths[:s]) for s in range(len(lengths))] and out["order"].shape[0] == sum(lengths)
+    for s, L in enumerate(lengths):
+        sl = slice(out["offsets"][s], out["offsets"][s] + L)
+        sconf, order = torch.sort(conf[s], stable=True, descending=True)
+        assert torch.equal(out["order"][sl].long(), order), L
+        assert torch.equal(out["conf"][sl], sconf), L
+        assert torch.equal(out["pts"][sl], torch.gather(pts[s], 0, order[:, None].expand(-1, 3))), L
+        m = mask[s] if mask[s] is not None else torch.ones(L, dtype=torch.int8, device="cuda")  # no mask: every pixel counts as kept
+        assert torch.equal(out["mask"][sl], torch.gather(m, 0, order)), L
+
+
+def test_scene_collect_at_wave_and_tile_boundaries(built_lib):
+    """prefixes of one entry, of a wave's 64 and a collect tile's 1024 entries, and one short and one over each, over sorted segments"""
+    import fast3r_amd
+    from fast3r_amd import ops
+    nums = [1, 63, 64, 65, 1023, 1024, 1025]
+    conf, pts, img, mask = boundary_segments([1100] * len(nums), 92)
+    out = ops.scene_sort(conf, pts, img, mask, torch.from_numpy(fast3r_amd.scene.turbo_lut_u8()).cuda())
+    seg = [slice(o, o + 1100) for o in out["offsets"]]
+    spts = [out["pts"][sl].contiguous() for sl in seg]
+    srgb = [out["rgb"][sl].contiguous() for sl in seg]
+    smask = [out["mask"][sl].contiguous() if mask[s] is not None else None for s, sl in enumerate(seg)]
+    p, c = ops.scene_collect(spts, srgb, smask, nums, [None] * len(nums))
+    want_p, want_c = [], []
+    for s, n in enumerate(nums):
+        k = smask[s][:n] > 0 if smask[s] is not None else torch.ones(n, dtype=torch.bool, device="cuda")
+        want_p.append(spts[s][:n][k])
+        want_c.append(srgb[s][:n][k])
+    assert torch.equal(p, torch.cat(want_p)) and torch.equal(c, torch.cat(want_c))
+
+
 def test_two_runs_give_the_same_bits(built_lib):
     import fast3r_amd
     scene = C.build("lengths")
