@@ -151,6 +151,9 @@ SYMBOLS = {
     "f3r_ply_pack": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_vp, _c_vp]),
     "f3r_color_range": (ctypes.c_int, [_c_vp, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
     "f3r_color_to_u8": (ctypes.c_int, [_c_vp, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp]),
+    "f3r_sky_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "f3r_sky_detect": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp,
+                                      ctypes.c_size_t, _c_vp, _c_vp, _c_vp]),
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")
@@ -170,6 +173,10 @@ LOSS_ABI_VERSION = 380  # f3r_mv_conf_loss (checked in fast3r_amd/ops.py too)
 SCENE_ABI_VERSION = 390  # f3r_scene_*, f3r_ply_pack, f3r_color_* (checked in fast3r_amd/ops.py too)
 SCENE_TILE = 4096  # F3R_SCENE_TILE: keys per tile of the segmented sort; COLLECT_TILE: entries per tile of collect_points
 COLLECT_TILE = 1024
+SKY_ABI_VERSION = 400  # f3r_sky_detect (checked in fast3r_amd/ops.py too)
+F3R_SKY_CLASSIFY, F3R_SKY_MORPH, F3R_SKY_LABEL = 1, 2, 4
+F3R_SKY_EMPTY, F3R_SKY_NO_TOP, F3R_SKY_TOP = 0, 1, 2
+SKY_PIX_TILE, SKY_WORD_TILE = 16, 256  # F3R_SKY_PIX_TILE, F3R_SKY_WORD_TILE: words per workgroup of the two kinds of sky kernel
 
 
 def lib():

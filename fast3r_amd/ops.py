@@ -1103,3 +1103,69 @@ def color_to_u8(colors, rule, lo=0.0, hi=1.0):
         check(_scene_lib().f3r_color_to_u8(ptr(colors), colors.numel(), _real_id(colors.dtype), int(rule), float(lo), float(hi), ptr(out),
                                            stream_ptr()), "f3r_color_to_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------- sky detection
+def _sky_lib():
+    l = _lib.lib()
+    if l.f3r_version() < _lib.SKY_ABI_VERSION:
+        raise _lib.F3RError(f"{_lib.LIB_PATH} is version {l.f3r_version()}; sky detection needs >= {_lib.SKY_ABI_VERSION}: "
+                            "rebuild it (fast3r_amd/csrc/build.sh)")
+    return l
+
+
+def sky_row_words(W):
+    """64-bit words per row of the bit-packed bitmap (include/f3r.h f3r_sky_detect)"""
+    return (W + 63) // 64
+
+
+def sky_detect(src, shapes, stages, *, want_not_sky=True, want_roots=False, want_bits=False):
+    """f3r_sky_detect (include/f3r.h) on a list of views in one call.  src[i]: with F3R_SKY_CLASSIFY in `stages` the (3, H * W) fp32
+    planes of view i, otherwise its (H, W) int8 bitmap, on the GPU; shapes[i] = (H, W).
+    -> dict(not_sky: list of (H, W) int8, roots: list of (H, W) int32, stats: (V, 5) int32 on the device, bits: uint64 words as int64
+    (V concatenated), word_offsets) with the entries that were asked for and that the stages produce."""
+    V = len(src)
+    if V < 1 or len(shapes) != V:
+        raise ValueError(f"sky_detect: need one shape per view and at least one view (got {V} views, {len(shapes)} shapes)")
+    classify, label = bool(stages & _lib.F3R_SKY_CLASSIFY), bool(stages & _lib.F3R_SKY_LABEL)
+    dev = src[0].device
+    keep, rows, hw = [], [], []
+    word_off = pix_off = width_off = 0
+    pix_starts, word_starts = [0], [0]
+    not_sky, roots = [], []
+    for i, (t, (H, W)) in enumerate(zip(src, shapes)):
+        H, W = int(H), int(W)
+        if H < 1 or W < 1 or H * W >= 2 ** 31:
+            raise ValueError(f"sky_detect: view {i} is {H} x {W}; need H, W >= 1 and H * W < 2^31")
+        require_gpu(t, f"view {i}")
+        want = ((3, H * W), torch.float32) if classify else ((H, W), torch.int8)
+        if tuple(t.shape) != want[0] or t.dtype != want[1] or t.device != dev:
+            raise ValueError(f"sky_detect: view {i} must be {want[0]} {want[1]} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        t = t.contiguous()
+        keep.append(t)
+        ns = torch.empty((H, W), dtype=torch.int8, device=dev) if (label and want_not_sky) else None
+        rt = torch.empty((H, W), dtype=torch.int32, device=dev) if (label and want_roots) else None
+        not_sky.append(ns)
+        roots.append(rt)
+        n_words = H * sky_row_words(W)
+        # mask.size * 0.01 and int(height * 0.4) are Python doubles in the reference; an integer size exceeds the first iff it exceeds its floor
+        rows.append([t.data_ptr(), 0 if ns is None else ns.data_ptr(), 0 if rt is None else rt.data_ptr(), H, W, word_off, pix_off, width_off,
+                     int(math.floor(H * W * 0.01)), int(H * 0.4)])
+        hw += [H, W]
+        word_off += n_words
+        pix_off += H * W
+        width_off += W
+        pix_starts.append(pix_starts[-1] + (n_words + _lib.SKY_PIX_TILE - 1) // _lib.SKY_PIX_TILE)
+        word_starts.append(word_starts[-1] + (n_words + _lib.SKY_WORD_TILE - 1) // _lib.SKY_WORD_TILE)
+    table = torch.tensor([x for r in rows for x in r] + pix_starts + word_starts, dtype=torch.int64).to(dev)   # one small upload
+    host_hw = (ctypes.c_int64 * len(hw))(*hw)
+    l = _sky_lib()
+    ws_bytes = l.f3r_sky_workspace_bytes(word_off, pix_off, width_off, stages)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    stats = torch.empty((V, 5), dtype=torch.int32, device=dev) if label else None
+    bits = torch.empty(word_off, dtype=torch.int64, device=dev) if (want_bits or not label) else None
+    with torch.cuda.device(dev):
+        check(l.f3r_sky_detect(ptr(table), host_hw, V, pix_starts[-1], word_starts[-1], word_off, pix_off, width_off, stages, ptr(ws), ws_bytes,
+                               ptr(stats), ptr(bits), stream_ptr()), "f3r_sky_detect")
+    del keep, ws, table  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    return {"not_sky": not_sky, "roots": roots, "stats": stats, "bits": bits, "word_offsets": [r[5] for r in rows]}

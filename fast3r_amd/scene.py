@@ -11,9 +11,9 @@ single-threaded numpy; here every per-point step is a HIP kernel (fast3r_amd/csr
 
 Deviations, all stated in DESIGN.md section 7: colours are stored as uint8 (for RGB the reference's float arrays are these / 255.0 and
 the round trip through `safe_color_conversion` is the identity; for the other two colourings the uint8 values are exactly what reaches
-the PLY); image values outside [-1, 1] saturate where the reference's uint8 cast wraps; sky *detection* (`detect_sky_mask`: OpenCV
-HSV thresholds, morphology, connected components) is not built -- the mask is an input (`not_sky`), like `valid_mask` elsewhere;
-`sample` selects the batch row where the reference's `squeeze()` only works at B = 1.
+the PLY); image values outside [-1, 1] saturate where the reference's uint8 cast wraps; the sky mask is an input (`not_sky`), like
+`valid_mask` elsewhere, or `not_sky="detect"` computes it as the reference does (`detect_sky_mask`: fast3r_amd/sky.py) -- the default,
+None, still means no sky anywhere; `sample` selects the batch row where the reference's `squeeze()` only works at B = 1.
 """
 import colorsys
 import os
@@ -200,7 +200,11 @@ def _check_inputs(preds, views, sample, not_sky):
     B = preds[0]["conf"].shape[0]
     if not 0 <= sample < B:
         raise ValueError(f"assemble_scene: sample = {sample} outside [0, {B})")
-    if not_sky is not None:
+    if isinstance(not_sky, str):
+        if not_sky != "detect":
+            raise ValueError(f"assemble_scene: not_sky = {not_sky!r}; accepted values are None (no sky anywhere), 'detect' (detect_sky_masks "
+                             "on the views' images) or a list of per-view (H, W) masks")
+    elif not_sky is not None:
         if len(not_sky) != len(preds):
             raise ValueError(f"assemble_scene: not_sky has {len(not_sky)} masks for {len(preds)} views")
         for i, m in enumerate(not_sky):
@@ -215,8 +219,9 @@ def _check_inputs(preds, views, sample, not_sky):
 def assemble_scene(output_or_preds, views=None, *, sample=0, not_sky=None, global_conf_thr_value_to_drop_view=1.5, niter_PnP=100, poses=True):
     """Everything `start_visualization` prepares before it draws (viser_visualizer.py:279-282, :343-427).  Takes what `inference()` returns
     ({'preds', 'views'}, host tensors: uploaded here) or (preds, views) with device tensors; views may differ in H x W; `sample` selects
-    the batch row.  `not_sky`: optional list of per-view (H, W) bool / int8 masks, nonzero = keep (what `detect_sky_mask` returns in the
-    reference; detection itself is not built).  Results stay on the device."""
+    the batch row.  `not_sky`: None (no sky anywhere), a list of per-view (H, W) bool / int8 masks, nonzero = keep (what `detect_sky_mask`
+    returns), or "detect": run fast3r_amd.sky's batched detection on the images already on the device and proceed as if given those masks.
+    Results stay on the device."""
     if isinstance(output_or_preds, dict):
         preds = output_or_preds["preds"]
         views = output_or_preds["views"] if views is None else views
@@ -244,6 +249,7 @@ def assemble_scene(output_or_preds, views=None, *, sample=0, not_sky=None, globa
             m = (m != 0).to(torch.int8)
         return m.reshape(-1)
 
+    detect = isinstance(not_sky, str)
     conf, pts, img, mask, shapes = [], [], [], [], []
     for head in ("global", "local"):
         for i, (pred, view) in enumerate(zip(preds, views)):
@@ -253,10 +259,13 @@ def assemble_scene(output_or_preds, views=None, *, sample=0, not_sky=None, globa
                 if tuple(view["img"].shape[1:]) != (3, H, W):
                     raise ValueError(f"assemble_scene: views[{i}]['img'] is {tuple(view['img'].shape)}; expected (B, 3, {H}, {W})")
                 img.append(flat(view["img"], (3, H * W)))   # the (3, H, W) planes as stored: nothing is permuted
-                mask.append(None if not_sky is None else mask_of(not_sky[i]))
+                mask.append(None if (not_sky is None or detect) else mask_of(not_sky[i]))
                 conf.append(flat(pred["conf"], (H * W,)))
                 pts.append(flat(pred["pts3d_in_other_view"], (H * W, 3)))
             else:
+                if detect and i == 0:   # every view's planes are on the device now: one batched detection, no host synchronisation
+                    from .sky import detect_sky_planes
+                    mask[:V] = [m.reshape(-1) for m in detect_sky_planes(img[:V], shapes)[0]]
                 img.append(img[i])
                 mask.append(mask[i])
                 conf.append(flat(pred["conf_local"], (H * W,)))

@@ -48,7 +48,7 @@ typedef enum { F3R_LOSS_DIS = 0, F3R_LOSS_LOG1P = 1 } f3r_loss_dis_mode; /* avg_
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 400 = 0.4.0 (+ f3r_sky_detect, f3r_sky_workspace_bytes); 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -581,6 +581,46 @@ int f3r_scene_collect_write(const int64_t* table, int n_segments, int64_t n_tile
 int f3r_ply_pack(const float* pts, const uint8_t* rgb, int64_t n, void* out, f3r_stream_t stream);
 int f3r_color_range(const void* colors, int64_t n, int dtype, uint64_t* out, f3r_stream_t stream);
 int f3r_color_to_u8(const void* colors, int64_t n, int dtype, int rule, double lo, double hi, uint8_t* out, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sky detection (ABI 400): the reference's detect_sky_mask (fast3r/viz/viser_visualizer.py:24-72) for every view of a scene in one call.
+ * Python: fast3r_amd/sky.py.  Per view, in the reference's order:
+ *   1. u = trunc((img + 1) * 127.5) per channel (an fp32 add and an fp32 multiply; saturated outside [0, 255], NaN -> 0);
+ *   2. OpenCV's 8-bit BGR2HSV (H in [0, 180), 12-bit fixed-point tables, rounding to nearest even);
+ *   3. sky-coloured = H, S, V inside one of [105, 50, 140]-[135, 255, 255], [95, 5, 150]-[145, 100, 255], [0, 0, 235]-[180, 10, 255]
+ *      (inclusive), or in rows < int(H * 0.4): S < 50 and V > 150;
+ *   4. dilate 7 x 7, then open 7 x 7 (erode, dilate), pixels outside the image ignored;
+ *   5. 4-connected components; none: nothing changes (F3R_SKY_EMPTY); none touches row 0: the mask stays as it is (F3R_SKY_NO_TOP);
+ *      otherwise (F3R_SKY_TOP) sky = the components that touch row 0 and have more than thr pixels;
+ *   6. not_sky = 1 where not sky, else 0 (int8).
+ * `stages` selects what runs: F3R_SKY_CLASSIFY (steps 1-3 from the image; without it `src` is an (H, W) int8 bitmap, nonzero = set),
+ *   F3R_SKY_MORPH (step 4), F3R_SKY_LABEL (steps 5-6).  bits_out (optional with F3R_SKY_LABEL, else required) receives the bitmap after
+ *   the last of the first two stages that ran: total_words uint64, view i from its word_off, row y of a view = ceil(W / 64) words, pixel
+ *   x = bit x % 64 of word x / 64, bits beyond W zero.
+ * `table` is a DEVICE int64 array: n_views rows of 10 { src pointer (fp32 planes (3, H * W) as stored, or the int8 bitmap), not_sky
+ *   pointer ((H, W) int8 out; 0 = none), roots pointer ((H, W) int32 out: the smallest pixel index y * W + x of the pixel's component, -1
+ *   for background; 0 = none), H, W, word_off, pix_off, width_off (the running sums of H * ceil(W / 64), H * W and W), thr (floor(H * W *
+ *   0.01) with the product formed in double), upper (int(H * 0.4)) }, then n_views + 1 tile starts of F3R_SKY_PIX_TILE words and n_views +
+ *   1 tile starts of F3R_SKY_WORD_TILE words (running sums of ceil(H * ceil(W / 64) / tile)).  host_hw: HOST int64 [n_views][2] = the same
+ *   H, W; the totals are checked against it before anything is launched.
+ * stats (device int32 [n_views][5], written with F3R_SKY_LABEL) = { set pixels entering step 5, components, components touching row 0,
+ *   components kept as sky, branch }.  Integer atomics only, and a component's label is its smallest pixel index: two runs give the
+ *   same bits.  Inputs are not written to.
+ * F3R_ERR_ARG before any launch: a null table, host_hw or workspace; n_views < 1; H or W < 1 or H * W >= 2^31; totals that do not match
+ *   host_hw; an unknown stage bit; stats null with F3R_SKY_LABEL; bits_out null without it; a workspace that is too small.
+ */
+#define F3R_SKY_CLASSIFY 1
+#define F3R_SKY_MORPH 2
+#define F3R_SKY_LABEL 4
+#define F3R_SKY_EMPTY 0
+#define F3R_SKY_NO_TOP 1
+#define F3R_SKY_TOP 2
+#define F3R_SKY_PIX_TILE 16
+#define F3R_SKY_WORD_TILE 256
+size_t f3r_sky_workspace_bytes(int64_t total_words, int64_t total_pixels, int64_t total_width, int stages);
+int f3r_sky_detect(const int64_t* table, const int64_t* host_hw, int n_views, int64_t n_pix_tiles, int64_t n_word_tiles, int64_t total_words,
+                   int64_t total_pixels, int64_t total_width, int stages, void* workspace, size_t workspace_bytes, int32_t* stats,
+                   uint64_t* bits_out, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).

@@ -1,6 +1,6 @@
 """Kernel micro-benchmarks on the GPU box (interleaved rounds, random data, HIP events on the launch stream): the attention kernels
 f3r_attn_fwd can take (--what attnproduct / attnsel / attnhd) and the model's GEMM / conv shapes per f3r_gemm_args.kernel_sel, with the vendor
-library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement; --what scene: scene assembly and PLY export likewise.  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
+library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement; --what scene: scene assembly and PLY export likewise; --what sky: sky detection alone, inside assemble_scene and next to the CPU (--what skydetect: its kernels alone, for a profiler run).  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
 F3R_LAB_LIB=tools/lab/libf3r_hip_lab.so.)"""
 import argparse
 import math
@@ -591,6 +591,139 @@ def bench_scene(sizes=(100, 320), H=512, W=512, out_path="profiles/r09_scene_ben
         f.write(line + "\n")
 
 
+def bench_sky(sizes=(100, 320), H=512, W=512, out_path="profiles/r10_sky_bench.jsonl", detect_only=False):
+    """Sky detection (fast3r_amd/sky.py, f3r_sky.hip) at N views of H x W generated on the device: a procedural outdoor set (blue sky with
+    noise above a horizon that differs per view, ground colours below, a lake) and a uniform-noise set, the labelling's bad case.  Per set:
+    * `detect_sky_planes` alone (what `assemble_scene(not_sky="detect")` calls: no read-back), wall clock and stream time, with the bytes
+      the stage must move whatever the method (12 B read + 1 B written per pixel) over that time;
+    * `assemble_scene(not_sky="detect")` against `assemble_scene(not_sky=None)`, alternating call by call, poses=False;
+    * two CPU times on this machine, 8 views scaled to N: tests/sky_ref.py (numpy boolean box filters + scipy's labelling), and the
+      reference's own steps through the stand-in tests/cv2_sky_stub.py (its uint8 cvtColor / inRange / dilate / morphologyEx, then
+      sky_ref's labelling and rule);
+    * at the first size the labelling alone (`F3R_SKY_LABEL` on a caller's bitmaps) on N one-pixel spirals, its longest parent chains,
+      next to N bitmaps of 50 % noise.
+    detect_only: a few detection calls at the first size, for a profiler run of its own.  One JSON line, appended to profiles/."""
+    import os
+    import statistics
+    import time
+    import fast3r_amd
+    from fast3r_amd import sky as K
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import numpy as np
+    import cv2_sky_stub as CV
+    import sky_cases as C
+    import sky_ref as R
+
+    def once_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def cpu_through_stand_in(img):
+        """the reference's steps with the stand-in's uint8 calls in place of cv2's, then sky_ref's labelling and rule"""
+        hsv = CV.cvtColor(CV.cvtColor(R.to_u8(img), CV.COLOR_RGB2BGR), CV.COLOR_BGR2HSV)
+        mask = (CV.inRange(hsv, [105, 50, 140], [135, 255, 255]) | CV.inRange(hsv, [95, 5, 150], [145, 100, 255])
+                | CV.inRange(hsv, [0, 0, 235], [180, 10, 255]))
+        upper = int(img.shape[0] * 0.4)
+        mask[:upper] |= ((hsv[:upper, :, 1] < 50) & (hsv[:upper, :, 2] > 150)).astype(np.uint8)
+        k = np.ones((7, 7), np.uint8)
+        mask = CV.morphologyEx(CV.dilate(mask, k, iterations=1), CV.MORPH_OPEN, k)
+        sky, _ = R.select(mask != 0)
+        return (~sky).astype(np.int8)
+
+    def stats(ts):
+        return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "n": len(ts)}
+
+    g = torch.Generator(device=DEV).manual_seed(0)
+    rnd = lambda *s: torch.rand(*s, generator=g, device=DEV)  # noqa: E731
+
+    def outdoor(v):
+        u = torch.empty(3, H, W, device=DEV)
+        horizon = int(H * (0.3 + 0.3 * ((v * 37) % 11) / 10))
+        sky_c = torch.tensor([100.0, 150.0, 230.0], device=DEV)[:, None, None]
+        ground = torch.tensor([[70.0, 110.0, 50.0], [110.0, 90.0, 60.0]], device=DEV)[v % 2][:, None, None]
+        u[:, :horizon] = sky_c + (rnd(3, horizon, W) * 12 - 6)
+        u[:, horizon:] = ground + (rnd(3, H - horizon, W) * 60 - 30)
+        y0 = min(H - 40, horizon + 60)
+        u[:, y0:y0 + 30, W // 5:W // 2] = sky_c + (rnd(3, 30, W // 2 - W // 5) * 12 - 6)
+        return ((u.clamp_(0, 255).floor_() / 255 - 0.5) / 0.5)[None]
+
+    rec = {"what": "sky", "device": torch.cuda.get_device_name(0), "B": 1, "HW": [H, W], "sizes": {}}
+    for n in sizes:
+        row = {}
+        for kind in ("outdoor", "noise"):
+            views = [{"img": outdoor(v) if kind == "outdoor" else rnd(1, 3, H, W) * 2 - 1} for v in range(n)]
+            planes = [v["img"][0].reshape(3, H * W) for v in views]
+            shapes = [(H, W)] * n
+            detect = lambda: K.detect_sky_planes(planes, shapes)  # noqa: E731
+            once_ms(detect)
+            if detect_only:
+                for _ in range(3):
+                    detect()
+                torch.cuda.synchronize()
+                continue
+            preds = [{"pts3d_in_other_view": rnd(1, H, W, 3) * 4 - 2, "pts3d_local_aligned_to_global": rnd(1, H, W, 3) * 4 - 2,
+                      "conf": 1.0 + 20.0 * rnd(1, H, W) ** 2, "conf_local": 1.0 + 20.0 * rnd(1, H, W) ** 2} for _ in range(n)]
+            with_detect = lambda: fast3r_amd.assemble_scene(preds, views, not_sky="detect", poses=False)  # noqa: E731
+            without = lambda: fast3r_amd.assemble_scene(preds, views, not_sky=None, poses=False)  # noqa: E731
+            once_ms(with_detect)
+            once_ms(without)
+            td, ta, tn = [], [], []
+            for _ in range(5):   # alternating
+                td.append(once_ms(detect)[0])
+                ta.append(once_ms(with_detect)[0])
+                tn.append(once_ms(without)[0])
+            stream_ms, stream_best = time_ms(detect, rounds=5, inner=1)
+            st = K.stats_dicts(detect()[1])
+            sc = with_detect()
+            # the numpy restatement on this machine's CPU: 8 views, scaled to n
+            host = [views[i]["img"][0].permute(1, 2, 0).contiguous().cpu().numpy() for i in range(8)]
+            t0 = time.perf_counter()
+            want = [R.detect_sky_mask(img)[0] for img in host]
+            cpu8_ms = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            want_cv = [cpu_through_stand_in(img) for img in host]
+            cpu8_cv_ms = (time.perf_counter() - t0) * 1e3
+            masks = detect()[0]
+            assert all(np.array_equal(masks[i].cpu().numpy(), want[i]) and np.array_equal(want[i], want_cv[i]) for i in range(8))
+            must = 13 * n * H * W
+            d_med, a_med, n_med = statistics.median(td), statistics.median(ta), statistics.median(tn)
+            row[kind] = {
+                "pixels": n * H * W, "detect_sky_planes": stats(td), "detect_stream_ms": round(stream_ms, 3), "detect_stream_best_ms": round(stream_best, 3),
+                "bytes_must_move_per_pixel": 13, "detect_TB_per_s_of_must_move_bytes": round(must / (stream_ms * 1e-3) / 1e12, 3),
+                "assemble_scene_detect": stats(ta), "assemble_scene_none": stats(tn), "detect_over_none": round(a_med / n_med, 3),
+                "added_ms": round(a_med - n_med, 3), "is_outdoor": bool(sc.is_outdoor),
+                "mean_components": round(sum(s["components"] for s in st) / n, 1), "mean_sky_fraction": round(sum(s["sky_pixels"] for s in st) / (n * H * W), 3),
+                "branches": {b: sum(s["branch"] == b for s in st) for b in ("empty", "no_top", "top")},
+                "cpu_numpy_restatement_8_views_ms": round(cpu8_ms, 1), "cpu_numpy_restatement_scaled_to_n_ms": round(cpu8_ms * n / 8, 1),
+                "cpu_scaled_over_detect": round(cpu8_ms * n / 8 / d_med, 1),
+                "cpu_stand_in_8_views_ms": round(cpu8_cv_ms, 1), "cpu_stand_in_scaled_to_n_ms": round(cpu8_cv_ms * n / 8, 1),
+                "first_8_masks_equal_both_cpu_paths": True}
+            del preds, views, planes, sc, masks
+            torch.cuda.empty_cache()
+        if detect_only:
+            return
+        if n == sizes[0]:   # the labelling alone: its longest chains (one-pixel spirals) next to 50 % noise
+            lab = {}
+            for kind, bm in (("spiral", torch.from_numpy(C.spiral(H, W).astype(np.int8)).to(DEV)), ("noise50", None)):
+                src = [bm.clone() if bm is not None else (rnd(H, W) < 0.5).to(torch.int8) for _ in range(n)]
+                label = lambda: ops.sky_detect(src, [(H, W)] * n, _lib.F3R_SKY_LABEL, want_not_sky=True, want_roots=False)  # noqa: E731
+                once_ms(label)
+                ms, best = time_ms(label, rounds=5, inner=1)
+                lab[kind] = {"label_stream_ms": round(ms, 3), "label_stream_best_ms": round(best, 3),
+                             "set_pixels_per_view": int(src[0].sum().item()), "components_view0": int(label()["stats"][0, 1].item())}
+                del src
+            row["labelling_alone"] = lab
+        rec["sizes"][str(n)] = row
+    line = json.dumps(rec)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+
+
 def bench_posemetric(sizes=(320, 1500), H=512, W=512, out_path="profiles/r07_pose_metric_bench.jsonl"):
     """camera_pose_metrics (RRA / RTA / mAA from f3r_pose_pair_metrics) at B = 1 next to estimate_poses at the same view count in the same
     run: the metric stage is O(pairs) trigonometry on a few hundred kilobytes of poses and must stay below 5 % of the PnP stage.  Wall
@@ -877,6 +1010,12 @@ if __name__ == "__main__":
         bench_loss()
     if args.what == "scene":  # scene assembly and PLY export next to a torch-eager restatement and the numpy restatement on the CPU
         bench_scene()
+        sys.exit(0)
+    if args.what == "sky":  # sky detection alone and inside assemble_scene, next to the numpy restatement on the CPU
+        bench_sky()
+        sys.exit(0)
+    if args.what == "skydetect":  # the detection kernels alone at N = 100 (both sets), for a profiler run of its own
+        bench_sky(sizes=(100,), detect_only=True)
         sys.exit(0)
     if args.what == "scenesort":  # f3r_scene_sort alone at N = 100, for a profiler run of its own
         bench_scene(sizes=(100,), sort_only=True)
