@@ -423,7 +423,8 @@ extern "C" int f3r_gemm(const f3r_gemm_args* args, f3r_stream_t stream) {
   if (a.split == F3R_SPLIT_X3F8 || a.fin_w) {  // one kernel family takes these (f3r_gemm256_f8.hip): no second path, no fallback
     if (!f3r_gemm256_eligible(a)) {
       f3r_set_error("f3r_gemm: split X3F8 / fin_w but the launch is not eligible for the 256-tile kernel (conv_C %% 64 (X3F8: 128) == 0, "
-                    "N %% 128 == 0 (fin_w: N == 128), operand below 4 GiB)");
+                    "N %% 128 == 0 (fin_w: N == 128), operand below 4 GiB, at most %d K-tiles: 9 conv_C / 64 per plane product, of which X3 has three and "
+                    "X3F8 the equivalent of two)", f3r_gemm256_max_conv_k_tiles());
       return F3R_ERR_UNSUPPORTED;
     }
     return f3r_gemm256_launch(a, s, 1);

@@ -6,7 +6,8 @@ int f3r_gemm256_run_bf16(const f3r_gemm_args& a, hipStream_t stream, int stagger
 int f3r_gemm256_run_conv_f8_fin(const f3r_gemm_args& a, hipStream_t stream);         // f3r_gemm256_f8.hip
 
 // Whether the 256-tile kernel takes this (already validated) problem: everything its LDS-DMA staging cannot express -- K tails, ragged
-// channel counts, strided or pre-activated conv operands, small or narrow outputs -- stays on the 128-tile kernel.
+// channel counts, strided or pre-activated conv operands, small or narrow outputs, convolutions with more K-tiles than the K-tile table
+// in LDS has records (TileCfg::TAB_ENTRIES; the K-tile count is conv_k_tiles) -- stays on the 128-tile kernel.
 bool f3r_gemm256_eligible(const f3r_gemm_args& a) {
   if (a.N % 128 != 0) return false;
   if (a.epi == F3R_EPI_QKV) {  // a 256-wide tile must lie in ONE of the q / k / v parts
@@ -23,6 +24,8 @@ bool f3r_gemm256_eligible(const f3r_gemm_args& a) {
     // 32-bit byte offsets into the NHWC operand (B * H * W pixels; stride 2 reads four times the output's pixel count)
     if (a.M / ((int64_t)a.conv_OH * a.conv_OW) * a.conv_H * a.conv_W * a.conv_C * 2 >= (1ll << 32)) return false;
     if (a.split == F3R_SPLIT_X3F8 && (a.conv_C % 128 != 0 || a.dtype != F3R_F16)) return false;
+    // one table record per K-tile in LDS (gemm256_body): 9 C / 64 per plane product -- with 512 records C <= 3584 on one plane, 1792 (w2, x3f8), 1152 (x3)
+    if (conv_k_tiles(a) > TileCfg<1>::TAB_ENTRIES) return false;
   }
   if (a.split == F3R_SPLIT_X3F8 && a.a_mode != F3R_A_CONV3X3) return false;
   if (a.fin_w && (a.a_mode != F3R_A_CONV3X3 || a.N != 128 || a.epi != F3R_EPI_GENERIC)) return false;
@@ -35,6 +38,8 @@ bool f3r_gemm256_eligible(const f3r_gemm_args& a) {
   if (a.a_mode == F3R_A_CONV3X3 ? (add == F3R_ADD_RES_F32 || add == F3R_ADD_ROWADD) : add == F3R_ADD_RES_LP) return false;
   return true;
 }
+
+int f3r_gemm256_max_conv_k_tiles() { return TileCfg<1>::TAB_ENTRIES; }
 
 // Whether the 256-tile kernel (in the tile form tile_halves picks) is also the FASTER choice: one workgroup per CU, so with few tiles or
 // an unlucky tail round the 128-tile kernel (2 workgroups per CU, 4x the tiles) fills the chip better -- see tile_score.

@@ -48,6 +48,17 @@ template <int NH> struct TileCfg {
   static constexpr int LDS_BYTES = NBUF * BUF * 2 + TAB_ENTRIES * 16;   // 139264 / 155648
 };
 
+static_assert(TileCfg<1>::TAB_ENTRIES == TileCfg<2>::TAB_ENTRIES, "conv_k_tiles is checked against one table size");
+
+// K-tiles of a 3x3 convolution = records gemm256_body writes into the table: the expression it calls nk (F8: nk1 fp16 tiles + 2 * nk8 fp8 tiles)
+inline int conv_k_tiles(const f3r_gemm_args& a) {
+  const int nseg = a.split == F3R_SPLIT_NONE ? 1 : (a.split == F3R_SPLIT_W2 ? 2 : 3);
+  const int Kpad1 = a.split == F3R_SPLIT_NONE ? a.Kpad : a.Kpad / 2;
+  const int nk1 = Kpad1 / BK;
+  const int nk8 = nk1 / 2;
+  return a.split == F3R_SPLIT_X3F8 ? nk1 + 2 * nk8 : nseg * nk1;
+}
+
 inline int f3r_num_cus() {  // CUs of the CURRENT device, rounded down to a multiple of 8 (XCDs); cached per device index
   constexpr int MAXD = 64;
   static std::atomic<int> cache[MAXD];  // zero-initialised; a racing first call computes the same value twice
@@ -589,7 +600,10 @@ __device__ __forceinline__ void gemm256_body(const f3r_gemm_args& p, uint16_t* s
   dry = !first;
   opening_loads();
   dry = false;
-  gemm_acc_init_additive<T, Frag, ADDSRC, SWAP>(p, acc, m_base, n_base, lane);
+  // X3 convolutions take the bias behind the K loop: three plane products of up to 9 * 1152 terms stay fp32-class only if they are summed from zero
+  // (gemm_acc_add_bias); wave-uniform
+  const bool bias_last = A_MODE == F3R_A_CONV3X3 && !F8 && !SWAP && p.split == F3R_SPLIT_X3;
+  gemm_acc_init_additive<T, Frag, ADDSRC, SWAP>(p, acc, m_base, n_base, lane, !bias_last);
   if (first && MERGED) {
     if constexpr (NH == 2) F3R_VMCNT(8);  // A0, W0, A1 of tile 0 have landed (younger: W1 of tile 0, A0, W0, A1 of tile 1)
     else F3R_VMCNT(6);                    // tile 0 has landed (younger: tile 1)
@@ -646,9 +660,12 @@ __device__ __forceinline__ void gemm256_body(const f3r_gemm_args& p, uint16_t* s
   }
   // Past the last tile the cursors stay clamped, so the tail re-loads the last tile into half tiles nobody reads any more; drain them
   // before the workgroup's LDS can be handed to the next one.
+  float4v bias_late[2 * NH];
+  if (bias_last) gemm_bias_load<Frag>(p, bias_late, n_base, lane);  // lands under the drain of the tail's loads
   F3R_VMCNT(0);
   if (STAGGER && wm == 0) __builtin_amdgcn_s_barrier();
   if (LAB & 128) stamp[2] = __builtin_amdgcn_s_memtime();
+  if (bias_last) gemm_acc_add_bias<Frag>(acc, bias_late);
   if (has_next) {  // every wave is past its last LDS read and the queue is empty: stage the next tile's opening half tiles under the epilogue
     setup_tile(m0_next, n0_next);
     opening_loads();

@@ -206,16 +206,18 @@ inline int gemm_additive_pattern(const f3r_gemm_args& a) {
 }
 
 template <class T, class L, int SRC, bool SWAP>
-__device__ __forceinline__ void gemm_acc_init_additive(const f3r_gemm_args& p, float4v* acc, int64_t m_base, int n_base, int lane) {
+__device__ __forceinline__ void gemm_acc_init_additive(const f3r_gemm_args& p, float4v* acc, int64_t m_base, int n_base, int lane, const bool with_bias = true) {
   constexpr int NF = L::NF, MF = L::MF;
   const int fr = lane & 15, fg = lane >> 4;
+  // with_bias = false: the caller adds the bias behind the K loop (gemm_acc_add_bias)
+  const float* const bias = with_bias ? p.bias : nullptr;
   // The bias goes in through the accumulators as well (act(sum + b) with the sum started at b): the epilogue then has no load that
   // a store could be waiting behind.
   if (SWAP) {  // swapped roles: a lane owns 4 tokens of ONE channel n = fr
 #pragma unroll
     for (int nf = 0; nf < NF; ++nf) {
       const int n = n_base + L::col(nf) + fr;
-      const float b = (p.bias && n < p.N) ? p.bias[n] : 0.f;
+      const float b = (bias && n < p.N) ? bias[n] : 0.f;
 #pragma unroll
       for (int mf = 0; mf < MF; ++mf) acc[mf * NF + nf] = float4v{b, b, b, b};
     }
@@ -226,7 +228,7 @@ __device__ __forceinline__ void gemm_acc_init_additive(const f3r_gemm_args& p, f
     float4v b4[NF];
 #pragma unroll
     for (int nf = 0; nf < NF; ++nf)
-      b4[nf] = p.bias ? *(const float4v*)((const char*)(p.bias + n_base + L::col(nf)) + (uint32_t)(fg * L::LW * 4)) : float4v{0.f, 0.f, 0.f, 0.f};
+      b4[nf] = bias ? *(const float4v*)((const char*)(bias + n_base + L::col(nf)) + (uint32_t)(fg * L::LW * 4)) : float4v{0.f, 0.f, 0.f, 0.f};
     if (SRC == F3R_ADD_NONE) {
 #pragma unroll
       for (int nf = 0; nf < NF; ++nf)
@@ -308,7 +310,7 @@ __device__ __forceinline__ void gemm_acc_init_additive(const f3r_gemm_args& p, f
   for (int nf = 0; nf < NF; ++nf) {
     const int nb = n_base + L::col(nf) + fg * L::LW;
     nbc[nf] = nb < p.N ? nb : p.N - 4;
-    bias4[nf] = p.bias ? *(const float4v*)(p.bias + nbc[nf]) : float4v{0.f, 0.f, 0.f, 0.f};
+    bias4[nf] = bias ? *(const float4v*)(bias + nbc[nf]) : float4v{0.f, 0.f, 0.f, 0.f};
   }
   if (SRC == F3R_ADD_NONE) {
 #pragma unroll
@@ -373,6 +375,26 @@ __device__ __forceinline__ void gemm_acc_init_additive(const f3r_gemm_args& p, f
 // i.e. `global_store v_off, v_data, s[base:base+1] offset:imm`: 3 instructions per fragment instead of ~20.  The general bodies below
 // (64-bit multiplies, compares and exec masking per fragment, 64-bit divisions per row in the QKV roles) made the epilogue a quarter of
 // the time of a K = 1024 tile (s_memtime stamps, profiles/r02_gemm256_tile_stamps.jsonl); they remain for the edge tiles.
+// The bias behind the K loop instead of under it (the 256-tile kernel's X3 convolutions): every MFMA step rounds at the size of the accumulator, and
+// started at the bias the three plane products of a long K (C = 1152: 972 steps) end 1.5x further from float64 than started at zero -- 3.6e-6
+// against 2.4e-6 of the output scale, where hi + lo fp16 planes promise 3e-6.
+template <class L>
+__device__ __forceinline__ void gemm_bias_load(const f3r_gemm_args& p, float4v* b, int n_base, int lane) {
+  const int fg = lane >> 4;
+#pragma unroll
+  for (int nf = 0; nf < L::NF; ++nf) {
+    const int nb = n_base + L::col(nf) + fg * L::LW;
+    b[nf] = p.bias ? *(const float4v*)(p.bias + (nb < p.N ? nb : p.N - 4)) : float4v{0.f, 0.f, 0.f, 0.f};
+  }
+}
+template <class L>
+__device__ __forceinline__ void gemm_acc_add_bias(float4v* acc, const float4v* b) {
+#pragma unroll
+  for (int nf = 0; nf < L::NF; ++nf)
+#pragma unroll
+    for (int mf = 0; mf < L::MF; ++mf) acc[nf * L::MF + mf] += b[nf];
+}
+
 template <class L>
 __device__ __forceinline__ bool gemm_wave_interior(const f3r_gemm_args& p, int64_t m_base, int n_base) {
   return m_base + L::row(L::MF - 1) + 16 <= p.M && n_base + L::col_end() <= p.N;

@@ -14,42 +14,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_cases import conv64 as _conv64, dec8 as _dec8, planes_ref as _planes_ref  # (one copy: the geometry suite sums the same planes)
 from fast3r_amd import ops
 from test_kernels_gpu import DEV, assert_close
 
 pytestmark = pytest.mark.gpu
 H16 = torch.float16
-
-
-def _dec8(b):
-    return b.view(torch.float8_e4m3fn).double()
-
-
-def _decode_weight_f8(wp, sc, co, ci):
-    """pack_conv3x3_weight_f8 rows -> (w_hi, w_lo8 decoded, w_hi8 decoded) as float64 (Cout, Cin, 3, 3)"""
-    kp = 9 * ci
-    raw = wp.view(torch.uint8).view(co, 4 * kp)
-    hi = raw[:, :2 * kp].contiguous().view(torch.float16).double()
-    e_lo = (sc.long() & 0xff).double()
-    e_hi = ((sc.long() >> 8) & 0xff).double()
-    lo8 = _dec8(raw[:, 2 * kp:3 * kp].contiguous()) * torch.exp2(e_lo - 127)[:, None]
-    hi8 = _dec8(raw[:, 3 * kp:].contiguous()) * torch.exp2(e_hi - 127)[:, None]
-    cv = lambda t: t.view(co, 3, 3, ci).permute(0, 3, 1, 2).contiguous()
-    return cv(hi), cv(lo8), cv(hi8)
-
-
-def _conv64(x_nhwc, w, stride=1):
-    return F.conv2d(x_nhwc.double().permute(0, 3, 1, 2), w.double(), None, padding=1, stride=stride).permute(0, 2, 3, 1)
-
-
-def _planes_ref(x32, wp, sc, co, ci):
-    """what split "x3f8" computes, in float64, from the planes the kernel reads"""
-    x_hi = x32.to(H16)
-    p8 = ops.f8_planes(x32)
-    a_hi8 = _dec8(p8[..., :ci].contiguous())
-    a_lo8 = _dec8(p8[..., ci:].contiguous()) / 4096.0
-    w_hi, w_lo8, w_hi8 = _decode_weight_f8(wp, sc, co, ci)
-    return _conv64(x_hi, w_hi) + _conv64(a_hi8, w_lo8) + _conv64(a_lo8, w_hi8), x_hi, p8
 
 
 @pytest.mark.parametrize("B,H,W,Ci,Co,res", [(2, 48, 40, 128, 128, False), (1, 64, 64, 256, 128, False), (2, 40, 48, 256, 256, True),
