@@ -695,7 +695,10 @@ __device__ __forceinline__ void gemm_epilogue_vt(const f3r_gemm_args& p, const f
   }
 #pragma unroll
   for (int nf = 0; nf < NF; ++nf) {
-    const int n = n_base + L::col(nf) + fr;  // < N
+    const int n = n_base + L::col(nf) + fr;
+    // N an odd multiple of 64 (an odd number of heads): the last 128-wide tile of the 128-tile kernel hangs 64 columns over N, and the wave that
+    // holds them runs in this role.  Its channels d >= Dm would land in the next sequence's rows (behind the buffer for the last one).
+    if (n >= p.N) continue;
     const int d = n - Dq - Dm;
     const float bb = (BIAS && p.bias) ? p.bias[n] : 0.f;
 #pragma unroll
