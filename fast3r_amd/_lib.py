@@ -154,6 +154,13 @@ SYMBOLS = {
     "f3r_sky_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
     "f3r_sky_detect": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp,
                                       ctypes.c_size_t, _c_vp, _c_vp, _c_vp]),
+    "f3r_mesh_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i64, _c_i64, ctypes.c_int]),
+    "f3r_mesh_threshold": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_vp, _c_vp, _c_vp]),
+    "f3r_mesh_count": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_vp, ctypes.c_int, _c_vp,
+                                      ctypes.c_size_t, _c_vp, _c_vp]),
+    "f3r_mesh_write": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "f3r_mesh_ply_pack": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")
@@ -177,6 +184,9 @@ SKY_ABI_VERSION = 400  # f3r_sky_detect (checked in fast3r_amd/ops.py too)
 F3R_SKY_CLASSIFY, F3R_SKY_MORPH, F3R_SKY_LABEL = 1, 2, 4
 F3R_SKY_EMPTY, F3R_SKY_NO_TOP, F3R_SKY_TOP = 0, 1, 2
 SKY_PIX_TILE, SKY_WORD_TILE = 16, 256  # F3R_SKY_PIX_TILE, F3R_SKY_WORD_TILE: words per workgroup of the two kinds of sky kernel
+MESH_ABI_VERSION = 410  # f3r_mesh_* (checked in fast3r_amd/ops.py too)
+MESH_TILE = 1024  # F3R_MESH_TILE: pixels, or quads, per workgroup of the mesh kernels
+F3R_INDEX_I32, F3R_INDEX_I64 = 0, 1
 
 
 def lib():

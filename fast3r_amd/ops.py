@@ -5,6 +5,7 @@ fallback: CPU tensors raise F3RError.
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1169,3 +1170,124 @@ def sky_detect(src, shapes, stages, *, want_not_sky=True, want_roots=False, want
                                ptr(stats), ptr(bits), stream_ptr()), "f3r_sky_detect")
     del keep, ws, table  # the launches are stream-ordered before the caching allocator can hand these blocks out again
     return {"not_sky": not_sky, "roots": roots, "stats": stats, "bits": bits, "word_offsets": [r[5] for r in rows]}
+
+
+# ------------------------------------------------------------------------------------------------------------------- mesh export
+def _mesh_lib():
+    l = _lib.lib()
+    if l.f3r_version() < _lib.MESH_ABI_VERSION:
+        raise _lib.F3RError(f"{_lib.LIB_PATH} is version {l.f3r_version()}; mesh export needs >= {_lib.MESH_ABI_VERSION}: "
+                            "rebuild it (fast3r_amd/csrc/build.sh)")
+    return l
+
+
+def mesh_index_id(index_dtype):
+    if index_dtype == torch.int32:
+        return _lib.F3R_INDEX_I32
+    if index_dtype == torch.int64:
+        return _lib.F3R_INDEX_I64
+    raise ValueError(f"mesh: index_dtype must be torch.int32 or torch.int64, got {index_dtype}")
+
+
+def mesh_build(conf, pts, img, mask, shapes, ranks, *, double_sided=True, drop_unreferenced=False, flip_axes=False, index_dtype=torch.int64):
+    """The triangle mesh of a list of views in one pass (f3r_mesh_threshold / _count / _write, include/f3r.h).  Lists over views of GPU
+    tensors: conf (H W,) fp32 or None (validity is the mask alone), pts (H W, 3) fp32, img (3, H W) fp32 planes or (H W, 3) uint8 colours,
+    mask (H W,) uint8 or None; shapes[i] = (H, W); ranks[i] = (k_lo, k_hi, gamma) as scene.percentile_indexes gives them (ignored without
+    conf).  -> dict(vertices (Nv, 3) fp32, faces (F, 3) index_dtype, face_colors (F, 3) uint8 on the device; thresholds (V,) fp32 and
+    nan_counts (V,) numpy, or None without any conf; counts (V, 3) int64 numpy: kept A, kept B, vertices per view).  The host reads back
+    the per-view counts once, between the count and the write."""
+    V = len(pts)
+    if V < 1 or not (len(conf) == len(img) == len(mask) == len(shapes) == len(ranks) == V):
+        raise ValueError("mesh_build: need one conf, pts, img, mask, shape and rank entry per view, and at least one view")
+    idx_id = mesh_index_id(index_dtype)
+    dev = pts[0].device
+    f32, u8 = torch.float32, torch.uint8
+    rows, hw, keep, vbase = [], [], [], 0
+    tsv, tsq = [0], [0]
+    T = _lib.MESH_TILE
+    for i in range(V):
+        H, W = int(shapes[i][0]), int(shapes[i][1])
+        if H < 1 or W < 1:
+            raise ValueError(f"mesh_build: view {i} is {H} x {W}; need H, W >= 1")
+        n = H * W
+        c, p, g, m = conf[i], pts[i], img[i], mask[i]
+        for t in (c, p, g, m):
+            if t is not None:
+                require_gpu(t, f"view {i}")
+                if t.device != dev:
+                    raise ValueError(f"mesh_build: view {i}: tensors on {t.device} and {dev}")
+        if p.dtype != f32 or tuple(p.shape) != (n, 3):
+            raise ValueError(f"mesh_build: view {i}: pts must be ({n}, 3) fp32, got {tuple(p.shape)} {p.dtype}")
+        if c is not None and (c.dtype != f32 or tuple(c.shape) != (n,)):
+            raise ValueError(f"mesh_build: view {i}: conf must be ({n},) fp32, got {tuple(c.shape)} {c.dtype}")
+        img_u8 = g.dtype == u8
+        if not ((img_u8 and tuple(g.shape) == (n, 3)) or (g.dtype == f32 and tuple(g.shape) == (3, n))):
+            raise ValueError(f"mesh_build: view {i}: img must be (3, {n}) fp32 planes or ({n}, 3) uint8, got {tuple(g.shape)} {g.dtype}")
+        if m is not None and (m.dtype != u8 or tuple(m.shape) != (n,)):
+            raise ValueError(f"mesh_build: view {i}: mask must be ({n},) uint8, got {tuple(m.shape)} {m.dtype}")
+        c = None if c is None else c.contiguous()
+        m = None if m is None else m.contiguous()
+        p, g = p.contiguous(), g.contiguous()
+        keep += [c, p, g, m]
+        k_lo, k_hi, gamma = (0, 0, 0.0) if c is None else ranks[i]
+        gamma_bits = int(np.asarray(gamma, dtype=np.float32).reshape(1).view(np.uint32)[0])
+        rows.append([0 if c is None else c.data_ptr(), p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), H, W, vbase,
+                     int(img_u8), int(k_lo), int(k_hi), gamma_bits, 0])
+        hw += [H, W]
+        vbase += n
+        tsv.append(tsv[-1] + (n + T - 1) // T)
+        tsq.append(tsq[-1] + max(1, ((H - 1) * (W - 1) + T - 1) // T))
+    total = vbase
+    if total >= 2 ** 31:
+        raise ValueError(f"mesh_build: {total} vertices; the indices are 32-bit: need fewer than 2^31 in all")
+    nvt, nqt = tsv[-1], tsq[-1]
+    table = torch.tensor([x for r in rows for x in r] + tsv + tsq, dtype=torch.int64).to(dev)   # one small upload
+    host_hw = (ctypes.c_int64 * len(hw))(*hw)
+    drop, ds, flip = int(bool(drop_unreferenced)), int(bool(double_sided)), int(bool(flip_axes))
+    have_conf = any(c is not None for c in conf)
+    l = _mesh_lib()
+    ws_bytes = l.f3r_mesh_workspace_bytes(nvt, nqt, total, drop)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    # one block: thresholds as fp32 bits, NaN counts, then the (V, 3) counts -- one readback
+    small = torch.empty(V * 5, dtype=torch.int32, device=dev)
+    thr, nans, counts = small[:V], small[V:2 * V], small[2 * V:]
+    with torch.cuda.device(dev):
+        if have_conf:
+            check(l.f3r_mesh_threshold(ptr(table), V, ptr(thr), ptr(nans), stream_ptr()), "f3r_mesh_threshold")
+        check(l.f3r_mesh_count(ptr(table), host_hw, V, nvt, nqt, total, ptr(thr) if have_conf else None, drop, ptr(ws), ws_bytes, ptr(counts),
+                               stream_ptr()), "f3r_mesh_count")
+        host = small.cpu().numpy()
+        cnt = host[2 * V:].view(np.uint32).reshape(V, 3).astype(np.int64)
+        n_faces = int((ds + 1) * (cnt[:, 0].sum() + cnt[:, 1].sum()))
+        n_vert = int(cnt[:, 2].sum())
+        vertices = torch.empty((n_vert, 3), dtype=f32, device=dev)
+        faces = torch.empty((n_faces, 3), dtype=index_dtype, device=dev)
+        colors = torch.empty((n_faces, 3), dtype=u8, device=dev)
+        check(l.f3r_mesh_write(ptr(table), host_hw, V, nvt, nqt, total, ds, drop, flip, idx_id, ptr(ws), ws_bytes,
+                               ptr(vertices) if n_vert else None, ptr(faces) if n_faces else None, ptr(colors) if n_faces else None,
+                               stream_ptr()), "f3r_mesh_write")
+    del keep, ws, table  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    return {"vertices": vertices, "faces": faces, "face_colors": colors, "counts": cnt,
+            "thresholds": host[:V].view(np.float32).copy() if have_conf else None,
+            "nan_counts": host[V:2 * V].view(np.uint32).copy() if have_conf else None}
+
+
+def mesh_ply_pack(vertices, faces, face_colors):
+    """(Nv, 3) fp32 vertices, (F, 3) int32 / int64 faces and (F, 3) uint8 face colours on the GPU -> uint8 device tensor of the 12 Nv + 16 F
+    record bytes (f3r_mesh_ply_pack)"""
+    for t, name in ((vertices, "vertices"), (faces, "faces"), (face_colors, "face_colors")):
+        require_gpu(t, name)
+    nv, nf = vertices.shape[0], faces.shape[0]
+    if (vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or tuple(faces.shape) != (nf, 3)
+            or tuple(face_colors.shape) != (nf, 3) or face_colors.dtype != torch.uint8):
+        raise ValueError(f"mesh_ply_pack: vertices (Nv, 3) fp32, faces (F, 3) and face_colors (F, 3) uint8, got {tuple(vertices.shape)} "
+                         f"{vertices.dtype}, {tuple(faces.shape)} {faces.dtype}, {tuple(face_colors.shape)} {face_colors.dtype}")
+    idx_id = mesh_index_id(faces.dtype)
+    if nv >= 2 ** 31:
+        raise ValueError(f"mesh_ply_pack: {nv} vertices; the file's indices are 32-bit: need fewer than 2^31")
+    vertices, faces, face_colors = vertices.contiguous(), faces.contiguous(), face_colors.contiguous()
+    out = torch.empty(nv * 3 + nf * 4, dtype=torch.int32, device=vertices.device)
+    with torch.cuda.device(vertices.device):
+        check(_mesh_lib().f3r_mesh_ply_pack(ptr(vertices) if nv else None, nv, ptr(faces) if nf else None, ptr(face_colors) if nf else None, nf,
+                                            idx_id, ptr(out), stream_ptr()), "f3r_mesh_ply_pack")
+    return out.view(torch.uint8)

@@ -186,34 +186,36 @@ class Scene:
         return p.shape[0]
 
 
-def _check_inputs(preds, views, sample, not_sky):
+def _check_inputs(preds, views, sample, not_sky, *, what="assemble_scene", keys=None, mask_name="not_sky"):
+    """the input checks of assemble_scene; build_mesh (fast3r_amd/mesh.py) runs the same ones under its own name, with the keys of the head
+    it reads (`keys`) and its `valid` masks in the place of `not_sky`"""
     if len(preds) == 0 or len(views) != len(preds):
-        raise ValueError(f"assemble_scene: need one view per pred and at least one (got {len(preds)} preds, {len(views)} views)")
+        raise ValueError(f"{what}: need one view per pred and at least one (got {len(preds)} preds, {len(views)} views)")
     for i, pred in enumerate(preds):
-        if "pts3d_local_aligned_to_global" not in pred:
+        if keys is None and "pts3d_local_aligned_to_global" not in pred:
             raise KeyError(f"'pts3d_local_aligned_to_global' not in preds[{i}]: call align_local_pts3d_to_global(preds, views) first")
-        for key in ("pts3d_in_other_view", "conf", "conf_local"):
+        for key in ("pts3d_in_other_view", "conf", "conf_local") if keys is None else keys:
             if key not in pred:
                 raise KeyError(f"'{key}' not in preds[{i}]")
         if "img" not in views[i]:
             raise KeyError(f"'img' not in views[{i}]")
-    B = preds[0]["conf"].shape[0]
+    B = preds[0]["conf" if keys is None else keys[1]].shape[0]
     if not 0 <= sample < B:
-        raise ValueError(f"assemble_scene: sample = {sample} outside [0, {B})")
+        raise ValueError(f"{what}: sample = {sample} outside [0, {B})")
     if isinstance(not_sky, str):
         if not_sky != "detect":
-            raise ValueError(f"assemble_scene: not_sky = {not_sky!r}; accepted values are None (no sky anywhere), 'detect' (detect_sky_masks "
+            raise ValueError(f"{what}: {mask_name} = {not_sky!r}; accepted values are None (no sky anywhere), 'detect' (detect_sky_masks "
                              "on the views' images) or a list of per-view (H, W) masks")
     elif not_sky is not None:
         if len(not_sky) != len(preds):
-            raise ValueError(f"assemble_scene: not_sky has {len(not_sky)} masks for {len(preds)} views")
+            raise ValueError(f"{what}: {mask_name} has {len(not_sky)} masks for {len(preds)} views")
         for i, m in enumerate(not_sky):
             m = torch.as_tensor(m)
-            hw = tuple(preds[i]["conf"].shape[1:3])
+            hw = tuple(preds[i]["conf" if keys is None else keys[1]].shape[1:3])
             if tuple(m.shape) != hw:
-                raise ValueError(f"assemble_scene: not_sky[{i}] has shape {tuple(m.shape)}; view {i} is {hw}")
+                raise ValueError(f"{what}: {mask_name}[{i}] has shape {tuple(m.shape)}; view {i} is {hw}")
             if m.dtype not in (torch.bool, torch.int8, torch.uint8):
-                raise ValueError(f"assemble_scene: not_sky[{i}] must be bool or int8, got {m.dtype}")
+                raise ValueError(f"{what}: {mask_name}[{i}] must be bool or int8, got {m.dtype}")
 
 
 def assemble_scene(output_or_preds, views=None, *, sample=0, not_sky=None, global_conf_thr_value_to_drop_view=1.5, niter_PnP=100, poses=True):

@@ -48,7 +48,7 @@ typedef enum { F3R_LOSS_DIS = 0, F3R_LOSS_LOG1P = 1 } f3r_loss_dis_mode; /* avg_
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 400 = 0.4.0 (+ f3r_sky_detect, f3r_sky_workspace_bytes); 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 410 = 0.4.1 (+ f3r_mesh_threshold, f3r_mesh_count, f3r_mesh_write, f3r_mesh_ply_pack, f3r_mesh_workspace_bytes); 400 = 0.4.0 (+ f3r_sky_detect, f3r_sky_workspace_bytes); 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -621,6 +621,53 @@ size_t f3r_sky_workspace_bytes(int64_t total_words, int64_t total_pixels, int64_
 int f3r_sky_detect(const int64_t* table, const int64_t* host_hw, int n_views, int64_t n_pix_tiles, int64_t n_word_tiles, int64_t total_words,
                    int64_t total_pixels, int64_t total_width, int stages, void* workspace, size_t workspace_bytes, int32_t* stats,
                    uint64_t* bits_out, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Mesh export (ABI 410): the as_mesh=True branch of the reference's notebooks/demo_multiview.ipynb plot_3d_points_with_colors --
+ * np.percentile(conf, p), conf > thr, fast3r/dust3r/viz.py pts3d_to_trimesh (:43-90) and cat_meshes (:93-104) -- for every view of a scene
+ * in one pass.  Python: fast3r_amd/mesh.py.  Quads of a view are numbered q = y (W - 1) + x, y < H - 1, x < W - 1; with i = y W + x,
+ * triangle A = (i, i + 1, i + W) and B = (i + 1, i + W, i + W + 1); a triangle is kept iff its three vertices are valid.
+ * `table` is a DEVICE int64 array: n_views rows of 12 { conf pointer ((H W) fp32; 0 = validity is the mask alone), pts pointer ((H W, 3)
+ *   fp32), img pointer (fp32 planes (3, H W) as stored, or with img_u8 != 0 the (H W, 3) colour bytes), mask pointer ((H W) bytes, nonzero =
+ *   valid; 0 = none), H, W, vbase (the sum of H W over the views before), img_u8, k_lo, k_hi (the two 0-based ranks np.percentile reads),
+ *   gamma (the bits of its fp32 weight), 0 }, then n_views + 1 vertex-tile starts (running sum of ceil(H W / F3R_MESH_TILE)) and n_views +
+ *   1 quad-tile starts (running sum of max(1, ceil((H - 1)(W - 1) / F3R_MESH_TILE))).  host_hw: HOST int64 [n_views][2] = the same H, W;
+ *   f3r_mesh_count and f3r_mesh_write check the three totals against it before anything is launched.
+ * f3r_mesh_threshold: thresholds[v] = numpy's fp32 _lerp (a + (b - a) g, or b - (b - a)(1 - g) where g >= 0.5) of the order statistics
+ *   k_lo, k_hi of view v's conf, found exactly by radix select, one workgroup per view; nan_counts[v] = its NaNs, and then thresholds[v]
+ *   is the quiet NaN 0x7fc00000 (np.percentile returns a NaN; nothing passes conf > NaN).
+ * f3r_mesh_count: valid = conf > thresholds[v] (skipped when thresholds or the view's conf is null) AND mask != 0, bit-packed into the
+ *   workspace; kept A and B per quad tile and their exclusive scans; with drop_unreferenced the vertices that a kept triangle uses (from
+ *   the validity of the up to six triangles at a vertex: no atomics) and their scan.  counts (device uint32 [n_views][3]) = { kept A, kept
+ *   B, vertices (used ones with drop_unreferenced, else H W) }.  View v then has (double_sided ? 2 : 1)(A + B) faces.
+ * f3r_mesh_write, with the same table, totals, drop_unreferenced and workspace as the count: vertices [sum of counts[.][2]][3] fp32 in view
+ *   order then pixel order ((x, y, z) -> (x, z, -y) with flip_axes); faces [F][3] of index_dtype and face_colors [F][3] bytes, view v's
+ *   from slot F_v = the faces of the views before: kept A in quad order as (i1, i2, i3); the same as (i3, i2, i1); kept B as (i2, i3,
+ *   i4); the same as (i4, i3, i2) -- the two backward blocks only with double_sided.  Indices are vbase + pixel, or with
+ *   drop_unreferenced the vertex's rank among the used ones.  A faces take the colour of the quad's top-left pixel, B faces of its
+ *   bottom-right: the byte as given, or trunc((img + 1.0f) * 127.5f) as two rounded fp32 operations, saturated to [0, 255] (NaN -> 0).
+ *   vertices may be null when there are none to write, faces when the count found none.
+ * f3r_mesh_ply_pack: n_vertices records of 12 bytes (xyz little-endian fp32), then n_faces of 16 { 3, three little-endian int32, r, g,
+ *   b }, into out (4-byte aligned, 12 n_vertices + 16 n_faces bytes).
+ * Limits, F3R_ERR_ARG before any launch: fewer than 2^31 vertices in all (indices, and the file's, are 32-bit; vbase and every face slot
+ *   are 64-bit).  The scan's counters are uint32: they hold kept A and kept B triangles separately, each at most the quad count, which
+ *   is below the vertex count, so they cannot wrap; up to 4 (2^31 - 1) faces are addressed.  Also F3R_ERR_ARG: null table, host_hw,
+ *   workspace or counts; n_views < 1; negative counts; H or W < 1; totals that do not match host_hw; an unknown index_dtype; a workspace
+ *   that is too small.  Inputs are not written to; two runs give the same bits.
+ */
+#define F3R_MESH_TILE 1024
+#define F3R_INDEX_I32 0
+#define F3R_INDEX_I64 1
+size_t f3r_mesh_workspace_bytes(int64_t n_vertex_tiles, int64_t n_quad_tiles, int64_t total_vertices, int drop_unreferenced);
+int f3r_mesh_threshold(const int64_t* table, int n_views, float* thresholds, uint32_t* nan_counts, f3r_stream_t stream);
+int f3r_mesh_count(const int64_t* table, const int64_t* host_hw, int n_views, int64_t n_vertex_tiles, int64_t n_quad_tiles,
+                   int64_t total_vertices, const float* thresholds, int drop_unreferenced, void* workspace, size_t workspace_bytes,
+                   uint32_t* counts, f3r_stream_t stream);
+int f3r_mesh_write(const int64_t* table, const int64_t* host_hw, int n_views, int64_t n_vertex_tiles, int64_t n_quad_tiles,
+                   int64_t total_vertices, int double_sided, int drop_unreferenced, int flip_axes, int index_dtype, const void* workspace,
+                   size_t workspace_bytes, float* vertices, void* faces, uint8_t* face_colors, f3r_stream_t stream);
+int f3r_mesh_ply_pack(const float* vertices, int64_t n_vertices, const void* faces, const uint8_t* face_colors, int64_t n_faces,
+                      int index_dtype, void* out, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
