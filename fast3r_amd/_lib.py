@@ -17,6 +17,13 @@ F3R_SPLIT_NONE, F3R_SPLIT_W2, F3R_SPLIT_X3, F3R_SPLIT_W2F8, F3R_SPLIT_X3F8 = 0, 
 F3R_MAX_SEG = 8
 F3R_REAL_F32, F3R_REAL_F64 = 0, 1
 F3R_LOSS_DIS, F3R_LOSS_LOG1P = 0, 1
+SCENE_TILE = 4096  # F3R_SCENE_TILE: keys per tile of the segmented sort; COLLECT_TILE: entries per tile of collect_points
+COLLECT_TILE = 1024
+F3R_SKY_CLASSIFY, F3R_SKY_MORPH, F3R_SKY_LABEL = 1, 2, 4
+F3R_SKY_EMPTY, F3R_SKY_NO_TOP, F3R_SKY_TOP = 0, 1, 2
+SKY_PIX_TILE, SKY_WORD_TILE = 16, 256  # F3R_SKY_PIX_TILE, F3R_SKY_WORD_TILE: words per workgroup of the two kinds of sky kernel
+MESH_TILE = 1024  # F3R_MESH_TILE: pixels, or quads, per workgroup of the mesh kernels
+F3R_INDEX_I32, F3R_INDEX_I64 = 0, 1
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
 
@@ -173,20 +180,7 @@ class F3RError(RuntimeError):
     pass
 
 
-ABI_VERSION = 350  # f3r_version() of include/f3r.h this file mirrors (the reconstruction metrics need RECON_ABI_VERSION)
-RECON_ABI_VERSION = 360
-POSE_METRIC_ABI_VERSION = 370  # f3r_pose_pair_metrics / f3r_pose_error_stats (fast3r_amd/ops.py checks it where it calls them)
-LOSS_ABI_VERSION = 380  # f3r_mv_conf_loss (checked in fast3r_amd/ops.py too)
-SCENE_ABI_VERSION = 390  # f3r_scene_*, f3r_ply_pack, f3r_color_* (checked in fast3r_amd/ops.py too)
-SCENE_TILE = 4096  # F3R_SCENE_TILE: keys per tile of the segmented sort; COLLECT_TILE: entries per tile of collect_points
-COLLECT_TILE = 1024
-SKY_ABI_VERSION = 400  # f3r_sky_detect (checked in fast3r_amd/ops.py too)
-F3R_SKY_CLASSIFY, F3R_SKY_MORPH, F3R_SKY_LABEL = 1, 2, 4
-F3R_SKY_EMPTY, F3R_SKY_NO_TOP, F3R_SKY_TOP = 0, 1, 2
-SKY_PIX_TILE, SKY_WORD_TILE = 16, 256  # F3R_SKY_PIX_TILE, F3R_SKY_WORD_TILE: words per workgroup of the two kinds of sky kernel
-MESH_ABI_VERSION = 410  # f3r_mesh_* (checked in fast3r_amd/ops.py too)
-MESH_TILE = 1024  # F3R_MESH_TILE: pixels, or quads, per workgroup of the mesh kernels
-F3R_INDEX_I32, F3R_INDEX_I64 = 0, 1
+ABI_VERSION = 410  # f3r_version() of include/f3r.h this file mirrors: lib() accepts no older library
 
 
 def lib():
@@ -197,16 +191,20 @@ def lib():
             raise F3RError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(fast3r_amd has no CPU / torch fallback)")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+
+        def bind(name):
             fn = getattr(l, name)  # AttributeError if the .so does not export what the header declares
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype, fn.argtypes = SYMBOLS[name]
+
+        bind("f3r_version")  # first: an older library lacks later symbols, and "rebuild it" says more than an AttributeError
+        if l.f3r_version() < ABI_VERSION:
+            raise F3RError(f"{LIB_PATH} is version {l.f3r_version()}, this host code needs >= {ABI_VERSION}: rebuild it (fast3r_amd/csrc/build.sh)")
+        for name in SYMBOLS:
+            bind(name)
         if l.f3r_sizeof(0) != ctypes.sizeof(GemmArgs) or l.f3r_sizeof(1) != ctypes.sizeof(AttnArgs) or l.f3r_sizeof(2) != ctypes.sizeof(AttnF32Args):
             raise F3RError("fast3r_amd/_lib.py struct layout does not match include/f3r.h "
                            f"(gemm {l.f3r_sizeof(0)} vs {ctypes.sizeof(GemmArgs)}, attn {l.f3r_sizeof(1)} vs {ctypes.sizeof(AttnArgs)}, "
                            f"attn_f32 {l.f3r_sizeof(2)} vs {ctypes.sizeof(AttnF32Args)}): rebuild the library (fast3r_amd/csrc/build.sh)")
-        if l.f3r_version() < ABI_VERSION:
-            raise F3RError(f"{LIB_PATH} is version {l.f3r_version()}, this host code needs >= {ABI_VERSION}: rebuild it (fast3r_amd/csrc/build.sh)")
         _lib = l
     return _lib
 

@@ -13,7 +13,7 @@ degrees) of a threshold or of a histogram edge k * 30 / 31; the reference's own 
 import numpy as np
 import torch
 
-from . import ops
+from . import post_ops
 from ._lib import work_device
 
 N_BINS_EXTRA = 1  # calculate_auc asks torch.histc for max_threshold + 1 bins over [0, max_threshold] (cam_pose_metric.py:93)
@@ -40,7 +40,7 @@ def camera_to_rel_deg(pred_cameras_c2w, gt_cameras_c2w, device=None, batch_size=
     pred, gt = _pair_inputs(pred_cameras_c2w, gt_cameras_c2w, "camera_to_rel_deg")
     if pred.dim() != 3:
         raise ValueError(f"camera_to_rel_deg: poses must be (N, 4, 4); got {tuple(pred.shape)}")
-    counts, rel_r, rel_t = ops.pose_pair_metrics(pred[None], gt[None], (), (), 1, 1.0, want_pairs=True)
+    counts, rel_r, rel_t = post_ops.pose_pair_metrics(pred[None], gt[None], (), (), 1, 1.0, want_pairs=True)
     if int(counts[0, 1]) != 0:
         raise ValueError("A matrix has trace outside valid range [-1-eps,3+eps].")
     return rel_r[0].to(home), rel_t[0].to(home)
@@ -63,7 +63,7 @@ def calculate_auc(r_error, t_error, max_threshold=30):
         raise ValueError(f"calculate_auc: r_error and t_error must be 1-D, of one length and dtype; got {tuple(r_error.shape)} and {tuple(t_error.shape)}")
     home, dev = r_error.device, work_device(r_error, "r_error")
     n_bins = int(max_threshold) + N_BINS_EXTRA
-    counts = ops.pose_error_stats(r_error.to(dev), t_error.to(dev), (), (), n_bins, float(max_threshold))
+    counts = post_ops.pose_error_stats(r_error.to(dev), t_error.to(dev), (), (), n_bins, float(max_threshold))
     return _auc_from_bins(counts[:n_bins], r_error.shape[0], r_error.dtype).to(home)
 
 
@@ -79,7 +79,7 @@ def camera_pose_metrics(pred_c2w, gt_c2w, rra_thresholds=(5, 15, 30), rta_thresh
         raise ValueError(f"camera_pose_metrics: poses must be (B, N, 4, 4); got {tuple(pred.shape)}")
     B, N = pred.shape[:2]
     n_r, n_t, n_bins = len(rra_thresholds), len(rta_thresholds), int(max_threshold) + N_BINS_EXTRA
-    counts, _, _ = ops.pose_pair_metrics(pred, gt, rra_thresholds, rta_thresholds, n_bins, float(max_threshold))
+    counts, _, _ = post_ops.pose_pair_metrics(pred, gt, rra_thresholds, rta_thresholds, n_bins, float(max_threshold))
     counts = counts.cpu()
     if int(counts[:, n_r + n_t + n_bins].sum()) != 0:
         raise ValueError("A matrix has trace outside valid range [-1-eps,3+eps].")

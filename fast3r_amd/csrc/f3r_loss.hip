@@ -54,26 +54,18 @@ struct Params {
   double clip, alpha;
 };
 
-size_t align8(size_t x) { return (x + 7) / 8 * 8; }
-
 size_t carve(Work* w, void* base, long long nseg) {
-  size_t off = 0;
-  char* p = (char*)base;
-  auto take = [&](size_t bytes) {
-    char* q = p ? p + off : nullptr;
-    off += align8(bytes);
-    return q;
-  };
-  const size_t slots = (size_t)MAX_BLOCKS + (size_t)nseg;
-  double* inv = (double*)take(sizeof(double) * 12 * nseg);
-  long long* tile0 = (long long*)take(sizeof(long long) * (nseg + 1));
-  double* mom_a = (double*)take(sizeof(double) * NA * nseg);
-  double* fac = (double*)take(sizeof(double) * 4 * nseg);
-  double* part_a = (double*)take(sizeof(double) * NA * slots);
-  double* part_b = (double*)take(sizeof(double) * NB * slots);
-  double* mom_b = (double*)take(sizeof(double) * NB * nseg);
+  Carve c(base, 8);
+  const size_t n = (size_t)nseg, slots = (size_t)MAX_BLOCKS + n;
+  double* inv = c.take<double>(12 * n);
+  long long* tile0 = c.take<long long>(n + 1);
+  double* mom_a = c.take<double>(NA * n);
+  double* fac = c.take<double>(4 * n);
+  double* part_a = c.take<double>(NA * slots);
+  double* part_b = c.take<double>(NB * slots);
+  double* mom_b = c.take<double>(NB * n);
   if (w) *w = Work{inv, tile0, mom_a, fac, part_a, part_b, mom_b};
-  return off;
+  return c.bytes();
 }
 
 // General inverse by Gauss-Jordan elimination with partial pivoting (the reference: torch.linalg.inv on the fp32 matrix).  A singular

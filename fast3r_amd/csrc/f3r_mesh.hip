@@ -38,12 +38,6 @@ struct MeshRow {  // one row of the device table, 12 x 8 bytes
 };
 static_assert(sizeof(MeshRow) == 12 * 8, "include/f3r.h states the row layout");
 
-__device__ __forceinline__ uint8_t sat_u8(float y) {  // truncation to uint8; below 0 and NaN -> 0, above 255 -> 255 (as f3r_scene.hip)
-  if (!(y > 0.f)) return 0;
-  if (y >= 255.f) return 255;
-  return (uint8_t)(int)y;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // thr[v] = np.percentile(conf of view v, p): numpy's _lerp on the order statistics k_lo, k_hi with weight gamma; NaN if any conf is NaN
 __global__ __launch_bounds__(THR_NT) void mesh_threshold_kernel(const MeshRow* __restrict__ rows, float* __restrict__ thr,
@@ -311,22 +305,16 @@ struct MeshWs {
 };
 
 MeshWs mesh_ws(void* base, int64_t nvt, int64_t nqt, int64_t total_vertices, int drop) {
-  char* w = (char*)base;
-  size_t o = 0;
+  Carve c(base, 256);
   MeshWs m = {};
-  m.bits = (uint64_t*)(w + o);
-  o += align256((size_t)nvt * MESH_STEPS * 8);
-  m.scanf = (uint32_t*)(w + o);
-  o += align256((size_t)(nqt + 1) * 2 * 4);
+  m.bits = c.take<uint64_t>((size_t)nvt * MESH_STEPS);
+  m.scanf = c.take<uint32_t>((size_t)(nqt + 1) * 2);
   if (drop) {
-    m.ubits = (uint64_t*)(w + o);
-    o += align256((size_t)nvt * MESH_STEPS * 8);
-    m.scanv = (uint32_t*)(w + o);
-    o += align256((size_t)(nvt + 1) * 4);
-    m.remap = (int32_t*)(w + o);
-    o += align256((size_t)total_vertices * 4);
+    m.ubits = c.take<uint64_t>((size_t)nvt * MESH_STEPS);
+    m.scanv = c.take<uint32_t>(nvt + 1);
+    m.remap = c.take<int32_t>(total_vertices);
   }
-  m.bytes = o;
+  m.bytes = c.bytes();
   return m;
 }
 

@@ -16,6 +16,7 @@
 
 #include <type_traits>
 
+#include "f3r_carve.h"
 #include "f3r_common.h"
 
 // ---- order-preserving integer keys: a < b as numbers <=> key(a) < key(b) as unsigned integers (-0.0 < +0.0, NaNs beyond the infinities)
@@ -34,6 +35,13 @@ __device__ __forceinline__ uint64_t dkey(double v) {
 __device__ __forceinline__ double dkey_inv(uint64_t k) {
   const uint64_t u = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
   return __builtin_bit_cast(double, u);
+}
+
+// ---- the 8-bit colour of an image value (scene, sky and mesh form (img + 1) * 127.5 themselves)
+__device__ __forceinline__ uint8_t sat_u8(float y) {  // truncation to uint8; below 0 and NaN -> 0, above 255 -> 255
+  if (!(y > 0.f)) return 0;
+  if (y >= 255.f) return 255;
+  return (uint8_t)(int)y;
 }
 
 // ---- ballots
@@ -137,6 +145,5 @@ static __global__ __launch_bounds__(NT) void exclusive_scan_rows_kernel(uint32_t
   if (threadIdx.x == NT - 1 && totals) totals[blockIdx.x] = sh[NT - 1];
 }
 
-// ---- host
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// ---- host (align256 and the workspace carver: f3r_carve.h)
 inline unsigned blocks_of(int64_t n, int nt) { return (unsigned)((n + nt - 1) / nt); }

@@ -680,20 +680,39 @@ __global__ void to_i32_kernel(const uint32_t* __restrict__ a, int n, int32_t* __
   if (t < n) o[t] = (int32_t)a[t];
 }
 
-// the sort buffers of f3r_nn_workspace_bytes(n), carved from ws
+// the workspaces, sized on a null base and carved on the caller's (a braced list is evaluated left to right: the regions lie in that order).
+// First the sort buffers of f3r_nn_build / _query
 struct SortWs {
   uint32_t *k0, *v0, *k1, *v1, *hist, *misc;
+  size_t bytes;
 };
 SortWs carve(void* ws, int64_t n) {
-  char* p = (char*)ws;
-  SortWs w;
-  w.k0 = (uint32_t*)p; p += align256(4 * n);
-  w.v0 = (uint32_t*)p; p += align256(4 * n);
-  w.k1 = (uint32_t*)p; p += align256(4 * n);
-  w.v1 = (uint32_t*)p; p += align256(4 * n);
-  w.hist = (uint32_t*)p; p += align256(4 * (256 * tiles_of(n) + 1));
-  w.misc = (uint32_t*)p;
-  return w;
+  Carve c(ws, 256);
+  return {c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(256 * tiles_of(n) + 1),
+          c.take<uint32_t>(MISC_BYTES / 4), c.bytes()};
+}
+struct StatsWs {
+  double *dots, *partial;
+  SelState* st;
+  uint32_t* hist;
+  size_t bytes;
+};
+StatsWs stats_ws(void* ws, int64_t n) {
+  Carve c(ws, 256);
+  return {c.take<double>(n), c.take<double>(3 * RED_BLOCKS), c.take<SelState>(1), c.take<uint32_t>(512), c.bytes()};
+}
+struct PrepareWs {
+  float* thr;
+  uint32_t *cnt, *tot;
+  float *pred_c, *gticp_c;
+  uint8_t* w_c;
+  size_t bytes;
+};
+PrepareWs prepare_ws(void* ws, int n_samples, int n_views, int64_t L) {
+  const size_t B = (size_t)n_samples, BL = B * (size_t)L;
+  Carve c(ws, 256);
+  return {c.take<float>(2 * B * n_views), c.take<uint32_t>(2 * B * tiles_of(L)), c.take<uint32_t>(2 * B), c.take<float>(3 * BL), c.take<float>(3 * BL),
+          c.take<uint8_t>(BL), c.bytes()};
 }
 
 int key_bits_of(int64_t ncells) {
@@ -742,7 +761,7 @@ extern "C" size_t f3r_nn_index_bytes(int64_t m) {
 
 extern "C" size_t f3r_nn_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return 4 * align256(4 * (size_t)n) + align256(4 * (size_t)(256 * tiles_of(n) + 1)) + MISC_BYTES;
+  return carve(nullptr, n).bytes;
 }
 
 extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t index_bytes, void* workspace, size_t ws_bytes, f3r_stream_t stream) {
@@ -909,7 +928,7 @@ extern "C" int f3r_estimate_normals(const void* index, const float* pts, int k, 
 
 extern "C" size_t f3r_recon_stats_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return align256(8 * (size_t)n) + align256(8 * 3 * RED_BLOCKS) + align256(sizeof(SelState)) + align256(4 * 512);
+  return stats_ws(nullptr, n).bytes;
 }
 
 extern "C" int f3r_recon_stats(const double* dist, const int32_t* idx, const double* normals_q, const double* normals_db, int64_t n, int64_t m_db,
@@ -920,11 +939,7 @@ extern "C" int f3r_recon_stats(const double* dist, const int32_t* idx, const dou
   F3R_REQUIRE(!normals_q == !normals_db && (!normals_q || idx || n == 0), "f3r_recon_stats: normals need both clouds' normals and idx");
   F3R_REQUIRE(ws_bytes >= f3r_recon_stats_workspace_bytes(n) && (((uintptr_t)workspace) & 255) == 0, "f3r_recon_stats: workspace too small / misaligned");
   hipStream_t s = (hipStream_t)stream;
-  char* p = (char*)workspace;
-  double* dots = (double*)p; p += align256(8 * (size_t)n);
-  double* partial = (double*)p; p += align256(8 * 3 * RED_BLOCKS);
-  SelState* st = (SelState*)p; p += align256(sizeof(SelState));
-  uint32_t* hist = (uint32_t*)p;
+  const auto [dots, partial, st, hist, bytes] = stats_ws(workspace, n);
   const bool nrm = normals_q != nullptr;
   if (nrm && n) hipLaunchKernelGGL(dots_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, idx, normals_q, normals_db, n, m_db, dots);
   hipLaunchKernelGGL(reduce_kernel, dim3(RED_BLOCKS), dim3(RED_NT), 0, s, dist, nrm ? dots : nullptr, n, dist_th, partial);
@@ -937,9 +952,7 @@ extern "C" int f3r_recon_stats(const double* dist, const int32_t* idx, const dou
 
 extern "C" size_t f3r_recon_prepare_workspace_bytes(int n_samples, int n_views, int64_t L) {
   if (n_samples <= 0 || n_views <= 0 || L <= 0) return 0;
-  const size_t BL = (size_t)n_samples * (size_t)L;
-  return align256(4 * 2 * (size_t)n_samples * (size_t)n_views) + align256(4 * 2 * (size_t)n_samples * (size_t)tiles_of(L)) +
-         align256(4 * 2 * (size_t)n_samples) + 2 * align256(12 * BL) + align256(BL);
+  return prepare_ws(nullptr, n_samples, n_views, L).bytes;
 }
 
 extern "C" int f3r_recon_prepare(const float* conf, const float* pred, const float* gt, const uint8_t* valid, const int64_t* seg, int n_samples,
@@ -954,13 +967,7 @@ extern "C" int f3r_recon_prepare(const float* conf, const float* pred, const flo
   const int B = n_samples, V = n_views;
   const int64_t nt = tiles_of(L);
   const size_t BL = (size_t)B * (size_t)L;
-  char* p = (char*)workspace;
-  float* thr = (float*)p; p += align256(4 * 2 * (size_t)B * V);
-  uint32_t* cnt = (uint32_t*)p; p += align256(4 * 2 * (size_t)B * nt);
-  uint32_t* tot = (uint32_t*)p; p += align256(4 * 2 * (size_t)B);
-  float* pred_c = (float*)p; p += align256(12 * BL);
-  float* gticp_c = (float*)p; p += align256(12 * BL);
-  uint8_t* w_c = (uint8_t*)p;
+  const auto [thr, cnt, tot, pred_c, gticp_c, w_c, bytes] = prepare_ws(workspace, B, V, L);
   hipLaunchKernelGGL(recon_thr_kernel, dim3(B * V), dim3(PNT), 0, s, conf, seg, q_metric, q_icp, thr);
   hipLaunchKernelGGL(recon_count_kernel, dim3((unsigned)nt, B), dim3(64), 0, s, conf, valid, seg, thr, V, L, nt, cnt);
   hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(2 * B), dim3(SCAN_NT), 0, s, cnt, (const int64_t*)nullptr, nt, tot);

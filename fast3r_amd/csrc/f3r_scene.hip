@@ -63,12 +63,6 @@ __global__ void scene_stats_init_kernel(uint32_t* __restrict__ stats, int S) {
   if (i < S * 4) stats[i] = (i & 3) == 0 ? 0xffffffffu : 0u;
 }
 
-__device__ __forceinline__ uint8_t sat_u8(float y) {  // truncation to uint8; below 0 and NaN -> 0, above 255 -> 255
-  if (!(y > 0.f)) return 0;
-  if (y >= 255.f) return 255;
-  return (uint8_t)(int)y;
-}
-
 template <bool FIRST>
 __global__ __launch_bounds__(SCENE_NT) void scene_hist_kernel(const SegRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                               const uint32_t* __restrict__ keys, int shift, uint32_t* __restrict__ hist,
@@ -432,11 +426,31 @@ __global__ void color_to_u8_kernel(const T* __restrict__ c, int64_t n, int rule,
 
 constexpr size_t EXT_HIST_BYTES = 3 * 4 * 2048 * sizeof(uint32_t);
 
+// the workspaces, sized on a null base and carved on the caller's (a braced list is evaluated left to right: the regions lie in that order)
+struct SortWs {
+  uint32_t *k0, *v0, *k1, *v1, *hist;
+  u32x4* recs;
+  size_t bytes;
+};
+SortWs sort_ws(void* base, int64_t n, int64_t n_tiles) {
+  Carve c(base, 256);
+  return {c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(n_tiles * 256), c.take<u32x4>(n), c.bytes()};
+}
+struct ExtWs {
+  uint32_t* hist;
+  ExtState* st;
+  size_t bytes;
+};
+ExtWs ext_ws(void* base) {
+  Carve c(base, 256);
+  return {c.take<uint32_t>(EXT_HIST_BYTES / sizeof(uint32_t)), c.take<ExtState>(1), c.bytes()};
+}
+
 }  // namespace
 
 extern "C" size_t f3r_scene_sort_workspace_bytes(int64_t total_keys, int64_t n_tiles) {
   if (total_keys < 1 || n_tiles < 1) return 0;
-  return 4 * align256((size_t)total_keys * 4) + align256((size_t)n_tiles * 256 * 4) + align256((size_t)total_keys * 16);
+  return sort_ws(nullptr, total_keys, n_tiles).bytes;
 }
 
 extern "C" int f3r_scene_sort(const int64_t* table, int n_segments, int64_t n_tiles, int64_t total_keys, const uint8_t* lut, void* workspace,
@@ -450,11 +464,7 @@ extern "C" int f3r_scene_sort(const int64_t* table, int n_segments, int64_t n_ti
   hipStream_t s = (hipStream_t)stream;
   const SegRow* rows = (const SegRow*)table;
   const int64_t* ts = table + (int64_t)n_segments * 6;
-  char* w = (char*)workspace;
-  const size_t kb = align256((size_t)total_keys * 4);
-  uint32_t *k0 = (uint32_t*)w, *v0 = (uint32_t*)(w + kb), *k1 = (uint32_t*)(w + 2 * kb), *v1 = (uint32_t*)(w + 3 * kb);
-  uint32_t* hist = (uint32_t*)(w + 4 * kb);
-  u32x4* recs = (u32x4*)(w + 4 * kb + align256((size_t)n_tiles * 256 * 4));
+  const auto [k0, v0, k1, v1, hist, recs, ws_bytes] = sort_ws(workspace, total_keys, n_tiles);
   const SceneOut o = {order, pts, conf, rgb, conf_rgb, mask};
   const dim3 g((unsigned)n_tiles), b(SCENE_NT);
   hipLaunchKernelGGL(scene_stats_init_kernel, dim3((n_segments * 4 + 255) / 256), dim3(256), 0, s, stats, n_segments);
@@ -478,7 +488,7 @@ extern "C" int f3r_scene_sort(const int64_t* table, int n_segments, int64_t n_ti
   return f3r_check_launch("f3r_scene_sort");
 }
 
-extern "C" size_t f3r_scene_extent_workspace_bytes(void) { return EXT_HIST_BYTES + align256(sizeof(ExtState)); }
+extern "C" size_t f3r_scene_extent_workspace_bytes(void) { return ext_ws(nullptr).bytes; }
 
 extern "C" int f3r_scene_extent(const float* pts, int64_t m, const int64_t* ranks, void* workspace, size_t workspace_bytes, uint32_t* out,
                                 f3r_stream_t stream) {
@@ -491,8 +501,7 @@ extern "C" int f3r_scene_extent(const float* pts, int64_t m, const int64_t* rank
     rk.k[r] = ranks[r];
   }
   hipStream_t s = (hipStream_t)stream;
-  uint32_t* hist = (uint32_t*)workspace;
-  ExtState* st = (ExtState*)((char*)workspace + EXT_HIST_BYTES);
+  const auto [hist, st, ws_bytes] = ext_ws(workspace);
   const unsigned nb = (unsigned)std::min<int64_t>(1024, (m + EXT_NT - 1) / EXT_NT);
   hipLaunchKernelGGL(ext_init_kernel, dim3(1), dim3(64), 0, s, st, rk);
   if (hipMemsetAsync(hist, 0, EXT_HIST_BYTES, s) != hipSuccess) return f3r_check_launch("f3r_scene_extent");

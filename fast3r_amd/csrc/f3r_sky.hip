@@ -58,12 +58,6 @@ constexpr HsvTab make_hsv_tab() {
 }
 __constant__ HsvTab kHsvTab = make_hsv_tab();
 
-__device__ __forceinline__ int sat_u8(float y) {  // truncation to uint8; below 0 and NaN -> 0, above 255 -> 255 (as f3r_scene.hip)
-  if (!(y > 0.f)) return 0;
-  if (y >= 255.f) return 255;
-  return (int)y;
-}
-
 // steps 1-3 for one pixel: is it sky-coloured?
 __device__ __forceinline__ bool sky_colour(float fr, float fg, float fb, bool in_upper, const int32_t* sdiv, const int32_t* hdiv) {
   const int r = sat_u8((fr + 1.0f) * 127.5f), g = sat_u8((fg + 1.0f) * 127.5f), b = sat_u8((fb + 1.0f) * 127.5f);
@@ -281,20 +275,24 @@ __global__ __launch_bounds__(SKY_NT) void sky_apply_kernel(const SkyRow* __restr
   if (lane == 0 && n_kept) atomicAdd(stats + t.seg * 5 + 3, n_kept);
 }
 
-struct SkyLayout {
-  size_t bits_bytes, parent_bytes, size_bytes;
+// the workspace, sized on a null base and carved on the caller's (a braced list is evaluated left to right: the regions lie in that order)
+struct SkyWs {
+  uint64_t *cur, *other;
+  int32_t *parent, *top_size;  // empty without F3R_SKY_LABEL
+  size_t bytes;
 };
-SkyLayout sky_layout(int64_t total_words, int64_t total_pixels, int64_t total_width, int stages) {
+SkyWs sky_ws(void* base, int64_t total_words, int64_t total_pixels, int64_t total_width, int stages) {
   const bool label = stages & F3R_SKY_LABEL;
-  return {align256((size_t)total_words * 8), label ? align256((size_t)total_pixels * 4) : 0, label ? align256((size_t)total_width * 4) : 0};
+  Carve c(base, 256);
+  return {c.take<uint64_t>(total_words), c.take<uint64_t>(total_words), c.take<int32_t>(label ? total_pixels : 0),
+          c.take<int32_t>(label ? total_width : 0), c.bytes()};
 }
 
 }  // namespace
 
 extern "C" size_t f3r_sky_workspace_bytes(int64_t total_words, int64_t total_pixels, int64_t total_width, int stages) {
   if (total_words < 1 || total_pixels < 1 || total_width < 1) return 0;
-  const SkyLayout l = sky_layout(total_words, total_pixels, total_width, stages);
-  return 2 * l.bits_bytes + l.parent_bytes + l.size_bytes;
+  return sky_ws(nullptr, total_words, total_pixels, total_width, stages).bytes;
 }
 
 extern "C" int f3r_sky_detect(const int64_t* table, const int64_t* host_hw, int n_views, int64_t n_pix_tiles, int64_t n_word_tiles,
@@ -330,11 +328,7 @@ extern "C" int f3r_sky_detect(const int64_t* table, const int64_t* host_hw, int 
   const SkyRow* rows = (const SkyRow*)table;
   const int64_t* ts_pix = table + (int64_t)n_views * SKY_ROW;
   const int64_t* ts_word = ts_pix + n_views + 1;
-  const SkyLayout l = sky_layout(total_words, total_pixels, total_width, stages);
-  char* w = (char*)workspace;
-  uint64_t *cur = (uint64_t*)w, *other = (uint64_t*)(w + l.bits_bytes);
-  int32_t* parent = (int32_t*)(w + 2 * l.bits_bytes);
-  int32_t* top_size = (int32_t*)(w + 2 * l.bits_bytes + l.parent_bytes);
+  auto [cur, other, parent, top_size, ws_bytes] = sky_ws(workspace, total_words, total_pixels, total_width, stages);
   const dim3 gp((unsigned)n_pix_tiles), gw((unsigned)n_word_tiles), b(SKY_NT);
 
   if (stages & F3R_SKY_CLASSIFY)

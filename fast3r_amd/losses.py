@@ -2,7 +2,7 @@
 
 Every released config validates with `ConfLossMultiviewV2(Regr3DMultiviewV4(L21Loss, norm_mode="avg_dis"), alpha=0.2)` (data_scaling and
 model_scaling: `Regr3DMultiviewV3`).  The classes here carry the reference's names and constructor signatures, so such a config line
-builds the same object; calling it runs one HIP kernel family (f3r_loss.hip, `ops.mv_conf_loss`) instead of the reference's chain of
+builds the same object; calling it runs one HIP kernel family (f3r_loss.hip, `post_ops.mv_conf_loss`) instead of the reference's chain of
 concatenations, NaN fills, boolean gathers and einsums, and returns the reference's `(loss, details)`:
 
     loss      0-dim fp32 tensor on the device, without grad (there is no backward here)
@@ -29,7 +29,7 @@ from copy import copy, deepcopy
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import _lib, post_ops
 
 
 class LLoss(nn.Module):
@@ -99,7 +99,7 @@ class MultiLoss(nn.Module):
 
 
 def _parse_norm_mode(norm_mode, version):
-    """-> ops dis_mode; raises what the module docstring lists."""
+    """-> post_ops dis_mode; raises what the module docstring lists."""
     name = f"Regr3DMultiviewV{version}"
     if not norm_mode:
         raise ValueError(f"{name}: an empty norm_mode is not supported (the reference fails on it too); use 'avg_dis' or 'avg_log1p'")
@@ -191,7 +191,7 @@ class ConfLossMultiviewV2(MultiLoss):
                 _lib.require_gpu(p[k], f"preds[{i}]['{k}']")
         dev = preds[0]["pts3d_in_other_view"].device
         pl = self.pixel_loss
-        out = ops.mv_conf_loss(
+        out = post_ops.mv_conf_loss(
             [g["pts3d"].to(dev) for g in gts], [g["valid_mask"].to(dev) for g in gts], [g["camera_pose"].to(dev) for g in gts],
             [p["pts3d_in_other_view"] for p in preds], [p["conf"] for p in preds],
             [p["pts3d_local"] for p in preds] if local else None, [p["conf_local"] for p in preds] if local else None,

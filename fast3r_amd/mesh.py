@@ -40,9 +40,10 @@ indices, red, green, blue).
 import numpy as np
 import torch
 
-from . import ops
+from . import post_ops
+from ._frontend import check_inputs, fp32_on, on_work_device, preds_and_views, read_back
 from ._lib import require_gpu, work_device
-from .scene import _check_inputs, percentile_indexes
+from .scene import percentile_indexes
 
 MESH_VERTEX_BYTES = 12
 MESH_FACE_BYTES = 16
@@ -55,18 +56,11 @@ def mesh_ply_header(n_vertices, n_faces):
     return "\n".join(lines).encode("ascii") + b"\n"
 
 
-def _on_device(x, name):
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not torch.is_tensor(x):
-        raise ValueError(f"generate_mesh_ply_bytes: {name} must be a torch tensor or a numpy array, got {type(x).__name__}")
-    return x.to(work_device(x, name))
-
-
 def generate_mesh_ply_bytes(vertices, faces, face_colors):
     """The binary PLY of a mesh (layout: the module text), packed on the device and brought back with one copy through pinned memory.
     vertices (Nv, 3) fp32, faces (F, 3) int32 / int64, face_colors (F, 3) uint8; torch or numpy."""
-    vertices, faces, face_colors = _on_device(vertices, "vertices"), _on_device(faces, "faces"), _on_device(face_colors, "face_colors")
+    vertices, faces, face_colors = (on_work_device(x, "generate_mesh_ply_bytes", name)[0]
+                                    for x, name in ((vertices, "vertices"), (faces, "faces"), (face_colors, "face_colors")))
     nv, nf = vertices.shape[0], faces.shape[0]
     if vertices.dim() != 2 or vertices.shape[1] != 3 or tuple(faces.shape) != (nf, 3) or tuple(face_colors.shape) != (nf, 3):
         raise ValueError(f"generate_mesh_ply_bytes: vertices (Nv, 3), faces (F, 3) and face_colors (F, 3), got {tuple(vertices.shape)}, "
@@ -76,11 +70,8 @@ def generate_mesh_ply_bytes(vertices, faces, face_colors):
     header = mesh_ply_header(nv, nf)
     if nv == 0 and nf == 0:
         return header
-    rec = ops.mesh_ply_pack(vertices, faces.to(vertices.device), face_colors.to(vertices.device))
-    host = torch.empty(rec.shape[0], dtype=torch.uint8, pin_memory=True)
-    host.copy_(rec, non_blocking=True)
-    torch.cuda.current_stream(rec.device).synchronize()
-    return header + host.numpy().tobytes()
+    rec = post_ops.mesh_ply_pack(vertices, faces.to(vertices.device), face_colors.to(vertices.device))
+    return header + read_back(rec)
 
 
 def save_mesh_ply(path, vertices, faces, face_colors):
@@ -127,7 +118,7 @@ def pts3d_to_trimesh(img, pts3d, valid=None):
             mask = valid.reshape(-1)
         else:
             raise ValueError(f"pts3d_to_trimesh: valid must be bool or uint8, got {valid.dtype}")
-    out = ops.mesh_build([None], [pts3d.reshape(-1, 3)], [img.reshape(-1, 3)], [mask], [(H, W)], [None])
+    out = post_ops.mesh_build([None], [pts3d.reshape(-1, 3)], [img.reshape(-1, 3)], [mask], [(H, W)], [None])
     return dict(vertices=out["vertices"], face_colors=out["face_colors"], faces=out["faces"])
 
 
@@ -150,32 +141,20 @@ def build_mesh(output_or_preds, views=None, *, sample=0, head="global", min_conf
     `double_sided=False` leaves the backward-wound copies out; `drop_unreferenced=True` keeps only the vertices that a face uses, in
     their order, and renumbers the faces; `flip_axes=True` maps (x, y, z) to (x, z, -y); `index_dtype`: torch.int64 (the reference's)
     or torch.int32.  Input tensors are never written.  Results stay on the device."""
-    if isinstance(output_or_preds, dict):
-        preds = output_or_preds["preds"]
-        views = output_or_preds["views"] if views is None else views
-    else:
-        preds = output_or_preds
-    if views is None:
-        raise ValueError("build_mesh: views are needed for the face colours")
+    preds, views = preds_and_views(output_or_preds, views, "build_mesh", "face colours")
     if head not in ("global", "local"):
         raise ValueError(f"build_mesh: head must be 'global' or 'local', got {head!r}")
     if not 0 <= min_conf_thr_percentile <= 100:
         raise ValueError(f"build_mesh: min_conf_thr_percentile = {min_conf_thr_percentile} outside [0, 100]")
     if isinstance(valid, str):
         raise ValueError(f"build_mesh: valid = {valid!r}; accepted values are None or a list of per-view (H, W) masks")
-    ops.mesh_index_id(index_dtype)
+    post_ops.mesh_index_id(index_dtype)
     conf_key = "conf" if head == "global" else "conf_local"
     pts_key = "pts3d_in_other_view"
     if head == "local":
         pts_key = "pts3d_local_aligned_to_global" if len(preds) and all("pts3d_local_aligned_to_global" in p for p in preds) else "pts3d_local"
-    _check_inputs(preds, views, sample, valid, what="build_mesh", keys=(pts_key, conf_key), mask_name="valid")
+    check_inputs(preds, views, sample, valid, what="build_mesh", keys=(pts_key, conf_key), mask_name="valid")
     dev = work_device(preds[0][conf_key], "preds")
-
-    def flat(t, tail):
-        t = t[sample]
-        if t.device != dev or t.dtype != torch.float32:
-            t = t.to(dev, torch.float32)
-        return t.reshape(tail)
 
     conf, pts, img, mask, shapes, ranks = [], [], [], [], [], []
     for i, (pred, view) in enumerate(zip(preds, views)):
@@ -185,9 +164,9 @@ def build_mesh(output_or_preds, views=None, *, sample=0, head="global", min_conf
         if tuple(pred[pts_key].shape[1:]) != (H, W, 3):
             raise ValueError(f"build_mesh: preds[{i}]['{pts_key}'] is {tuple(pred[pts_key].shape)}; expected (B, {H}, {W}, 3)")
         shapes.append((H, W))
-        conf.append(flat(pred[conf_key], (H * W,)))
-        pts.append(flat(pred[pts_key], (H * W, 3)))
-        img.append(flat(view["img"], (3, H * W)))   # the (3, H, W) planes as stored: nothing is permuted
+        conf.append(fp32_on(pred[conf_key][sample], dev, (H * W,)))
+        pts.append(fp32_on(pred[pts_key][sample], dev, (H * W, 3)))
+        img.append(fp32_on(view["img"][sample], dev, (3, H * W)))   # the (3, H, W) planes as stored: nothing is permuted
         ranks.append(percentile_indexes(H * W, min_conf_thr_percentile))
         m = None
         if valid is not None:
@@ -197,8 +176,8 @@ def build_mesh(output_or_preds, views=None, *, sample=0, head="global", min_conf
             m = m.contiguous().view(torch.uint8) if m.dtype in (torch.bool, torch.int8) else m
             m = m.reshape(-1)
         mask.append(m)
-    out = ops.mesh_build(conf, pts, img, mask, shapes, ranks, double_sided=double_sided, drop_unreferenced=drop_unreferenced,
-                         flip_axes=flip_axes, index_dtype=index_dtype)
+    out = post_ops.mesh_build(conf, pts, img, mask, shapes, ranks, double_sided=double_sided, drop_unreferenced=drop_unreferenced,
+                              flip_axes=flip_axes, index_dtype=index_dtype)
     cnt = out["counts"]
     return Mesh(out["vertices"], out["faces"], out["face_colors"], out["thresholds"], (2 if double_sided else 1) * (cnt[:, 0] + cnt[:, 1]),
                 cnt[:, 2].copy())

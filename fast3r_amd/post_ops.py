@@ -1,0 +1,454 @@
+"""Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
+loss, scene assembly, sky detection and mesh export.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
+"""
+import ctypes
+import itertools
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, require_gpu, stream_ptr
+
+
+def _thresholds(ts):
+    ts = [float(t) for t in ts]
+    return (ctypes.c_double * max(1, len(ts)))(*ts), len(ts)
+
+
+def _real_id(dt):
+    if dt == torch.float32:
+        return _lib.F3R_REAL_F32
+    if dt == torch.float64:
+        return _lib.F3R_REAL_F64
+    raise ValueError(f"fast3r_amd: camera-pose metrics take torch.float32 or torch.float64, got {dt}")
+
+
+def pose_pair_metrics(pred, gt, r_thresholds, t_thresholds, n_bins, max_threshold, want_pairs=False):
+    """Relative-pose errors of every view pair i < j of every sample (cam_pose_metric.py:17-40) and their counts.  pred, gt: (B, N, 4, 4)
+    cam-to-world, fp32 or fp64, same dtype, on the GPU.  -> (counts int64 (B, n_r + n_t + n_bins + 2) = thresholds passed | histc bins of
+    max(r, t) | pairs with a trace out of range | pairs with the 1e6 default, rel_r, rel_t): the per-pair errors in degrees, (B, N (N - 1) / 2)
+    in the input dtype in torch.combinations order, only with want_pairs (otherwise None: nothing per pair is allocated or written)."""
+    require_gpu(pred, "pred")
+    require_gpu(gt, "gt")
+    if pred.dim() != 4 or tuple(pred.shape[2:]) != (4, 4) or pred.shape != gt.shape or pred.dtype != gt.dtype:
+        raise ValueError(f"pred and gt must both be (B, N, 4, 4) of one dtype; got {tuple(pred.shape)} {pred.dtype} and {tuple(gt.shape)} {gt.dtype}")
+    B, N = pred.shape[:2]
+    pred, gt = pred.contiguous(), gt.contiguous()
+    rt, n_r = _thresholds(r_thresholds)
+    tt, n_t = _thresholds(t_thresholds)
+    counts = torch.empty((B, n_r + n_t + int(n_bins) + 2), dtype=torch.int64, device=pred.device)
+    rel_r = torch.empty((B, N * (N - 1) // 2), dtype=pred.dtype, device=pred.device) if want_pairs else None
+    rel_t = torch.empty_like(rel_r) if want_pairs else None
+    with torch.cuda.device(pred.device):
+        check(_lib.lib().f3r_pose_pair_metrics(ptr(pred), ptr(gt), _real_id(pred.dtype), B, N, rt, n_r, tt, n_t, int(n_bins), float(max_threshold),
+                                               ptr(rel_r), ptr(rel_t), ptr(counts), stream_ptr()), "f3r_pose_pair_metrics")
+    return counts, rel_r, rel_t
+
+
+def pose_error_stats(r_error, t_error, r_thresholds, t_thresholds, n_bins, max_threshold):
+    """The counts of pose_pair_metrics from given per-pair errors (1-D, same length and dtype, on the GPU): int64 (n_r + n_t + n_bins + 2)."""
+    require_gpu(r_error, "r_error")
+    require_gpu(t_error, "t_error")
+    if r_error.dim() != 1 or r_error.shape != t_error.shape or r_error.dtype != t_error.dtype:
+        raise ValueError(f"r_error and t_error must be 1-D, of one length and dtype; got {tuple(r_error.shape)} {r_error.dtype} and "
+                         f"{tuple(t_error.shape)} {t_error.dtype}")
+    r_error, t_error = r_error.contiguous(), t_error.contiguous()
+    n = r_error.numel()
+    rt, n_r = _thresholds(r_thresholds)
+    tt, n_t = _thresholds(t_thresholds)
+    counts = torch.empty(n_r + n_t + int(n_bins) + 2, dtype=torch.int64, device=r_error.device)
+    with torch.cuda.device(r_error.device):
+        check(_lib.lib().f3r_pose_error_stats(ptr(r_error) if n else None, ptr(t_error) if n else None, n, _real_id(r_error.dtype), rt, n_r, tt, n_t,
+                                              int(n_bins), float(max_threshold), ptr(counts), stream_ptr()), "f3r_pose_error_stats")
+    return counts
+
+
+def mv_conf_loss(gt_pts, valid_mask, camera_pose, pred_pts, pred_conf, pred_pts_local=None, pred_conf_local=None, *, version=4, dis_mode=0,
+                 gt_scale=False, local_scale_consistent=False, dist_clip=None, alpha=1.0):
+    """ConfLossMultiviewV2(Regr3DMultiviewV3 | V4(L21Loss, avg_dis | avg_log1p), alpha) on the device (f3r_mv_conf_loss, include/f3r.h).
+    Lists over views of GPU tensors: gt_pts / pred_pts / pred_pts_local (B, H, W, 3) fp32, valid_mask (B, H, W) bool or uint8, camera_pose
+    (B, 4, 4) fp32 or fp64, pred_conf / pred_conf_local (B, H, W) fp32; (H, W) may differ between views.  Nothing is concatenated: the
+    kernels read every tensor where it lies (a non-contiguous one is made contiguous first).  -> fp64 device tensor (1 + 4 V):
+    total | pts3d_loss_global | pts3d_loss_local | conf_loss_global | conf_loss_local (the local parts only with a local head)."""
+    V = len(gt_pts)
+    local = pred_pts_local is not None
+    lists = [gt_pts, valid_mask, camera_pose, pred_pts, pred_conf] + ([pred_pts_local, pred_conf_local] if local else [])
+    if V < 1 or any(x is None or len(x) != V for x in lists):
+        raise ValueError("mv_conf_loss: every per-view list must have one entry per view (at least one view); pred_pts_local and "
+                         "pred_conf_local are given together")
+    dev = gt_pts[0].device
+    B = gt_pts[0].shape[0]
+    keep, rows, npix = [], [[] for _ in range(7)], []
+    pose_dtype = camera_pose[0].dtype
+    for v in range(V):
+        g = gt_pts[v]
+        if g.dim() != 4 or g.shape[-1] != 3 or g.shape[0] != B:
+            raise ValueError(f"mv_conf_loss: view {v}: pts3d must be (B = {B}, H, W, 3), got {tuple(g.shape)}")
+        want = {0: (g.shape, torch.float32), 3: (g.shape, torch.float32), 5: (g.shape, torch.float32), 1: (g.shape[:3], None),
+                4: (g.shape[:3], torch.float32), 6: (g.shape[:3], torch.float32), 2: ((B, 4, 4), pose_dtype)}
+        for i, lst in enumerate(lists):
+            t = lst[v]
+            require_gpu(t, f"view {v} of input {i}")
+            shape, dt = want[i]
+            if i == 1:
+                if t.dtype not in (torch.bool, torch.uint8):
+                    raise ValueError(f"mv_conf_loss: view {v}: valid_mask must be bool or uint8, got {t.dtype}")
+            elif t.dtype != dt:
+                raise ValueError(f"mv_conf_loss: view {v}, input {i}: expected {dt}, got {t.dtype}")
+            if tuple(t.shape) != tuple(shape) or t.device != dev:
+                raise ValueError(f"mv_conf_loss: view {v}, input {i}: expected shape {tuple(shape)} on {dev}, got {tuple(t.shape)} on {t.device}")
+            t = t.contiguous()
+            keep.append(t)
+            rows[i].append(t.data_ptr())
+        npix.append(g.shape[1] * g.shape[2])
+    if not local:
+        rows[5] = rows[6] = [0] * V
+    table = torch.tensor(rows + [npix], dtype=torch.int64).to(dev)  # one small upload: 7 pointer tables and the pixel counts
+    l = _lib.lib()
+    ws_bytes = l.f3r_mv_conf_loss_workspace_bytes(V, B)
+    if ws_bytes == 0:
+        raise ValueError(f"mv_conf_loss: {V} views x {B} samples is not a supported shape")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(1 + 4 * V, dtype=torch.float64, device=dev)
+    row = lambda i: table[i].data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        check(l.f3r_mv_conf_loss(row(0), row(1), row(2), _real_id(pose_dtype), row(3), row(4), row(5) if local else None, row(6) if local else None,
+                                 row(7), V, B, int(version), int(dis_mode), int(bool(gt_scale)), int(bool(local_scale_consistent)),
+                                 int(dist_clip is not None), float(dist_clip) if dist_clip is not None else 0.0, float(alpha), ptr(ws), ws_bytes,
+                                 ptr(out), stream_ptr()), "f3r_mv_conf_loss")
+    del keep  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    return out
+
+
+def tile_starts(lengths, tile, at_least_one=False):
+    """the n + 1 running tile counts of a list of lengths: ceil(length / tile) each, with at_least_one never fewer than one (an entry
+    without work still owns a workgroup)"""
+    floor = int(at_least_one)
+    return [0] + list(itertools.accumulate(max(floor, (n + tile - 1) // tile) for n in lengths))
+
+
+def table_words(rows, *starts):
+    """rows (one list of int64 per entry) followed by the lists of tile starts, as one host int64 tensor: the caller's one small upload"""
+    return torch.tensor([x for r in rows for x in r] + [x for st in starts for x in st], dtype=torch.int64)
+
+
+def scene_sort(conf, pts, img, mask, lut):
+    """The segmented stable confidence sort with its fused gathers (f3r_scene_sort, include/f3r.h).  Lists over segments of GPU tensors:
+    conf (L,) fp32, pts (L, 3) fp32, img (3, L) fp32 planes, mask (L,) int8 or None; lut (256, 3) uint8 on the device.
+    -> dict(order int32, pts, conf, rgb uint8, conf_rgb uint8, mask int8: concatenated over segments; offsets: the segments' first slots;
+    stats (S, 4) int32 bit patterns of the uint32 words)."""
+    S = len(conf)
+    if S < 1 or len(pts) != S or len(img) != S or len(mask) != S:
+        raise ValueError("scene_sort: need one conf, pts, img and mask entry per segment, and at least one segment")
+    dev = conf[0].device
+    require_gpu(lut, "lut")
+    if lut.dtype != torch.uint8 or lut.numel() != 768:
+        raise ValueError("scene_sort: lut must be 256 x 3 uint8")
+    rows, lengths, keep, off = [], [], [lut.contiguous()], 0
+    f32, i8 = torch.float32, torch.int8
+    for s in range(S):
+        c, p, g, m = conf[s], pts[s], img[s], mask[s]
+        L = c.numel()
+        for t in (c, p, g, m):
+            if t is not None and not t.is_cuda:
+                require_gpu(t, f"segment {s}")
+        if (c.dtype != f32 or p.dtype != f32 or g.dtype != f32 or c.dim() != 1 or p.shape != (L, 3) or g.shape != (3, L)
+                or p.device != dev or g.device != dev or c.device != dev):
+            raise ValueError(f"scene_sort: segment {s}: conf (L,), pts (L, 3), img (3, L), all fp32 on {dev}; got {tuple(c.shape)} {c.dtype}, "
+                             f"{tuple(p.shape)} {p.dtype}, {tuple(g.shape)} {g.dtype}")
+        if m is not None and (m.dtype != i8 or m.shape != (L,) or m.device != dev):
+            raise ValueError(f"scene_sort: segment {s}: mask must be ({L},) int8 on {dev}, got {tuple(m.shape)} {m.dtype} on {m.device}")
+        if not 1 <= L < 2 ** 31:
+            raise ValueError(f"scene_sort: segment {s} has {L} keys; need 1 <= L < 2^31")
+        c, p, g = c.contiguous(), p.contiguous(), g.contiguous()
+        m = None if m is None else m.contiguous()
+        keep += [c, p, g, m]
+        rows.append([c.data_ptr(), p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), L, off])
+        lengths.append(L)
+        off += L
+    total = off
+    starts = tile_starts(lengths, _lib.SCENE_TILE)
+    table, n_tiles = table_words(rows, starts).to(dev), starts[-1]
+    l = _lib.lib()
+    ws_bytes = l.f3r_scene_sort_workspace_bytes(total, n_tiles)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = {"order": torch.empty(total, dtype=torch.int32, device=dev), "pts": torch.empty((total, 3), dtype=torch.float32, device=dev),
+           "conf": torch.empty(total, dtype=torch.float32, device=dev), "rgb": torch.empty((total, 3), dtype=torch.uint8, device=dev),
+           "conf_rgb": torch.empty((total, 3), dtype=torch.uint8, device=dev), "mask": torch.empty(total, dtype=torch.int8, device=dev),
+           "stats": torch.empty((S, 4), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        check(l.f3r_scene_sort(ptr(table), S, n_tiles, total, ptr(keep[0]), ptr(ws), ws_bytes, ptr(out["order"]), ptr(out["pts"]), ptr(out["conf"]),
+                               ptr(out["rgb"]), ptr(out["conf_rgb"]), ptr(out["mask"]), ptr(out["stats"]), stream_ptr()), "f3r_scene_sort")
+    del keep, ws  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    out["offsets"] = [r[5] for r in rows]
+    return out
+
+
+def scene_extent_stats(pts, ranks):
+    """Order statistics `ranks` (four 0-based ranks in ascending order) of each axis of pts (M, 3) fp32 on the GPU (f3r_scene_extent).
+    -> int32 (15,) on the device: 12 fp32 bit patterns [axis][rank], then the NaN count of each axis."""
+    require_gpu(pts, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype != torch.float32 or not pts.is_contiguous() or pts.shape[0] < 1:
+        raise ValueError(f"scene_extent_stats: pts must be a contiguous (M >= 1, 3) fp32 tensor, got {tuple(pts.shape)} {pts.dtype}")
+    if len(ranks) != 4:
+        raise ValueError("scene_extent_stats: four ranks")
+    l = _lib.lib()
+    ws_bytes = l.f3r_scene_extent_workspace_bytes()
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pts.device)
+    out = torch.empty(15, dtype=torch.int32, device=pts.device)
+    rk = (ctypes.c_int64 * 4)(*[int(r) for r in ranks])
+    with torch.cuda.device(pts.device):
+        check(l.f3r_scene_extent(ptr(pts), pts.shape[0], rk, ptr(ws), ws_bytes, ptr(out), stream_ptr()), "f3r_scene_extent")
+    return out
+
+
+def scene_collect(pts, colors, masks, nums, const_colors):
+    """The prefix cut and stable mask compaction of collect_points (f3r_scene_collect_count / _write).  Lists over segments: pts (L, 3) fp32
+    sorted points, colors (L, 3) uint8 or None (then const_colors[s] = (r, g, b) is used), masks (L,) int8 or None (keep all), nums = how
+    many entries to take from the front (1 <= num <= L).  -> (points (M, 3) fp32, colors (M, 3) uint8) on the device, or (None, None) when
+    nothing is kept.  The host reads back one word: the total."""
+    S = len(pts)
+    if S < 1:
+        return None, None
+    dev = pts[0].device
+    rows, keep = [], []
+    for s in range(S):
+        p, c, m, n = pts[s], colors[s], masks[s], int(nums[s])
+        require_gpu(p, f"segment {s} pts")
+        L = p.shape[0]
+        if p.dim() != 2 or p.shape[1] != 3 or p.dtype != torch.float32 or not p.is_contiguous():
+            raise ValueError(f"scene_collect: segment {s}: pts must be contiguous (L, 3) fp32")
+        if not 1 <= n <= L:
+            raise ValueError(f"scene_collect: segment {s}: num = {n} outside [1, {L}]")
+        if c is not None and (tuple(c.shape) != (L, 3) or c.dtype != torch.uint8 or not c.is_contiguous() or c.device != dev):
+            raise ValueError(f"scene_collect: segment {s}: colors must be contiguous ({L}, 3) uint8 on {dev}")
+        if m is not None and (tuple(m.shape) != (L,) or m.dtype != torch.int8 or not m.is_contiguous() or m.device != dev):
+            raise ValueError(f"scene_collect: segment {s}: mask must be contiguous ({L},) int8 on {dev}")
+        cc = (0, 0, 0) if const_colors[s] is None else const_colors[s]
+        rows.append([p.data_ptr(), 0 if c is None else c.data_ptr(), 0 if m is None else m.data_ptr(), n,
+                     int(cc[0]) | int(cc[1]) << 8 | int(cc[2]) << 16])
+        keep += [p, c, m]
+    starts = tile_starts([r[3] for r in rows], _lib.COLLECT_TILE)
+    table, n_tiles = table_words(rows, starts).to(dev), starts[-1]
+    l = _lib.lib()
+    scan = torch.empty(n_tiles + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(l.f3r_scene_collect_count(ptr(table), S, n_tiles, ptr(scan), stream_ptr()), "f3r_scene_collect_count")
+        total = int(scan[n_tiles].item()) & 0xffffffff
+        if total == 0:
+            return None, None
+        out_p = torch.empty((total, 3), dtype=torch.float32, device=dev)
+        out_c = torch.empty((total, 3), dtype=torch.uint8, device=dev)
+        check(l.f3r_scene_collect_write(ptr(table), S, n_tiles, ptr(scan), ptr(out_p), ptr(out_c), stream_ptr()), "f3r_scene_collect_write")
+    del keep
+    return out_p, out_c
+
+
+def ply_pack(points, colors_u8):
+    """(M, 3) fp32 points and (M, 3) uint8 colours on the GPU -> uint8 device tensor of the 15 M record bytes (f3r_ply_pack)"""
+    require_gpu(points, "points")
+    require_gpu(colors_u8, "colors")
+    n = points.shape[0]
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or tuple(colors_u8.shape) != (n, 3) or colors_u8.dtype != torch.uint8:
+        raise ValueError(f"ply_pack: points (M, 3) fp32 and colors (M, 3) uint8, got {tuple(points.shape)} {points.dtype}, "
+                         f"{tuple(colors_u8.shape)} {colors_u8.dtype}")
+    points, colors_u8 = points.contiguous(), colors_u8.contiguous()
+    out = torch.empty((n * 15 + 3) // 4, dtype=torch.int32, device=points.device)
+    with torch.cuda.device(points.device):
+        check(_lib.lib().f3r_ply_pack(ptr(points), ptr(colors_u8), n, ptr(out), stream_ptr()), "f3r_ply_pack")
+    return out.view(torch.uint8)[:n * 15]
+
+
+def color_range(colors):
+    """int64 (3,) on the device: the bit patterns of {key of the minimum, key of the maximum, NaN count} of a float32 / float64 GPU tensor
+    (f3r_color_range; fast3r_amd/scene.py decodes the keys)"""
+    require_gpu(colors, "colors")
+    colors = colors.contiguous()
+    out = torch.empty(3, dtype=torch.int64, device=colors.device)
+    with torch.cuda.device(colors.device):
+        check(_lib.lib().f3r_color_range(ptr(colors), colors.numel(), _real_id(colors.dtype), ptr(out), stream_ptr()), "f3r_color_range")
+    return out
+
+
+def color_to_u8(colors, rule, lo=0.0, hi=1.0):
+    """safe_color_conversion's rule 0 / 1 / 2 in the tensor's own dtype (f3r_color_to_u8) -> uint8 tensor of the same shape"""
+    require_gpu(colors, "colors")
+    colors = colors.contiguous()
+    out = torch.empty(colors.shape, dtype=torch.uint8, device=colors.device)
+    with torch.cuda.device(colors.device):
+        check(_lib.lib().f3r_color_to_u8(ptr(colors), colors.numel(), _real_id(colors.dtype), int(rule), float(lo), float(hi), ptr(out),
+                                         stream_ptr()), "f3r_color_to_u8")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------- sky detection
+def sky_row_words(W):
+    """64-bit words per row of the bit-packed bitmap (include/f3r.h f3r_sky_detect)"""
+    return (W + 63) // 64
+
+
+def sky_detect(src, shapes, stages, *, want_not_sky=True, want_roots=False, want_bits=False):
+    """f3r_sky_detect (include/f3r.h) on a list of views in one call.  src[i]: with F3R_SKY_CLASSIFY in `stages` the (3, H * W) fp32
+    planes of view i, otherwise its (H, W) int8 bitmap, on the GPU; shapes[i] = (H, W).
+    -> dict(not_sky: list of (H, W) int8, roots: list of (H, W) int32, stats: (V, 5) int32 on the device, bits: uint64 words as int64
+    (V concatenated), word_offsets) with the entries that were asked for and that the stages produce."""
+    V = len(src)
+    if V < 1 or len(shapes) != V:
+        raise ValueError(f"sky_detect: need one shape per view and at least one view (got {V} views, {len(shapes)} shapes)")
+    classify, label = bool(stages & _lib.F3R_SKY_CLASSIFY), bool(stages & _lib.F3R_SKY_LABEL)
+    dev = src[0].device
+    keep, rows, hw, words = [], [], [], []
+    word_off = pix_off = width_off = 0
+    not_sky, roots = [], []
+    for i, (t, (H, W)) in enumerate(zip(src, shapes)):
+        H, W = int(H), int(W)
+        if H < 1 or W < 1 or H * W >= 2 ** 31:
+            raise ValueError(f"sky_detect: view {i} is {H} x {W}; need H, W >= 1 and H * W < 2^31")
+        require_gpu(t, f"view {i}")
+        want = ((3, H * W), torch.float32) if classify else ((H, W), torch.int8)
+        if tuple(t.shape) != want[0] or t.dtype != want[1] or t.device != dev:
+            raise ValueError(f"sky_detect: view {i} must be {want[0]} {want[1]} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        t = t.contiguous()
+        keep.append(t)
+        ns = torch.empty((H, W), dtype=torch.int8, device=dev) if (label and want_not_sky) else None
+        rt = torch.empty((H, W), dtype=torch.int32, device=dev) if (label and want_roots) else None
+        not_sky.append(ns)
+        roots.append(rt)
+        n_words = H * sky_row_words(W)
+        # mask.size * 0.01 and int(height * 0.4) are Python doubles in the reference; an integer size exceeds the first iff it exceeds its floor
+        rows.append([t.data_ptr(), 0 if ns is None else ns.data_ptr(), 0 if rt is None else rt.data_ptr(), H, W, word_off, pix_off, width_off,
+                     int(math.floor(H * W * 0.01)), int(H * 0.4)])
+        hw += [H, W]
+        words.append(n_words)
+        word_off += n_words
+        pix_off += H * W
+        width_off += W
+    pix_starts, word_starts = tile_starts(words, _lib.SKY_PIX_TILE), tile_starts(words, _lib.SKY_WORD_TILE)
+    table = table_words(rows, pix_starts, word_starts).to(dev)
+    host_hw = (ctypes.c_int64 * len(hw))(*hw)
+    l = _lib.lib()
+    ws_bytes = l.f3r_sky_workspace_bytes(word_off, pix_off, width_off, stages)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    stats = torch.empty((V, 5), dtype=torch.int32, device=dev) if label else None
+    bits = torch.empty(word_off, dtype=torch.int64, device=dev) if (want_bits or not label) else None
+    with torch.cuda.device(dev):
+        check(l.f3r_sky_detect(ptr(table), host_hw, V, pix_starts[-1], word_starts[-1], word_off, pix_off, width_off, stages, ptr(ws), ws_bytes,
+                               ptr(stats), ptr(bits), stream_ptr()), "f3r_sky_detect")
+    del keep, ws, table  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    return {"not_sky": not_sky, "roots": roots, "stats": stats, "bits": bits, "word_offsets": [r[5] for r in rows]}
+
+
+# ------------------------------------------------------------------------------------------------------------------- mesh export
+def mesh_index_id(index_dtype):
+    if index_dtype == torch.int32:
+        return _lib.F3R_INDEX_I32
+    if index_dtype == torch.int64:
+        return _lib.F3R_INDEX_I64
+    raise ValueError(f"mesh: index_dtype must be torch.int32 or torch.int64, got {index_dtype}")
+
+
+def mesh_build(conf, pts, img, mask, shapes, ranks, *, double_sided=True, drop_unreferenced=False, flip_axes=False, index_dtype=torch.int64):
+    """The triangle mesh of a list of views in one pass (f3r_mesh_threshold / _count / _write, include/f3r.h).  Lists over views of GPU
+    tensors: conf (H W,) fp32 or None (validity is the mask alone), pts (H W, 3) fp32, img (3, H W) fp32 planes or (H W, 3) uint8 colours,
+    mask (H W,) uint8 or None; shapes[i] = (H, W); ranks[i] = (k_lo, k_hi, gamma) as scene.percentile_indexes gives them (ignored without
+    conf).  -> dict(vertices (Nv, 3) fp32, faces (F, 3) index_dtype, face_colors (F, 3) uint8 on the device; thresholds (V,) fp32 and
+    nan_counts (V,) numpy, or None without any conf; counts (V, 3) int64 numpy: kept A, kept B, vertices per view).  The host reads back
+    the per-view counts once, between the count and the write."""
+    V = len(pts)
+    if V < 1 or not (len(conf) == len(img) == len(mask) == len(shapes) == len(ranks) == V):
+        raise ValueError("mesh_build: need one conf, pts, img, mask, shape and rank entry per view, and at least one view")
+    idx_id = mesh_index_id(index_dtype)
+    dev = pts[0].device
+    f32, u8 = torch.float32, torch.uint8
+    rows, hw, pix, quads, keep, vbase = [], [], [], [], [], 0
+    for i in range(V):
+        H, W = int(shapes[i][0]), int(shapes[i][1])
+        if H < 1 or W < 1:
+            raise ValueError(f"mesh_build: view {i} is {H} x {W}; need H, W >= 1")
+        n = H * W
+        c, p, g, m = conf[i], pts[i], img[i], mask[i]
+        for t in (c, p, g, m):
+            if t is not None:
+                require_gpu(t, f"view {i}")
+                if t.device != dev:
+                    raise ValueError(f"mesh_build: view {i}: tensors on {t.device} and {dev}")
+        if p.dtype != f32 or tuple(p.shape) != (n, 3):
+            raise ValueError(f"mesh_build: view {i}: pts must be ({n}, 3) fp32, got {tuple(p.shape)} {p.dtype}")
+        if c is not None and (c.dtype != f32 or tuple(c.shape) != (n,)):
+            raise ValueError(f"mesh_build: view {i}: conf must be ({n},) fp32, got {tuple(c.shape)} {c.dtype}")
+        img_u8 = g.dtype == u8
+        if not ((img_u8 and tuple(g.shape) == (n, 3)) or (g.dtype == f32 and tuple(g.shape) == (3, n))):
+            raise ValueError(f"mesh_build: view {i}: img must be (3, {n}) fp32 planes or ({n}, 3) uint8, got {tuple(g.shape)} {g.dtype}")
+        if m is not None and (m.dtype != u8 or tuple(m.shape) != (n,)):
+            raise ValueError(f"mesh_build: view {i}: mask must be ({n},) uint8, got {tuple(m.shape)} {m.dtype}")
+        c = None if c is None else c.contiguous()
+        m = None if m is None else m.contiguous()
+        p, g = p.contiguous(), g.contiguous()
+        keep += [c, p, g, m]
+        k_lo, k_hi, gamma = (0, 0, 0.0) if c is None else ranks[i]
+        gamma_bits = int(np.asarray(gamma, dtype=np.float32).reshape(1).view(np.uint32)[0])
+        rows.append([0 if c is None else c.data_ptr(), p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), H, W, vbase,
+                     int(img_u8), int(k_lo), int(k_hi), gamma_bits, 0])
+        hw += [H, W]
+        pix.append(n)
+        quads.append((H - 1) * (W - 1))
+        vbase += n
+    total = vbase
+    if total >= 2 ** 31:
+        raise ValueError(f"mesh_build: {total} vertices; the indices are 32-bit: need fewer than 2^31 in all")
+    tsv = tile_starts(pix, _lib.MESH_TILE)
+    tsq = tile_starts(quads, _lib.MESH_TILE, at_least_one=True)   # a view of one row or column has no quads and still one tile
+    nvt, nqt = tsv[-1], tsq[-1]
+    table = table_words(rows, tsv, tsq).to(dev)
+    host_hw = (ctypes.c_int64 * len(hw))(*hw)
+    drop, ds, flip = int(bool(drop_unreferenced)), int(bool(double_sided)), int(bool(flip_axes))
+    have_conf = any(c is not None for c in conf)
+    l = _lib.lib()
+    ws_bytes = l.f3r_mesh_workspace_bytes(nvt, nqt, total, drop)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    # one block: thresholds as fp32 bits, NaN counts, then the (V, 3) counts -- one readback
+    small = torch.empty(V * 5, dtype=torch.int32, device=dev)
+    thr, nans, counts = small[:V], small[V:2 * V], small[2 * V:]
+    with torch.cuda.device(dev):
+        if have_conf:
+            check(l.f3r_mesh_threshold(ptr(table), V, ptr(thr), ptr(nans), stream_ptr()), "f3r_mesh_threshold")
+        check(l.f3r_mesh_count(ptr(table), host_hw, V, nvt, nqt, total, ptr(thr) if have_conf else None, drop, ptr(ws), ws_bytes, ptr(counts),
+                               stream_ptr()), "f3r_mesh_count")
+        host = small.cpu().numpy()
+        cnt = host[2 * V:].view(np.uint32).reshape(V, 3).astype(np.int64)
+        n_faces = int((ds + 1) * (cnt[:, 0].sum() + cnt[:, 1].sum()))
+        n_vert = int(cnt[:, 2].sum())
+        vertices = torch.empty((n_vert, 3), dtype=f32, device=dev)
+        faces = torch.empty((n_faces, 3), dtype=index_dtype, device=dev)
+        colors = torch.empty((n_faces, 3), dtype=u8, device=dev)
+        check(l.f3r_mesh_write(ptr(table), host_hw, V, nvt, nqt, total, ds, drop, flip, idx_id, ptr(ws), ws_bytes,
+                               ptr(vertices) if n_vert else None, ptr(faces) if n_faces else None, ptr(colors) if n_faces else None,
+                               stream_ptr()), "f3r_mesh_write")
+    del keep, ws, table  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    return {"vertices": vertices, "faces": faces, "face_colors": colors, "counts": cnt,
+            "thresholds": host[:V].view(np.float32).copy() if have_conf else None,
+            "nan_counts": host[V:2 * V].view(np.uint32).copy() if have_conf else None}
+
+
+def mesh_ply_pack(vertices, faces, face_colors):
+    """(Nv, 3) fp32 vertices, (F, 3) int32 / int64 faces and (F, 3) uint8 face colours on the GPU -> uint8 device tensor of the 12 Nv + 16 F
+    record bytes (f3r_mesh_ply_pack)"""
+    for t, name in ((vertices, "vertices"), (faces, "faces"), (face_colors, "face_colors")):
+        require_gpu(t, name)
+    nv, nf = vertices.shape[0], faces.shape[0]
+    if (vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or tuple(faces.shape) != (nf, 3)
+            or tuple(face_colors.shape) != (nf, 3) or face_colors.dtype != torch.uint8):
+        raise ValueError(f"mesh_ply_pack: vertices (Nv, 3) fp32, faces (F, 3) and face_colors (F, 3) uint8, got {tuple(vertices.shape)} "
+                         f"{vertices.dtype}, {tuple(faces.shape)} {faces.dtype}, {tuple(face_colors.shape)} {face_colors.dtype}")
+    idx_id = mesh_index_id(faces.dtype)
+    if nv >= 2 ** 31:
+        raise ValueError(f"mesh_ply_pack: {nv} vertices; the file's indices are 32-bit: need fewer than 2^31")
+    vertices, faces, face_colors = vertices.contiguous(), faces.contiguous(), face_colors.contiguous()
+    out = torch.empty(nv * 3 + nf * 4, dtype=torch.int32, device=vertices.device)
+    with torch.cuda.device(vertices.device):
+        check(_lib.lib().f3r_mesh_ply_pack(ptr(vertices) if nv else None, nv, ptr(faces) if nf else None, ptr(face_colors) if nf else None, nf,
+                                           idx_id, ptr(out), stream_ptr()), "f3r_mesh_ply_pack")
+    return out.view(torch.uint8)

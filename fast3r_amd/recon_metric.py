@@ -14,14 +14,6 @@ from . import _lib
 from ._lib import check, ptr, stream_ptr, work_device
 
 
-def _lib_recon():
-    l = _lib.lib()
-    if l.f3r_version() < _lib.RECON_ABI_VERSION:
-        raise _lib.F3RError(f"{_lib.LIB_PATH} is version {l.f3r_version()}; the reconstruction metrics need >= {_lib.RECON_ABI_VERSION}: "
-                            "rebuild it (fast3r_amd/csrc/build.sh)")
-    return l
-
-
 def _points(x, dev, what):
     """(n, 3) fp32 contiguous on `dev`.  fp64 inputs are rounded to fp32 coordinates (the reference's flow only holds fp32 values)."""
     t = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
@@ -51,7 +43,7 @@ class NNIndex:
     def __init__(self, points):
         self.points = points
         self.m = points.shape[0]
-        l = _lib_recon()
+        l = _lib.lib()
         nb = l.f3r_nn_index_bytes(self.m)
         self.buf = torch.empty((nb + 15) // 16 * 4, dtype=torch.float32, device=points.device)
         ws = _workspace(l.f3r_nn_workspace_bytes(self.m), points.device)
@@ -60,7 +52,7 @@ class NNIndex:
 
     def query(self, q):
         """(dist fp64 [n], idx int64 [n]) of the nearest indexed point of every row of q ((n, 3) fp32 on the same device)."""
-        l = _lib_recon()
+        l = _lib.lib()
         n = q.shape[0]
         dist = torch.empty(n, dtype=torch.float64, device=q.device)
         idx = torch.empty(n, dtype=torch.int32, device=q.device)
@@ -71,7 +63,7 @@ class NNIndex:
 
     def knn(self, k=30, normals=True, neighbours=False):
         """Normals [m, 3] fp64 and / or the min(k, m) nearest indexed points of every indexed point ((idx int32, dist fp64) [m, k'])."""
-        l = _lib_recon()
+        l = _lib.lib()
         kk = min(k, self.m)
         dev = self.points.device
         nrm = torch.empty((self.m, 3), dtype=torch.float64, device=dev) if normals else None
@@ -109,7 +101,7 @@ def estimate_normals(points, knn=30):
 
 def _stats(dist, idx, nq, ndb, dist_th=0.0):
     m_db = 0 if ndb is None else ndb.shape[0]
-    l = _lib_recon()
+    l = _lib.lib()
     n = dist.shape[0]
     if n == 0:
         nq = ndb = None  # empty queries: NaN statistics (empty tensors carry no device address)
@@ -196,7 +188,7 @@ def reconstruction_metrics(views, preds, min_conf_thr_percentile_for_local_align
     L = sum(sizes[:V])
     q_metric = float(min_conf_thr_percentile_for_metric_cacluation) / 100.0
     q_icp = float(min_conf_thr_percentile_for_local_alignment_and_icp) / 100.0
-    l = _lib_recon()
+    l = _lib.lib()
     pred_out = torch.empty((B * L, 3), dtype=torch.float32, device=dev)
     gt_out = torch.empty((B * L, 3), dtype=torch.float32, device=dev)
     counts = torch.empty((2, B), dtype=torch.int32, device=dev)

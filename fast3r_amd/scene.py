@@ -22,7 +22,8 @@ import struct
 import numpy as np
 import torch
 
-from . import ops
+from . import post_ops
+from ._frontend import check_inputs, fp32_on, on_work_device, preds_and_views, read_back
 from ._lib import work_device
 
 TURBO_LUT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "turbo_lut_u8.bin")
@@ -175,7 +176,7 @@ class Scene:
                     consts.append(None)
         if not pts:
             return None, None
-        return ops.scene_collect(pts, cols, masks, nums, consts)
+        return post_ops.scene_collect(pts, cols, masks, nums, consts)
 
     def save_ply(self, path, **kwargs):
         """collect_points(**kwargs) -> save_ply; returns the number of points written (0: nothing visible, no file)"""
@@ -186,60 +187,16 @@ class Scene:
         return p.shape[0]
 
 
-def _check_inputs(preds, views, sample, not_sky, *, what="assemble_scene", keys=None, mask_name="not_sky"):
-    """the input checks of assemble_scene; build_mesh (fast3r_amd/mesh.py) runs the same ones under its own name, with the keys of the head
-    it reads (`keys`) and its `valid` masks in the place of `not_sky`"""
-    if len(preds) == 0 or len(views) != len(preds):
-        raise ValueError(f"{what}: need one view per pred and at least one (got {len(preds)} preds, {len(views)} views)")
-    for i, pred in enumerate(preds):
-        if keys is None and "pts3d_local_aligned_to_global" not in pred:
-            raise KeyError(f"'pts3d_local_aligned_to_global' not in preds[{i}]: call align_local_pts3d_to_global(preds, views) first")
-        for key in ("pts3d_in_other_view", "conf", "conf_local") if keys is None else keys:
-            if key not in pred:
-                raise KeyError(f"'{key}' not in preds[{i}]")
-        if "img" not in views[i]:
-            raise KeyError(f"'img' not in views[{i}]")
-    B = preds[0]["conf" if keys is None else keys[1]].shape[0]
-    if not 0 <= sample < B:
-        raise ValueError(f"{what}: sample = {sample} outside [0, {B})")
-    if isinstance(not_sky, str):
-        if not_sky != "detect":
-            raise ValueError(f"{what}: {mask_name} = {not_sky!r}; accepted values are None (no sky anywhere), 'detect' (detect_sky_masks "
-                             "on the views' images) or a list of per-view (H, W) masks")
-    elif not_sky is not None:
-        if len(not_sky) != len(preds):
-            raise ValueError(f"{what}: {mask_name} has {len(not_sky)} masks for {len(preds)} views")
-        for i, m in enumerate(not_sky):
-            m = torch.as_tensor(m)
-            hw = tuple(preds[i]["conf" if keys is None else keys[1]].shape[1:3])
-            if tuple(m.shape) != hw:
-                raise ValueError(f"{what}: {mask_name}[{i}] has shape {tuple(m.shape)}; view {i} is {hw}")
-            if m.dtype not in (torch.bool, torch.int8, torch.uint8):
-                raise ValueError(f"{what}: {mask_name}[{i}] must be bool or int8, got {m.dtype}")
-
-
 def assemble_scene(output_or_preds, views=None, *, sample=0, not_sky=None, global_conf_thr_value_to_drop_view=1.5, niter_PnP=100, poses=True):
     """Everything `start_visualization` prepares before it draws (viser_visualizer.py:279-282, :343-427).  Takes what `inference()` returns
     ({'preds', 'views'}, host tensors: uploaded here) or (preds, views) with device tensors; views may differ in H x W; `sample` selects
     the batch row.  `not_sky`: None (no sky anywhere), a list of per-view (H, W) bool / int8 masks, nonzero = keep (what `detect_sky_mask`
     returns), or "detect": run fast3r_amd.sky's batched detection on the images already on the device and proceed as if given those masks.
     Results stay on the device."""
-    if isinstance(output_or_preds, dict):
-        preds = output_or_preds["preds"]
-        views = output_or_preds["views"] if views is None else views
-    else:
-        preds = output_or_preds
-    if views is None:
-        raise ValueError("assemble_scene: views are needed for the image colours")
-    _check_inputs(preds, views, sample, not_sky)
+    preds, views = preds_and_views(output_or_preds, views, "assemble_scene", "image colours")
+    check_inputs(preds, views, sample, not_sky, what="assemble_scene")
     V = len(preds)
     dev = work_device(preds[0]["conf"], "preds")
-
-    def flat(t, tail):
-        t = t[sample]
-        if t.device != dev or t.dtype != torch.float32:
-            t = t.to(dev, torch.float32)
-        return t.reshape(tail)   # ops.scene_sort makes a non-contiguous one contiguous
 
     def mask_of(m):
         m = torch.as_tensor(m)
@@ -260,19 +217,19 @@ def assemble_scene(output_or_preds, views=None, *, sample=0, not_sky=None, globa
                 shapes.append((int(H), int(W)))
                 if tuple(view["img"].shape[1:]) != (3, H, W):
                     raise ValueError(f"assemble_scene: views[{i}]['img'] is {tuple(view['img'].shape)}; expected (B, 3, {H}, {W})")
-                img.append(flat(view["img"], (3, H * W)))   # the (3, H, W) planes as stored: nothing is permuted
+                img.append(fp32_on(view["img"][sample], dev, (3, H * W)))   # the (3, H, W) planes as stored: nothing is permuted
                 mask.append(None if (not_sky is None or detect) else mask_of(not_sky[i]))
-                conf.append(flat(pred["conf"], (H * W,)))
-                pts.append(flat(pred["pts3d_in_other_view"], (H * W, 3)))
+                conf.append(fp32_on(pred["conf"][sample], dev, (H * W,)))
+                pts.append(fp32_on(pred["pts3d_in_other_view"][sample], dev, (H * W, 3)))
             else:
                 if detect and i == 0:   # every view's planes are on the device now: one batched detection, no host synchronisation
                     from .sky import detect_sky_planes
                     mask[:V] = [m.reshape(-1) for m in detect_sky_planes(img[:V], shapes)[0]]
                 img.append(img[i])
                 mask.append(mask[i])
-                conf.append(flat(pred["conf_local"], (H * W,)))
-                pts.append(flat(pred["pts3d_local_aligned_to_global"], (H * W, 3)))
-    out = ops.scene_sort(conf, pts, img, mask, _lut_on(dev))
+                conf.append(fp32_on(pred["conf_local"][sample], dev, (H * W,)))
+                pts.append(fp32_on(pred["pts3d_local_aligned_to_global"][sample], dev, (H * W, 3)))
+    out = post_ops.scene_sort(conf, pts, img, mask, _lut_on(dev))
     offs = out["offsets"] + [out["order"].shape[0]]
     n_global = offs[V]
 
@@ -281,7 +238,7 @@ def assemble_scene(output_or_preds, views=None, *, sample=0, not_sky=None, globa
     hi_prev, hi_next, hi_gamma = percentile_indexes(n_global, EXTENT_PERCENTILE)
     ranks = sorted({lo_prev, lo_next, hi_prev, hi_next})
     ranks4 = (ranks + [ranks[-1]] * 4)[:4]
-    ext_dev = ops.scene_extent_stats(out["pts"][:n_global], ranks4)
+    ext_dev = post_ops.scene_extent_stats(out["pts"][:n_global], ranks4)
 
     poses_dev = focals_dev = None
     if poses:
@@ -338,14 +295,6 @@ def ply_header(n):
     return "\n".join(lines).encode("ascii") + b"\n"
 
 
-def _to_device(x, name):
-    if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not torch.is_tensor(x):
-        raise ValueError(f"generate_ply_bytes: {name} must be a torch tensor or a numpy array, got {type(x).__name__}")
-    return x.to(work_device(x, name))
-
-
 def colors_to_uint8(colors):
     """`safe_color_conversion` (viser_visualizer.py:205-226) on the device: uint8 passes through; float32 / float64 take one of the three
     range rules, evaluated in the input's own dtype.  ValueError where the reference would divide by zero (rule 3 on a constant input)
@@ -354,20 +303,20 @@ def colors_to_uint8(colors):
         return colors
     if colors.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"generate_ply_bytes: colors must be uint8, float32 or float64, got {colors.dtype}")
-    kmin, kmax, n_nan = (int(x) & 0xffffffffffffffff for x in ops.color_range(colors).cpu().tolist())
+    kmin, kmax, n_nan = (int(x) & 0xffffffffffffffff for x in post_ops.color_range(colors).cpu().tolist())
     if n_nan:
         raise ValueError("generate_ply_bytes: colors contain NaN")
     lo, hi = _double_of_key(kmin), _double_of_key(kmax)
     rule = color_rule(lo, hi)
     if rule == 2 and hi == lo:
         raise ValueError(f"generate_ply_bytes: constant colors {lo} outside [-1, 1]: the reference's linear scaling divides by zero")
-    return ops.color_to_u8(colors, rule, lo, hi)
+    return post_ops.color_to_u8(colors, rule, lo, hi)
 
 
 def generate_ply_bytes(points, colors):
     """The reference's binary PLY (`generate_ply_bytes`, :228-254): its header, then 15-byte little-endian records, packed on the device
     and brought back with one copy through pinned memory.  points (M, 3); colors (M, 3) uint8 or float32 / float64; torch or numpy."""
-    points, colors = _to_device(points, "points"), _to_device(colors, "colors")
+    points, colors = (on_work_device(x, "generate_ply_bytes", name)[0] for x, name in ((points, "points"), (colors, "colors")))
     n = points.shape[0]
     if points.dim() != 2 or points.shape[1] != 3 or tuple(colors.shape) != (n, 3):
         raise ValueError(f"generate_ply_bytes: points (M, 3) and colors (M, 3), got {tuple(points.shape)} and {tuple(colors.shape)}")
@@ -376,11 +325,8 @@ def generate_ply_bytes(points, colors):
     header = ply_header(n)
     if n == 0:
         return header
-    rec = ops.ply_pack(points.to(torch.float32), colors_to_uint8(colors))
-    host = torch.empty(rec.shape[0], dtype=torch.uint8, pin_memory=True)
-    host.copy_(rec, non_blocking=True)
-    torch.cuda.current_stream(rec.device).synchronize()
-    return header + host.numpy().tobytes()
+    rec = post_ops.ply_pack(points.to(torch.float32), colors_to_uint8(colors))
+    return header + read_back(rec)
 
 
 def save_ply(path, points, colors):

@@ -13,10 +13,10 @@ The reference's quirks are kept: the 8-bit conversion is `
 when no component touches row 0 the mask stays as it is.  Deviations: values outside [-1, 1] saturate where the reference's uint8 cast
 wraps, and NaN reads as 0 (as in `assemble_scene`).
 """
-import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, post_ops
+from ._frontend import as_tensor, fp32_on
 from ._lib import work_device
 
 STAT_NAMES = ("sky_pixels", "components", "components_top", "components_kept", "branch")
@@ -24,17 +24,9 @@ BRANCH_NAMES = {_lib.F3R_SKY_EMPTY: "empty", _lib.F3R_SKY_NO_TOP: "no_top", _lib
 _ALL = _lib.F3R_SKY_CLASSIFY | _lib.F3R_SKY_MORPH | _lib.F3R_SKY_LABEL
 
 
-def _as_tensor(x, name):
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x)), True
-    if not torch.is_tensor(x):
-        raise ValueError(f"{name} must be a torch tensor or a numpy array, got {type(x).__name__}")
-    return x, False
-
-
 def _bitmap_on_device(mask, name):
     """(H, W) bool / int8 / uint8 -> int8 on the work device (nonzero = set), the caller's device, and whether it was numpy"""
-    m, was_numpy = _as_tensor(mask, name)
+    m, was_numpy = as_tensor(mask, name)
     if m.dim() != 2 or m.dtype not in (torch.bool, torch.int8, torch.uint8):
         raise ValueError(f"{name} must be an (H, W) bool or int8 bitmap, got {tuple(m.shape)} {m.dtype}")
     home = m.device
@@ -50,18 +42,10 @@ def _give_back(t, home, was_numpy):
 
 def unpack_bits(words, H, W):
     """the (H, W) bool image of H * ceil(W / 64) bitmap words (int64 tensor, include/f3r.h f3r_sky_detect); for tests and debugging"""
-    WW = ops.sky_row_words(W)
+    WW = post_ops.sky_row_words(W)
     shifts = torch.arange(64, device=words.device, dtype=torch.int64)
     bits = (words.reshape(H, WW, 1) >> shifts) & 1
     return bits.reshape(H, WW * 64)[:, :W].to(torch.bool)
-
-
-def _planes(img_chw, dev):
-    """(3, H, W) -> the fp32 planes (3, H * W) on dev, as stored: nothing is permuted"""
-    t = img_chw
-    if t.device != dev or t.dtype != torch.float32:
-        t = t.to(dev, torch.float32)
-    return t.reshape(3, -1)
 
 
 def stats_dicts(stats):
@@ -77,7 +61,7 @@ def stats_dicts(stats):
 def detect_sky_planes(planes, shapes):
     """all views at once from their (3, H * W) fp32 device planes -> (list of (H, W) int8 device tensors, (V, 5) int32 device stats).
     No host synchronisation: `assemble_scene(not_sky="detect")` calls this."""
-    out = ops.sky_detect(planes, shapes, _ALL)
+    out = post_ops.sky_detect(planes, shapes, _ALL)
     return out["not_sky"], out["stats"]
 
 
@@ -101,7 +85,7 @@ def detect_sky_masks(views, sample=0):
         if dev is None:
             dev = work_device(img, "views")
         shapes.append((int(img.shape[2]), int(img.shape[3])))
-        planes.append(_planes(img[sample], dev))
+        planes.append(fp32_on(img[sample], dev, (3, -1)))   # the (3, H, W) planes as stored: nothing is permuted
     masks, stats = detect_sky_planes(planes, shapes)
     return masks, stats_dicts(stats)
 
@@ -109,7 +93,7 @@ def detect_sky_masks(views, sample=0):
 def detect_sky_mask(img_rgb):
     """The reference's `detect_sky_mask`: img_rgb (H, W, 3) in [-1, 1], numpy or torch, host or device -> (H, W) int8, 1 = not sky: a
     numpy array for numpy input, otherwise a tensor on the input's device."""
-    t, was_numpy = _as_tensor(img_rgb, "detect_sky_mask: img_rgb")
+    t, was_numpy = as_tensor(img_rgb, "detect_sky_mask: img_rgb")
     if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
         raise ValueError(f"detect_sky_mask: img_rgb must be (H, W, 3), got {tuple(t.shape)}")
     if t.dtype != torch.float32:   # the reference does `(img + 1) * 127.5` in the array's own type: only fp32 is reproduced here
@@ -127,7 +111,7 @@ def label_components(mask):
     a set pixel the smallest pixel index y * W + x of its component, -1 for the background (numpy for numpy input, otherwise a tensor on
     the input's device); count = the number of components."""
     m, home, was_numpy = _bitmap_on_device(mask, "label_components: mask")
-    out = ops.sky_detect([m], [tuple(m.shape)], _lib.F3R_SKY_LABEL, want_not_sky=False, want_roots=True)
+    out = post_ops.sky_detect([m], [tuple(m.shape)], _lib.F3R_SKY_LABEL, want_not_sky=False, want_roots=True)
     count = int(out["stats"][0, 1].item())
     return _give_back(out["roots"][0], home, was_numpy), count
 
@@ -136,19 +120,19 @@ def morphology(mask):
     """step 4 alone (dilate 7 x 7, open 7 x 7, pixels outside the image ignored) on an (H, W) bitmap -> (H, W) bool"""
     m, home, was_numpy = _bitmap_on_device(mask, "morphology: mask")
     H, W = m.shape
-    out = ops.sky_detect([m], [(H, W)], _lib.F3R_SKY_MORPH)
+    out = post_ops.sky_detect([m], [(H, W)], _lib.F3R_SKY_MORPH)
     return _give_back(unpack_bits(out["bits"], H, W), home, was_numpy)
 
 
 def classify(img_chw, bits=False):
     """steps 1-3 alone on a (3, H, W) image in [-1, 1] -> the (H, W) bool bitmap of sky-coloured pixels before any morphology (or, with
     bits=True, its H * ceil(W / 64) packed words as an int64 device tensor)"""
-    t, was_numpy = _as_tensor(img_chw, "classify: img")
+    t, was_numpy = as_tensor(img_chw, "classify: img")
     if t.dim() != 3 or t.shape[0] != 3:
         raise ValueError(f"classify: img must be (3, H, W), got {tuple(t.shape)}")
     home = t.device
     H, W = int(t.shape[1]), int(t.shape[2])
-    out = ops.sky_detect([_planes(t, work_device(t, "img"))], [(H, W)], _lib.F3R_SKY_CLASSIFY)
+    out = post_ops.sky_detect([fp32_on(t, work_device(t, "img"), (3, -1))], [(H, W)], _lib.F3R_SKY_CLASSIFY)
     if bits:
         return out["bits"]
     return _give_back(unpack_bits(out["bits"], H, W), home, was_numpy)

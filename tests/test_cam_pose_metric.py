@@ -35,8 +35,7 @@ def test_pose_metric_symbols_are_declared_exported_and_bound(built_lib):
     for name in ("f3r_pose_pair_metrics", "f3r_pose_error_stats"):
         assert re.search(r"\b%s\s*\(" % name, src), f"{name} not declared in include/f3r.h"
         assert hasattr(built_lib, name) and name in _lib.SYMBOLS
-    assert built_lib.f3r_version() >= 370 and _lib.POSE_METRIC_ABI_VERSION == 370
-    assert _lib.ABI_VERSION == 350
+    assert built_lib.f3r_version() >= 370 and _lib.ABI_VERSION >= 370
     import fast3r_amd
     for name in ("camera_to_rel_deg", "calculate_auc", "camera_pose_metrics"):
         assert callable(getattr(fast3r_amd, name))

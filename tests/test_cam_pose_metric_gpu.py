@@ -41,8 +41,8 @@ def metrics(pred, gt):
 
 
 def counts_of(pred, gt, want_pairs=False):
-    from fast3r_amd import ops
-    return ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD), want_pairs=want_pairs)
+    from fast3r_amd import post_ops
+    return post_ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD), want_pairs=want_pairs)
 
 
 def assert_dict_equals_golden(res, ref, what):
@@ -92,7 +92,7 @@ def test_counts_and_metrics_equal_the_goldens_bit_for_bit(built_lib, golden, nam
 
 
 def test_v1500_counts_only_equals_counts_of_own_pairs_and_pair_order(built_lib):
-    from fast3r_amd import ops
+    from fast3r_amd import post_ops
     V = 1500
     pred, gt = C.pose_set(*C.POSE_SETS["v1500"])
     p, g = pred.cuda()[None], gt.cuda()[None]
@@ -106,7 +106,7 @@ def test_v1500_counts_only_equals_counts_of_own_pairs_and_pair_order(built_lib):
     assert rel_r.shape == (1, V * (V - 1) // 2)
     # fp32 per-pair output rounds the fp64 errors, so the recount runs on the fp64 input's own pairs
     c64, r64, t64 = counts_of(p.double(), g.double(), want_pairs=True)
-    recount = ops.pose_error_stats(r64[0], t64[0], C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD))
+    recount = post_ops.pose_error_stats(r64[0], t64[0], C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD))
     assert torch.equal(c64, counts) and torch.equal(recount[:-2], counts[0, :-2])
     r_cpu, t_cpu = r64[0].cpu(), t64[0].cpu()
     host = [int((r_cpu < tau).sum()) for tau in C.RRA_THRESHOLDS] + [int((t_cpu < tau).sum()) for tau in C.RTA_THRESHOLDS]

@@ -367,6 +367,40 @@ def test_a_missing_or_stale_library_fails_loudly(tmp_path, monkeypatch):
         _lib.lib()
 
 
+def test_an_older_library_is_told_to_rebuild_before_any_other_symbol_is_bound(tmp_path, monkeypatch):
+    """A library of an earlier ABI lacks the later entry points: lib() must read f3r_version first and say "rebuild it", not die binding a
+    symbol that library never had (AttributeError)."""
+    import subprocess
+    from fast3r_amd import _lib
+    src, so = tmp_path / "stub.c", tmp_path / "libf3r_hip.so"
+    src.write_text("int f3r_version(void) { return 350; }\n")
+    subprocess.run(["gcc", "-shared", "-fPIC", str(src), "-o", str(so)], check=True)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "LIB_PATH", str(so))
+    with pytest.raises(F3RError, match="version 350.*rebuild"):
+        _lib.lib()
+    assert _lib._lib is None
+
+
+def test_tile_starts_and_table_words():
+    """post_ops.tile_starts / table_words: the running tile counts and the int64 words of a per-view device table (include/f3r.h: rows, then
+    the lists of n + 1 tile starts), as the sort, collect, sky and mesh wrappers upload them"""
+    from fast3r_amd import _lib, post_ops
+    for T in (_lib.SKY_PIX_TILE, _lib.SKY_WORD_TILE, _lib.COLLECT_TILE, _lib.MESH_TILE, _lib.SCENE_TILE):
+        assert post_ops.tile_starts([1, T, T + 1], T) == [0, 1, 2, 4]
+        assert post_ops.tile_starts([T - 1, 2 * T, 2 * T + 1], T) == [0, 1, 3, 6]
+    assert post_ops.tile_starts([], 16) == [0]
+    T = _lib.MESH_TILE
+    H, W = 1, 7   # a view of one row: no quads, and still one quad tile (f3r_mesh_count launches at least one workgroup per view)
+    assert post_ops.tile_starts([(H - 1) * (W - 1)], T, at_least_one=True) == [0, 1]
+    assert post_ops.tile_starts([(H - 1) * (W - 1)], T) == [0, 0]
+    assert post_ops.tile_starts([0, T + 1, 1], T, at_least_one=True) == [0, 1, 3, 4]
+    table = post_ops.table_words([[11, 12, 13], [21, 22, 23]], [0, 1, 3], [0, 2, 5])
+    assert table.dtype == torch.int64 and table.device.type == "cpu"
+    assert table.tolist() == [11, 12, 13, 21, 22, 23, 0, 1, 3, 0, 2, 5]
+    assert post_ops.table_words([[2 ** 62, -1]], [0, 1]).tolist() == [2 ** 62, -1, 0, 1]   # pointers are full 64-bit words
+
+
 def test_fp8_low_plane_weight_pack_on_cpu():
     """ops.pack_linear_weight_f8 (f3r.h F3R_SPLIT_W2F8): rows [K fp16 hi | K fp8 e4m3((W - hi) 2^s_n)] + one E8M0 word per output channel; decoding the
     planes recovers the weight ~16x closer than one fp16 plane, whatever the row's scale; no NaN code is ever produced"""

@@ -30,8 +30,7 @@ def test_loss_symbols_are_declared_exported_and_bound(built_lib):
     for name in NAMES:
         assert re.search(r"\b%s\s*\(" % name, src), f"{name} not declared in include/f3r.h"
         assert hasattr(built_lib, name) and name in _lib.SYMBOLS
-    assert built_lib.f3r_version() >= 380 and _lib.LOSS_ABI_VERSION == 380
-    assert _lib.ABI_VERSION == 350
+    assert built_lib.f3r_version() >= 380 and _lib.ABI_VERSION >= 380
     for doc in ("INTEGRATION.md", "DESIGN.md"):
         assert "f3r_mv_conf_loss" in open(os.path.join(ROOT, doc)).read(), doc
     import fast3r_amd

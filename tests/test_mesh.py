@@ -163,7 +163,7 @@ def test_ply_round_trip_on_restated_data():
 
 def test_library_exports_the_mesh_entry_points(built_lib):
     from fast3r_amd import _lib
-    assert _lib.MESH_ABI_VERSION == 410 and _lib.ABI_VERSION == 350
+    assert _lib.ABI_VERSION >= 410
     assert built_lib.f3r_version() >= 410
     for n in ("f3r_mesh_workspace_bytes", "f3r_mesh_threshold", "f3r_mesh_count", "f3r_mesh_write", "f3r_mesh_ply_pack"):
         assert hasattr(built_lib, n) and n in _lib.SYMBOLS, n

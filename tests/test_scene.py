@@ -136,7 +136,7 @@ def test_rgb_round_trip_is_the_identity():
 
 def test_library_exports_the_scene_entry_points(built_lib):
     from fast3r_amd import _lib
-    assert _lib.SCENE_ABI_VERSION == 390 and _lib.ABI_VERSION == 350
+    assert _lib.ABI_VERSION >= 390
     assert built_lib.f3r_version() >= 390
     for n in ("f3r_scene_sort", "f3r_scene_sort_workspace_bytes", "f3r_scene_extent", "f3r_scene_extent_workspace_bytes",
               "f3r_scene_collect_count", "f3r_scene_collect_write", "f3r_ply_pack", "f3r_color_range", "f3r_color_to_u8"):

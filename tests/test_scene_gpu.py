@@ -166,10 +166,10 @@ def boundary_segments(lengths, seed):
 def test_scene_sort_at_wave_and_tile_boundaries(built_lib):
     """segments of one key, of a wave's 64 keys and a tile's 4096 keys, and one short and one over each, in one call"""
     import fast3r_amd
-    from fast3r_amd import ops
+    from fast3r_amd import post_ops
     lengths = [1, 63, 64, 65, 4095, 4096, 4097]
     conf, pts, img, mask = boundary_segments(lengths, 91)
-    out = ops.scene_sort(conf, pts, img, mask, torch.from_numpy(fast3r_amd.scene.turbo_lut_u8()).cuda())
+    out = post_ops.scene_sort(conf, pts, img, mask, torch.from_numpy(fast3r_amd.scene.turbo_lut_u8()).cuda())
     assert out["offsets"] == [sum(lengths[:s]) for s in range(len(lengths))] and out["order"].shape[0] == sum(lengths)
     for s, L in enumerate(lengths):
         sl = slice(out["offsets"][s], out["offsets"][s] + L)
@@ -184,15 +184,15 @@ def test_scene_sort_at_wave_and_tile_boundaries(built_lib):
 def test_scene_collect_at_wave_and_tile_boundaries(built_lib):
     """prefixes of one entry, of a wave's 64 and a collect tile's 1024 entries, and one short and one over each, over sorted segments"""
     import fast3r_amd
-    from fast3r_amd import ops
+    from fast3r_amd import post_ops
     nums = [1, 63, 64, 65, 1023, 1024, 1025]
     conf, pts, img, mask = boundary_segments([1100] * len(nums), 92)
-    out = ops.scene_sort(conf, pts, img, mask, torch.from_numpy(fast3r_amd.scene.turbo_lut_u8()).cuda())
+    out = post_ops.scene_sort(conf, pts, img, mask, torch.from_numpy(fast3r_amd.scene.turbo_lut_u8()).cuda())
     seg = [slice(o, o + 1100) for o in out["offsets"]]
     spts = [out["pts"][sl].contiguous() for sl in seg]
     srgb = [out["rgb"][sl].contiguous() for sl in seg]
     smask = [out["mask"][sl].contiguous() if mask[s] is not None else None for s, sl in enumerate(seg)]
-    p, c = ops.scene_collect(spts, srgb, smask, nums, [None] * len(nums))
+    p, c = post_ops.scene_collect(spts, srgb, smask, nums, [None] * len(nums))
     want_p, want_c = [], []
     for s, n in enumerate(nums):
         k = smask[s][:n] > 0 if smask[s] is not None else torch.ones(n, dtype=torch.bool, device="cuda")

@@ -8,7 +8,7 @@ import torch
 
 import sky_cases as C
 import sky_ref as R
-from fast3r_amd import _lib, assemble_scene, detect_sky_mask, detect_sky_masks, generate_ply_bytes, label_components, ops, sky
+from fast3r_amd import _lib, assemble_scene, detect_sky_mask, detect_sky_masks, generate_ply_bytes, label_components, post_ops, sky
 
 pytestmark = pytest.mark.gpu
 GOLDEN_KEYS = ("sky_pixels", "components", "components_top", "components_kept")
@@ -61,7 +61,7 @@ def test_all_colours_above_and_below_the_upper_region(built_lib):
     for roll in rolls:
         c = torch.roll(col_d, -roll, 0).reshape(-1)   # row y shows colour row (y + roll) % N
         planes.append(torch.stack([lut_d[(c >> 16) & 255], lut_d[(c >> 8) & 255], lut_d[c & 255]]))
-    out = ops.sky_detect(planes, [(N, N)] * 3, _lib.F3R_SKY_CLASSIFY)
+    out = post_ops.sky_detect(planes, [(N, N)] * 3, _lib.F3R_SKY_CLASSIFY)
     n_words = N * N // 64
     seen_up, seen_down = np.zeros(N, bool), np.zeros(N, bool)
     for i, roll in enumerate(rolls):
@@ -81,8 +81,8 @@ def test_imgnorm_values_on_colour_slices(built_lib):
     g, b = np.meshgrid(u, u, indexing="ij")
     slices = [np.stack([np.full_like(g, 100), g, b], -1), np.stack([g, np.full_like(g, 150), b], -1), np.stack([g, b, np.full_like(g, 230)], -1)]
     imgs = [C.normalise(s) for s in slices]
-    out = ops.sky_detect([torch.from_numpy(i).permute(2, 0, 1).reshape(3, -1).contiguous().cuda() for i in imgs], [(256, 256)] * 3,
-                         _lib.F3R_SKY_CLASSIFY)
+    out = post_ops.sky_detect([torch.from_numpy(i).permute(2, 0, 1).reshape(3, -1).contiguous().cuda() for i in imgs], [(256, 256)] * 3,
+                              _lib.F3R_SKY_CLASSIFY)
     for i, img in enumerate(imgs):
         got = sky.unpack_bits(out["bits"][i * 1024:(i + 1) * 1024], 256, 256).cpu().numpy()
         want = R.classify(img)
@@ -120,7 +120,7 @@ def _morph_cases():
 
 def test_morphology_alone_on_word_and_tile_borders(built_lib):
     cases = _morph_cases()
-    out = ops.sky_detect([torch.from_numpy(m.astype(np.int8)).cuda() for m in cases], [m.shape for m in cases], _lib.F3R_SKY_MORPH)
+    out = post_ops.sky_detect([torch.from_numpy(m.astype(np.int8)).cuda() for m in cases], [m.shape for m in cases], _lib.F3R_SKY_MORPH)
     offs = out["word_offsets"] + [out["bits"].numel()]
     n_changed = 0
     for i, m in enumerate(cases):
@@ -143,7 +143,7 @@ def test_components_alone_on_bitmaps_morphology_never_emits(built_lib):
     cases = _label_cases()
     names = list(cases)
     src = [torch.from_numpy(cases[n].astype(np.int8)).cuda() for n in names]
-    out = ops.sky_detect(src, [cases[n].shape for n in names], _lib.F3R_SKY_LABEL, want_not_sky=True, want_roots=True)
+    out = post_ops.sky_detect(src, [cases[n].shape for n in names], _lib.F3R_SKY_LABEL, want_not_sky=True, want_roots=True)
     stats = sky.stats_dicts(out["stats"])
     for i, n in enumerate(names):
         m = cases[n]

@@ -10,7 +10,7 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-from fast3r_amd import _lib, ops  # noqa: E402
+from fast3r_amd import _lib, ops, post_ops  # noqa: E402
 
 DEV = "cuda"
 
@@ -438,7 +438,7 @@ def bench_loss(sizes=(100, 320), H=512, W=512, alpha=0.2, out_path="profiles/r08
         eager_ms = wall_ms(lambda: float(eager(views, preds, inverses)), reps=3)
         lists = ([v["pts3d"] for v in views], [v["valid_mask"] for v in views], [v["camera_pose"] for v in views],
                  [p["pts3d_in_other_view"] for p in preds], [p["conf"] for p in preds], [p["pts3d_local"] for p in preds], [p["conf_local"] for p in preds])
-        kernel_ms, kernel_best = time_ms(lambda: ops.mv_conf_loss(*lists, version=4, alpha=alpha), rounds=5, inner=3)
+        kernel_ms, kernel_best = time_ms(lambda: post_ops.mv_conf_loss(*lists, version=4, alpha=alpha), rounds=5, inner=3)
         must_read = 2 * 45 * n * H * W
         rec["sizes"][str(n)] = {"pixels_per_set": n * H * W, "criterion_call_ms": round(crit_ms, 3), "wrapper_and_launches_stream_ms": round(kernel_ms, 3),
                                 "wrapper_and_launches_stream_best_ms": round(kernel_best, 3), "eager_fp32_restatement_ms": round(eager_ms, 3),
@@ -524,7 +524,7 @@ def bench_scene(sizes=(100, 320), H=512, W=512, out_path="profiles/r09_scene_ben
                [v["img"].reshape(3, H * W) for v in views] * 2, [m.reshape(-1) for m in masks] * 2)
         if sort_only:
             for _ in range(3):
-                ops.scene_sort(*seg, lut)
+                post_ops.scene_sort(*seg, lut)
             torch.cuda.synchronize()
             return
         product = lambda: fast3r_amd.assemble_scene(preds, views, not_sky=masks, poses=False)  # noqa: E731
@@ -535,13 +535,13 @@ def bench_scene(sizes=(100, 320), H=512, W=512, out_path="profiles/r09_scene_ben
             tp.append(once_ms(product)[0])
             te.append(once_ms(lambda: eager(preds, views, masks))[0])
             torch.cuda.empty_cache()
-        sort_ms, sort_best = time_ms(lambda: ops.scene_sort(*seg, lut), rounds=5, inner=1)
+        sort_ms, sort_best = time_ms(lambda: post_ops.scene_sort(*seg, lut), rounds=5, inner=1)
         conf_all = torch.stack(seg[0])
         torch_sort_ms, _ = time_ms(lambda: torch.sort(conf_all, dim=1, descending=True, stable=True), rounds=5, inner=1)
         del conf_all
         gpts = torch.cat(seg[1][:n])
         ranks = sorted({k for pct in (20, 80) for k in S.percentile_indexes(gpts.shape[0], pct)[:2]})
-        extent_ms, _ = time_ms(lambda: ops.scene_extent_stats(gpts, (ranks * 4)[:4]), rounds=5, inner=1)
+        extent_ms, _ = time_ms(lambda: post_ops.scene_extent_stats(gpts, (ranks * 4)[:4]), rounds=5, inner=1)
         del gpts
         sc = product()
         tc, tply = [], []
@@ -709,7 +709,7 @@ def bench_sky(sizes=(100, 320), H=512, W=512, out_path="profiles/r10_sky_bench.j
             lab = {}
             for kind, bm in (("spiral", torch.from_numpy(C.spiral(H, W).astype(np.int8)).to(DEV)), ("noise50", None)):
                 src = [bm.clone() if bm is not None else (rnd(H, W) < 0.5).to(torch.int8) for _ in range(n)]
-                label = lambda: ops.sky_detect(src, [(H, W)] * n, _lib.F3R_SKY_LABEL, want_not_sky=True, want_roots=False)  # noqa: E731
+                label = lambda: post_ops.sky_detect(src, [(H, W)] * n, _lib.F3R_SKY_LABEL, want_not_sky=True, want_roots=False)  # noqa: E731
                 once_ms(label)
                 ms, best = time_ms(label, rounds=5, inner=1)
                 lab[kind] = {"label_stream_ms": round(ms, 3), "label_stream_best_ms": round(best, 3),
@@ -760,8 +760,8 @@ def bench_posemetric(sizes=(320, 1500), H=512, W=512, out_path="profiles/r07_pos
     for n in sizes:
         pred, gt = (x.cuda()[None] for x in C.pose_set(n, 0))
         counts_ms = wall_ms(lambda: camera_pose_metrics(pred, gt))
-        pairs_ms = wall_ms(lambda: ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD), want_pairs=True)[0].cpu())
-        kernel_ms, _ = time_ms(lambda: ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD)), rounds=5, inner=10)
+        pairs_ms = wall_ms(lambda: post_ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD), want_pairs=True)[0].cpu())
+        kernel_ms, _ = time_ms(lambda: post_ops.pose_pair_metrics(pred, gt, C.RRA_THRESHOLDS, C.RTA_THRESHOLDS, C.N_BINS, float(C.MAX_THRESHOLD)), rounds=5, inner=10)
         pts = Xw[None].cuda().expand(n, H, W, 3).contiguous()
         conf = conf1[None].cuda().expand(n, H, W).contiguous()
         pnp_ms = wall_ms(lambda: estimate_poses(pts, conf, 400.0), reps=3)
