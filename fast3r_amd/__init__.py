@@ -12,4 +12,5 @@ from .cam_pose_metric import calculate_auc, camera_pose_metrics, camera_to_rel_d
 from .losses import ConfLossMultiviewV2, L21, L21Loss, Regr3DMultiviewV3, Regr3DMultiviewV4  # noqa: F401
 from .scene import Scene, assemble_scene, generate_ply_bytes, save_ply  # noqa: F401
 from .mesh import Mesh, build_mesh, cat_meshes, generate_mesh_ply_bytes, pts3d_to_trimesh, save_mesh_ply  # noqa: F401
+from .cloud import combine_points, downsample_cloud, export_combined_ply, farthest_point_down_sample, voxel_down_sample  # noqa: F401
 from .sky import detect_sky_mask, detect_sky_masks, label_components  # noqa: F401

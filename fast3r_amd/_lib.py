@@ -24,6 +24,10 @@ F3R_SKY_EMPTY, F3R_SKY_NO_TOP, F3R_SKY_TOP = 0, 1, 2
 SKY_PIX_TILE, SKY_WORD_TILE = 16, 256  # F3R_SKY_PIX_TILE, F3R_SKY_WORD_TILE: words per workgroup of the two kinds of sky kernel
 MESH_TILE = 1024  # F3R_MESH_TILE: pixels, or quads, per workgroup of the mesh kernels
 F3R_INDEX_I32, F3R_INDEX_I64 = 0, 1
+# F3R_CLOUD_TILE: pixels per workgroup of the combine kernels; F3R_CLOUD_SORT_TILE: keys per workgroup of the voxel sort; F3R_CLOUD_FPS_TILE:
+# points per tile of the tiled farthest-point path; F3R_CLOUD_FPS_ONE_MAX: the most points its one-workgroup path takes
+CLOUD_TILE, CLOUD_SORT_TILE, CLOUD_FPS_TILE, CLOUD_FPS_ONE_MAX = 1024, 2048, 1024, 8192
+F3R_FPS_AUTO, F3R_FPS_ONE, F3R_FPS_TILED = 0, 1, 2
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
 
@@ -168,7 +172,22 @@ SYMBOLS = {
     "f3r_mesh_write": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_vp, _c_vp, _c_vp]),
     "f3r_mesh_ply_pack": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp, _c_vp]),
+    "f3r_cloud_combine_count": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "f3r_cloud_combine_write": (ctypes.c_int, [_c_vp, ctypes.c_int, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_vp, _c_vp, _c_vp]),
+    "f3r_cloud_bounds": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp]),
+    "f3r_cloud_voxel_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "f3r_cloud_voxel_sort": (ctypes.c_int, [_c_vp, _c_i64, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.POINTER(ctypes.c_int), _c_vp,
+                                            ctypes.c_size_t, _c_vp, _c_vp]),
+    "f3r_cloud_voxel_sums": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_vp, ctypes.c_size_t, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "f3r_cloud_fps_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "f3r_cloud_fps": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_vp]),
+    "f3r_cloud_mark": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "f3r_cloud_gather": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
 }
+
+# entry points added after ABI_VERSION: {symbol: the f3r_version() that first exports it}.  lib() binds one only when the loaded library
+# reports that version; entry() is the one place that tells a caller of a later symbol to rebuild an older library.
+SYMBOL_SINCE = {name: 420 for name in SYMBOLS if name.startswith("f3r_cloud_")}
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")
 if os.environ.get("F3R_LAB_LIB"):  # measurement builds only (tools/lab: kernels with ablation bits); never set by the product or the tests
@@ -180,7 +199,7 @@ class F3RError(RuntimeError):
     pass
 
 
-ABI_VERSION = 410  # f3r_version() of include/f3r.h this file mirrors: lib() accepts no older library
+ABI_VERSION = 410  # the oldest f3r_version() lib() accepts; entry points of a later version are listed in SYMBOL_SINCE and reached through entry()
 
 
 def lib():
@@ -200,13 +219,27 @@ def lib():
         if l.f3r_version() < ABI_VERSION:
             raise F3RError(f"{LIB_PATH} is version {l.f3r_version()}, this host code needs >= {ABI_VERSION}: rebuild it (fast3r_amd/csrc/build.sh)")
         for name in SYMBOLS:
-            bind(name)
+            if SYMBOL_SINCE.get(name, 0) <= l.f3r_version():
+                bind(name)
         if l.f3r_sizeof(0) != ctypes.sizeof(GemmArgs) or l.f3r_sizeof(1) != ctypes.sizeof(AttnArgs) or l.f3r_sizeof(2) != ctypes.sizeof(AttnF32Args):
             raise F3RError("fast3r_amd/_lib.py struct layout does not match include/f3r.h "
                            f"(gemm {l.f3r_sizeof(0)} vs {ctypes.sizeof(GemmArgs)}, attn {l.f3r_sizeof(1)} vs {ctypes.sizeof(AttnArgs)}, "
                            f"attn_f32 {l.f3r_sizeof(2)} vs {ctypes.sizeof(AttnF32Args)}): rebuild the library (fast3r_amd/csrc/build.sh)")
         _lib = l
     return _lib
+
+
+def library_version() -> int:
+    return lib().f3r_version()
+
+
+def entry(name: str):
+    """The bound entry point `name` of the loaded library; F3RError if that library predates it (SYMBOL_SINCE)."""
+    l = lib()
+    have, need = library_version(), SYMBOL_SINCE.get(name, 0)
+    if have < need:
+        raise F3RError(f"{LIB_PATH} is version {have}, {name} needs >= {need}: rebuild it (fast3r_amd/csrc/build.sh)")
+    return getattr(l, name)
 
 
 def check(status: int, what: str = ""):

@@ -1,5 +1,5 @@
 """Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
-loss, scene assembly, sky detection and mesh export.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+loss, scene assembly, sky detection, mesh export and point-cloud export.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
 out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
 """
 import ctypes
@@ -452,3 +452,229 @@ def mesh_ply_pack(vertices, faces, face_colors):
         check(_lib.lib().f3r_mesh_ply_pack(ptr(vertices) if nv else None, nv, ptr(faces) if nf else None, ptr(face_colors) if nf else None, nf,
                                            idx_id, ptr(out), stream_ptr()), "f3r_mesh_ply_pack")
     return out.view(torch.uint8)
+
+
+# ------------------------------------------------------------------------------------------------------------------- point-cloud export
+def cloud_combine(conf, pts, img, mask, shapes, ranks, *, flip_axes=False, thresholds=None):
+    """The kept pixels of a list of views as one cloud (f3r_mesh_threshold, then f3r_cloud_combine_count / _write, include/f3r.h).  Lists
+    over views of GPU tensors, as mesh_build takes them: conf (H W,) fp32 or None (no threshold test), pts (H W, 3) fp32, img (3, H W) fp32
+    planes or (H W, 3) uint8 colours, mask (H W,) uint8 (nonzero = keep) or None; shapes[i] = (H, W); ranks[i] = (k_lo, k_hi, gamma) of
+    scene.percentile_indexes (ignored without conf).  A pixel is kept iff conf > the view's threshold and its mask byte is nonzero.
+    thresholds: a (V,) fp32 device tensor to use instead of computing them.  -> (points (M, 3) fp32, colors (M, 3) uint8) on the device
+    in view order then pixel order, or (None, None) when nothing is kept.  The host reads back one word: the total."""
+    V = len(pts)
+    if V < 1 or not (len(conf) == len(img) == len(mask) == len(shapes) == len(ranks) == V):
+        raise ValueError("cloud_combine: need one conf, pts, img, mask, shape and rank entry per view, and at least one view")
+    count, write = _lib.entry("f3r_cloud_combine_count"), _lib.entry("f3r_cloud_combine_write")
+    dev = pts[0].device
+    f32, u8 = torch.float32, torch.uint8
+    rows, pix, keep, vbase = [], [], [], 0
+    for i in range(V):
+        H, W = int(shapes[i][0]), int(shapes[i][1])
+        if H < 1 or W < 1 or H * W >= 2 ** 31:
+            raise ValueError(f"cloud_combine: view {i} is {H} x {W}; need H, W >= 1 and H * W < 2^31")
+        n = H * W
+        c, p, g, m = conf[i], pts[i], img[i], mask[i]
+        for t in (c, p, g, m):
+            if t is not None:
+                require_gpu(t, f"view {i}")
+                if t.device != dev:
+                    raise ValueError(f"cloud_combine: view {i}: tensors on {t.device} and {dev}")
+        if p.dtype != f32 or tuple(p.shape) != (n, 3):
+            raise ValueError(f"cloud_combine: view {i}: pts must be ({n}, 3) fp32, got {tuple(p.shape)} {p.dtype}")
+        if c is not None and (c.dtype != f32 or tuple(c.shape) != (n,)):
+            raise ValueError(f"cloud_combine: view {i}: conf must be ({n},) fp32, got {tuple(c.shape)} {c.dtype}")
+        img_u8 = g.dtype == u8
+        if not ((img_u8 and tuple(g.shape) == (n, 3)) or (g.dtype == f32 and tuple(g.shape) == (3, n))):
+            raise ValueError(f"cloud_combine: view {i}: img must be (3, {n}) fp32 planes or ({n}, 3) uint8, got {tuple(g.shape)} {g.dtype}")
+        if m is not None and (m.dtype != u8 or tuple(m.shape) != (n,)):
+            raise ValueError(f"cloud_combine: view {i}: mask must be ({n},) uint8, got {tuple(m.shape)} {m.dtype}")
+        c = None if c is None else c.contiguous()
+        m = None if m is None else m.contiguous()
+        p, g = p.contiguous(), g.contiguous()
+        keep += [c, p, g, m]
+        k_lo, k_hi, gamma = (0, 0, 0.0) if c is None else ranks[i]
+        gamma_bits = int(np.asarray(gamma, dtype=np.float32).reshape(1).view(np.uint32)[0])
+        rows.append([0 if c is None else c.data_ptr(), p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), H, W, vbase,
+                     int(img_u8), int(k_lo), int(k_hi), gamma_bits, 0])
+        pix.append(n)
+        vbase += n
+    starts = tile_starts(pix, _lib.CLOUD_TILE)
+    n_tiles = starts[-1]
+    if n_tiles >= 2 ** 31:
+        raise ValueError(f"cloud_combine: {n_tiles} tiles; need fewer than 2^31")
+    table = table_words(rows, starts).to(dev)
+    have_conf = any(c is not None for c in conf)
+    if thresholds is not None:
+        require_gpu(thresholds, "thresholds")
+        if thresholds.dtype != f32 or tuple(thresholds.shape) != (V,) or thresholds.device != dev:
+            raise ValueError(f"cloud_combine: thresholds must be ({V},) fp32 on {dev}, got {tuple(thresholds.shape)} {thresholds.dtype}")
+        thr = thresholds.contiguous()
+    else:
+        small = torch.empty(2 * V, dtype=torch.int32, device=dev)
+        thr = small[:V].view(f32)
+    scan = torch.empty(n_tiles + 1, dtype=torch.int32, device=dev)
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        if have_conf and thresholds is None:
+            check(l.f3r_mesh_threshold(ptr(table), V, ptr(thr), ptr(small[V:]), stream_ptr()), "f3r_mesh_threshold")
+        thr_ptr = ptr(thr) if have_conf else None
+        check(count(ptr(table), V, n_tiles, thr_ptr, ptr(scan), stream_ptr()), "f3r_cloud_combine_count")
+        total = int(scan[n_tiles].item()) & 0xffffffff
+        if total == 0:
+            return None, None
+        out_p = torch.empty((total, 3), dtype=f32, device=dev)
+        out_c = torch.empty((total, 3), dtype=u8, device=dev)
+        check(write(ptr(table), V, n_tiles, thr_ptr, ptr(scan), int(bool(flip_axes)), ptr(out_p), ptr(out_c), stream_ptr()),
+              "f3r_cloud_combine_write")
+    del keep, table  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    return out_p, out_c
+
+
+def _cloud_points(points, who, colors=None):
+    require_gpu(points, "points")
+    n = points.shape[0] if points.dim() == 2 else -1
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or not 1 <= n < 2 ** 31:
+        raise ValueError(f"{who}: points must be (1 <= n < 2^31, 3) fp32, got {tuple(points.shape)} {points.dtype}")
+    if colors is not None:
+        require_gpu(colors, "colors")
+        if tuple(colors.shape) != (n, 3) or colors.dtype != torch.uint8 or colors.device != points.device:
+            raise ValueError(f"{who}: colors must be ({n}, 3) uint8 on {points.device}, got {tuple(colors.shape)} {colors.dtype} on {colors.device}")
+        colors = colors.contiguous()
+    return points.contiguous(), colors, n
+
+
+def _float_of_key(k):
+    k = int(k) & 0xffffffff
+    u = (k & 0x7fffffff) if k & 0x80000000 else (~k) & 0xffffffff
+    return float(np.array([u], dtype=np.uint32).view(np.float32)[0])
+
+
+def cloud_bounds(points):
+    """(min (3,), max (3,)) as Python floats over the finite coordinates, and the count of non-finite ones (f3r_cloud_bounds): one
+    readback of eight words"""
+    fn = _lib.entry("f3r_cloud_bounds")
+    points, _, n = _cloud_points(points, "cloud_bounds")
+    out = torch.empty(8, dtype=torch.int32, device=points.device)
+    with torch.cuda.device(points.device):
+        check(fn(ptr(points), n, ptr(out), stream_ptr()), "f3r_cloud_bounds")
+    w = out.cpu().tolist()
+    return [_float_of_key(k) for k in w[:3]], [_float_of_key(k) for k in w[3:6]], int(w[6]) & 0xffffffff
+
+
+def heuristic_voxel_size(min_bound, max_bound, max_num_points):
+    """the notebook's voxel size for a target count: the cube root of the bounding box's volume per point, as Python floats"""
+    extent = [float(hi) - float(lo) for lo, hi in zip(min_bound, max_bound)]
+    return (extent[0] * extent[1] * extent[2] / max_num_points) ** (1 / 3)
+
+
+def voxel_key_bits(min_bound, max_bound, voxel_size):
+    """Bits of the voxel key per axis: ceil(log2(c_a)) for c_a = floor(extent_a / voxel_size + 0.5) + 1 cells -- and never fewer cells than
+    the largest index the kernel's own expression floor((max_a - (min_a - 0.5 voxel_size)) / voxel_size) reaches, which rounding can put one
+    past that count.  ValueError when an axis needs more than 31 bits or the key more than 63."""
+    voxel_size = float(voxel_size)
+    if not (voxel_size > 0.0 and math.isfinite(voxel_size)):
+        raise ValueError(f"voxel_size = {voxel_size}; need a finite value > 0")
+    bits = []
+    for lo, hi in zip(min_bound, max_bound):
+        lo, hi = float(lo), float(hi)
+        cells = (hi - lo) / voxel_size + 0.5
+        top = (hi - (lo - 0.5 * voxel_size)) / voxel_size
+        if not (math.isfinite(cells) and math.isfinite(top)):
+            raise ValueError(f"voxel_size too small for this extent ({voxel_size} for {hi - lo})")
+        c = max(math.floor(cells) + 1, math.floor(top) + 1)
+        bits.append((c - 1).bit_length())
+    if max(bits) > 31 or sum(bits) > 63:
+        raise ValueError(f"voxel_size too small for this extent: {bits} key bits per axis; at most 31 each and 63 in all")
+    return bits
+
+
+def voxel_sort_passes(bits):
+    """8-bit LSD passes over a key of that many bits"""
+    return (sum(bits) + 7) // 8
+
+
+def cloud_voxel_down_sample(points, colors, voxel_size, bounds=None):
+    """Open3D's VoxelDownSample in a fixed order (f3r_cloud_voxel_sort / _sums, include/f3r.h).  points (n, 3) fp32, colors (n, 3) uint8 or
+    None, on the GPU; bounds: what cloud_bounds(points) returned, if the caller has it.  -> dict(points (M, 3) fp32, colors (M, 3) uint8 or
+    None, counts (M,) int32: voxels in ascending key order; bits: key bits per axis; passes: sort passes run).  ValueError on a NaN or inf
+    coordinate, voxel_size <= 0 and a key of more than 63 bits.  The host reads back the bounds and one word: the voxel count."""
+    sort, sums, sizer = _lib.entry("f3r_cloud_voxel_sort"), _lib.entry("f3r_cloud_voxel_sums"), _lib.entry("f3r_cloud_voxel_workspace_bytes")
+    points, colors, n = _cloud_points(points, "cloud_voxel_down_sample", colors)
+    lo, hi, bad = cloud_bounds(points) if bounds is None else bounds
+    if bad:
+        raise ValueError(f"cloud_voxel_down_sample: {bad} coordinates are NaN or inf")
+    voxel_size = float(voxel_size)
+    if not voxel_size > 0.0:
+        raise ValueError(f"cloud_voxel_down_sample: voxel_size = {voxel_size}; need > 0")
+    bits = voxel_key_bits(lo, hi, voxel_size)
+    dev = points.device
+    ws_bytes = sizer(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    n_vox = torch.empty(1, dtype=torch.int32, device=dev)
+    mb, cb = (ctypes.c_double * 3)(*lo), (ctypes.c_int * 3)(*bits)
+    with torch.cuda.device(dev):
+        check(sort(ptr(points), n, mb, voxel_size, cb, ptr(ws), ws_bytes, ptr(n_vox), stream_ptr()), "f3r_cloud_voxel_sort")
+        m = int(n_vox.item()) & 0xffffffff
+        out_p = torch.empty((m, 3), dtype=torch.float32, device=dev)
+        out_c = None if colors is None else torch.empty((m, 3), dtype=torch.uint8, device=dev)
+        counts = torch.empty(m, dtype=torch.int32, device=dev)
+        check(sums(ptr(points), ptr(colors), n, m, ptr(ws), ws_bytes, ptr(out_p), ptr(out_c), ptr(counts), stream_ptr()), "f3r_cloud_voxel_sums")
+    del ws  # the launches are stream-ordered before the caching allocator can hand this block out again
+    return {"points": out_p, "colors": out_c, "counts": counts, "bits": bits, "passes": voxel_sort_passes(bits)}
+
+
+def cloud_fps(points, num_samples, start_index=0, mode=_lib.F3R_FPS_AUTO):
+    """Open3D's FarthestPointDownSample (f3r_cloud_fps, include/f3r.h): points (n, 3) fp32 on the GPU, finite (the caller's check:
+    cloud_bounds counts) -> selected int32 (num_samples,) in selection order.  mode: F3R_FPS_AUTO, F3R_FPS_ONE (one workgroup, n <=
+    CLOUD_FPS_ONE_MAX) or F3R_FPS_TILED (one launch per sample).  O(n num_samples), as the reference's."""
+    fn, sizer = _lib.entry("f3r_cloud_fps"), _lib.entry("f3r_cloud_fps_workspace_bytes")
+    points, _, n = _cloud_points(points, "cloud_fps")
+    num_samples, start_index, mode = int(num_samples), int(start_index), int(mode)
+    if not 1 <= num_samples <= n:
+        raise ValueError(f"cloud_fps: num_samples = {num_samples} outside [1, {n}]")
+    if not 0 <= start_index < n:
+        raise ValueError(f"cloud_fps: start_index = {start_index} outside [0, {n})")
+    if mode not in (_lib.F3R_FPS_AUTO, _lib.F3R_FPS_ONE, _lib.F3R_FPS_TILED) or (mode == _lib.F3R_FPS_ONE and n > _lib.CLOUD_FPS_ONE_MAX):
+        raise ValueError(f"cloud_fps: mode = {mode} for n = {n}; F3R_FPS_ONE takes n <= {_lib.CLOUD_FPS_ONE_MAX}")
+    dev = points.device
+    tiled = mode == _lib.F3R_FPS_TILED or (mode == _lib.F3R_FPS_AUTO and n > _lib.CLOUD_FPS_ONE_MAX)
+    ws_bytes = sizer(n) if tiled else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if tiled else None
+    selected = torch.empty(num_samples, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(ptr(points), n, num_samples, start_index, mode, ptr(ws), ws_bytes, ptr(selected), stream_ptr()), "f3r_cloud_fps")
+    del ws  # the launches are stream-ordered before the caching allocator can hand this block out again
+    return selected
+
+
+def cloud_mark(selected, n):
+    """uint8 (n,) on the device: 1 at every index in selected (int32, every entry in [0, n)), 0 elsewhere (f3r_cloud_mark)"""
+    require_gpu(selected, "selected")
+    k, n = selected.numel(), int(n)
+    if selected.dim() != 1 or selected.dtype != torch.int32 or not 1 <= k <= n < 2 ** 31:
+        raise ValueError(f"cloud_mark: selected must be int32 (1 <= k <= n = {n} < 2^31,), got {tuple(selected.shape)} {selected.dtype}")
+    fn = _lib.entry("f3r_cloud_mark")
+    selected = selected.contiguous()
+    mask = torch.empty(n, dtype=torch.uint8, device=selected.device)
+    with torch.cuda.device(selected.device):
+        check(fn(ptr(selected), k, n, ptr(mask), stream_ptr()), "f3r_cloud_mark")
+    return mask
+
+
+def cloud_gather(points, colors, index):
+    """(points[index], colors[index]) in the order of index (int32 or int64, every entry in [0, n): the caller's contract) (f3r_cloud_gather);
+    colors may be None"""
+    points, colors, n = _cloud_points(points, "cloud_gather", colors)
+    require_gpu(index, "index")
+    m = index.numel()
+    if index.dim() != 1 or index.dtype not in (torch.int32, torch.int64) or index.device != points.device or not 1 <= m < 2 ** 31:
+        raise ValueError(f"cloud_gather: index must be int32 or int64 (1 <= m < 2^31,) on {points.device}, got {tuple(index.shape)} {index.dtype}")
+    fn = _lib.entry("f3r_cloud_gather")
+    index = index.contiguous()
+    out_p = torch.empty((m, 3), dtype=torch.float32, device=points.device)
+    out_c = None if colors is None else torch.empty((m, 3), dtype=torch.uint8, device=points.device)
+    with torch.cuda.device(points.device):
+        check(fn(ptr(points), ptr(colors), ptr(index), int(index.dtype == torch.int64), n, m, ptr(out_p), ptr(out_c), stream_ptr()),
+              "f3r_cloud_gather")
+    return out_p, out_c

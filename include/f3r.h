@@ -48,7 +48,7 @@ typedef enum { F3R_LOSS_DIS = 0, F3R_LOSS_LOG1P = 1 } f3r_loss_dis_mode; /* avg_
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 410 = 0.4.1 (+ f3r_mesh_threshold, f3r_mesh_count, f3r_mesh_write, f3r_mesh_ply_pack, f3r_mesh_workspace_bytes); 400 = 0.4.0 (+ f3r_sky_detect, f3r_sky_workspace_bytes); 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 420 = 0.4.2 (+ f3r_cloud_combine_count, f3r_cloud_combine_write, f3r_cloud_bounds, f3r_cloud_voxel_workspace_bytes, f3r_cloud_voxel_sort, f3r_cloud_voxel_sums, f3r_cloud_fps_workspace_bytes, f3r_cloud_fps, f3r_cloud_mark, f3r_cloud_gather); 410 = 0.4.1 (+ f3r_mesh_threshold, f3r_mesh_count, f3r_mesh_write, f3r_mesh_ply_pack, f3r_mesh_workspace_bytes); 400 = 0.4.0 (+ f3r_sky_detect, f3r_sky_workspace_bytes); 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -668,6 +668,62 @@ int f3r_mesh_write(const int64_t* table, const int64_t* host_hw, int n_views, in
                    size_t workspace_bytes, float* vertices, void* faces, uint8_t* face_colors, f3r_stream_t stream);
 int f3r_mesh_ply_pack(const float* vertices, int64_t n_vertices, const void* faces, const uint8_t* face_colors, int64_t n_faces,
                       int index_dtype, void* out, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Point-cloud export (ABI 420): export_combined_ply of the reference's notebooks/demo_multiview.ipynb -- per view np.percentile(conf, p),
+ * conf > thr, the colour line, concatenation -- and its two Open3D downsamplers, VoxelDownSample and FarthestPointDownSample, restated
+ * in a fixed arithmetic order.  Python: fast3r_amd/cloud.py.  Kernels: fast3r_amd/csrc/f3r_cloud.hip.
+ * `table` of the two combine entries is a DEVICE int64 array: n_views rows of 12 words laid out as the mesh rows above { conf pointer (0 =
+ *   no threshold test), pts pointer ((H W, 3) fp32), img pointer (fp32 planes (3, H W), or with img_u8 != 0 the (H W, 3) colour bytes), mask
+ *   pointer ((H W) bytes, nonzero = keep; 0 = none), H, W, vbase, img_u8, k_lo, k_hi, gamma, 0 } -- the thresholds come from
+ *   f3r_mesh_threshold on the same rows -- then n_views + 1 tile starts (running sum of ceil(H W / F3R_CLOUD_TILE)).
+ * f3r_cloud_combine_count: keep = conf > thresholds[v] (skipped when thresholds or the view's conf is null) AND mask != 0; scan (device
+ *   uint32 [n_tiles + 1]) = the exclusive scan of the kept pixels per tile; scan[n_tiles] = the total.
+ * f3r_cloud_combine_write, with the same table, thresholds and scan: points [total][3] fp32 and colors [total][3] bytes in view order then
+ *   pixel order; (x, y, z) -> (x, z, -y) with flip_axes; the colour is the byte as given, or trunc((img + 1.0f) * 127.5f) as two rounded
+ *   fp32 operations, saturated to [0, 255] (NaN -> 0).
+ * f3r_cloud_bounds: out (device uint32 [8]) = { the order-preserving keys (sign bit set -> all bits flipped, else sign bit set) of the
+ *   minimum of x, y, z over the finite coordinates, of the maximum of x, y, z, the count of non-finite coordinates, 0 }; integer atomics.
+ * f3r_cloud_voxel_sort: index_a = floor((p_a - vmin_a) / voxel_size) in fp64, vmin_a = min_bound[a] - 0.5 voxel_size (min_bound: HOST
+ *   double [3]); key = (index_x << (bits[1] + bits[2])) | (index_y << bits[2]) | index_z (bits: HOST int [3], at most 63 in all); a stable
+ *   LSD radix sort of (key, point index) with 8-bit digits in ceil(total bits / 8) passes; the segment heads (key differs from its
+ *   predecessor's) and their scan.  *n_voxels (device uint32) = the number of distinct keys.  The workspace then holds what
+ * f3r_cloud_voxel_sums reads (same n and workspace; n_voxels read back by the caller): one thread per voxel walks its run -- in original
+ *   index order: the sort is stable -- and adds, sequentially in fp64, the widened coordinates and colour / 255.0 per channel;
+ *   out_points[v] = (float)(sum / count), out_colors[v] = trunc(sum_c / count * 255.0), counts[v] = count; voxels in ascending key order.
+ *   colors may be null (then out_colors is not written).  No floating-point atomics: the outputs equal a sequential restatement bit for bit.
+ * f3r_cloud_fps: FarthestPointDownSample.  d[j] = inf; far = start_index; num_samples times: selected[i] = far; d[j] = min(d[j], (dx dx +
+ *   dy dy) + dz dz) in fp64 on the widened coordinates, (dx, dy, dz) = p[j] - p[far]; far = the smallest index attaining max d if that
+ *   maximum is > 0, else unchanged.  mode 0: one workgroup for n <= F3R_CLOUD_FPS_ONE_MAX, else tiled; 1: one workgroup (the whole loop in
+ *   one kernel; F3R_ERR_ARG beyond F3R_CLOUD_FPS_ONE_MAX); 2: tiled -- one launch per iteration of min(ceil(n / F3R_CLOUD_FPS_TILE), 1024)
+ *   workgroups with a grid-stride tile assignment; each reduces the previous launch's per-workgroup (distance, index) partials, updates its
+ *   tiles' d and writes its own partial into the other half of a ping-pong pair.  The launch boundary is the only cross-workgroup
+ *   synchronisation: no cooperative launch, no grid barrier, no spin-wait, no atomics.  The input must be finite (f3r_cloud_bounds counts).
+ * f3r_cloud_mark: mask[0 .. n) = 0, then mask[selected[i]] = 1 (plain stores).  f3r_cloud_gather: out[i] = in[index[i]] for points and
+ *   (unless null) colours; index is int32, or int64 with index_i64 != 0; every index in [0, n) (the caller's contract).
+ * Limits, F3R_ERR_ARG before any launch: 1 <= n < 2^31 everywhere; null pointers; a workspace that is too small; bits outside [0, 31] or
+ *   more than 63 in all; voxel_size not > 0; num_samples outside [1, n]; start_index outside [0, n); an unknown mode.  The
+ *   *_workspace_bytes functions return 0 for refused arguments.  Inputs are not written to; two runs give the same bits.
+ */
+#define F3R_CLOUD_TILE 1024
+#define F3R_CLOUD_SORT_TILE 2048
+#define F3R_CLOUD_FPS_TILE 1024
+#define F3R_CLOUD_FPS_ONE_MAX 8192
+int f3r_cloud_combine_count(const int64_t* table, int n_views, int64_t n_tiles, const float* thresholds, uint32_t* scan, f3r_stream_t stream);
+int f3r_cloud_combine_write(const int64_t* table, int n_views, int64_t n_tiles, const float* thresholds, const uint32_t* scan, int flip_axes,
+                            float* points, uint8_t* colors, f3r_stream_t stream);
+int f3r_cloud_bounds(const float* points, int64_t n, uint32_t* out, f3r_stream_t stream);
+size_t f3r_cloud_voxel_workspace_bytes(int64_t n);
+int f3r_cloud_voxel_sort(const float* points, int64_t n, const double* min_bound, double voxel_size, const int* bits, void* workspace,
+                         size_t workspace_bytes, uint32_t* n_voxels, f3r_stream_t stream);
+int f3r_cloud_voxel_sums(const float* points, const uint8_t* colors, int64_t n, int64_t n_voxels, const void* workspace,
+                         size_t workspace_bytes, float* out_points, uint8_t* out_colors, int32_t* counts, f3r_stream_t stream);
+size_t f3r_cloud_fps_workspace_bytes(int64_t n);
+int f3r_cloud_fps(const float* points, int64_t n, int64_t num_samples, int64_t start_index, int mode, void* workspace,
+                  size_t workspace_bytes, int32_t* selected, f3r_stream_t stream);
+int f3r_cloud_mark(const int32_t* selected, int64_t num_samples, int64_t n, uint8_t* mask, f3r_stream_t stream);
+int f3r_cloud_gather(const float* points, const uint8_t* colors, const void* index, int index_i64, int64_t n, int64_t m, float* out_points,
+                     uint8_t* out_colors, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).

@@ -1,6 +1,6 @@
 """Kernel micro-benchmarks on the GPU box (interleaved rounds, random data, HIP events on the launch stream): the attention kernels
 f3r_attn_fwd can take (--what attnproduct / attnsel / attnhd) and the model's GEMM / conv shapes per f3r_gemm_args.kernel_sel, with the vendor
-library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement; --what scene: scene assembly and PLY export likewise; --what sky: sky detection alone, inside assemble_scene and next to the CPU (--what skydetect: its kernels alone, for a profiler run).  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
+library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement; --what scene: scene assembly and PLY export likewise; --what cloud: point-cloud export (combine, voxel, farthest point) likewise; --what sky: sky detection alone, inside assemble_scene and next to the CPU (--what skydetect: its kernels alone, for a profiler run).  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
 F3R_LAB_LIB=tools/lab/libf3r_hip_lab.so.)"""
 import argparse
 import math
@@ -724,6 +724,186 @@ def bench_sky(sizes=(100, 320), H=512, W=512, out_path="profiles/r10_sky_bench.j
         f.write(line + "\n")
 
 
+def bench_cloud(sizes=(100, 320), H=512, W=512, max_num_points=1_000_000, out_path="profiles/r11_cloud_bench.jsonl"):
+    """Point-cloud export (fast3r_amd/cloud.py, f3r_cloud.hip) at N views of H x W generated on the device, percentile 0, B = 1.  Every shape
+    warmed up, medians of 5 calls with min / max:
+    * combine: `post_ops.cloud_combine` with the thresholds handed in, wall clock (synchronised) and stream events, alternating call by
+      call with a torch-eager restatement on the same GPU (one batched comparison, boolean gathers, the colour arithmetic);
+    * voxel with max_num_points (the notebook's heuristic size): stream times of f3r_cloud_bounds, of f3r_cloud_voxel_sort whole and with
+      a key of zero bits (keys, heads, scan and starts without any sort pass: the difference is the passes) and of f3r_cloud_voxel_sums;
+      torch.unique(return_inverse) + index_add_ in fp64 beside it (unordered atomic sums: a speed yardstick only); tests/cloud_ref.py on
+      this machine's CPU at the first size;
+    * farthest point, tiled: stream time per iteration at n = 1 M and n = N H W points, the rate that n (12 + 16) bytes per iteration
+      imply, and a torch-eager loop of the same step; the one-workgroup kernel per iteration at its largest n.
+    One JSON line, appended to profiles/."""
+    import ctypes
+    import os
+    import statistics
+    import time
+    import numpy as np
+    from fast3r_amd import cloud
+    from fast3r_amd.scene import percentile_indexes
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import cloud_ref as R
+
+    def once_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def stats(ts):
+        return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "n": len(ts)}
+
+    def events(fn, n=5):
+        fn()
+        ts = []
+        for _ in range(n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return stats(ts)
+
+    def fps_eager(p, k):
+        d = torch.full((p.shape[0],), float("inf"), dtype=torch.float64, device=DEV)
+        far = torch.zeros((), dtype=torch.long, device=DEV)
+        for _ in range(k):
+            diff = p.double() - p[far].double()
+            d = torch.minimum(d, (diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2])
+            far = torch.argmax(d)
+        return far
+
+    def fps_rates(p, k=17):
+        n = p.shape[0]
+        tiled = events(lambda: post_ops.cloud_fps(p, k, 0, _lib.F3R_FPS_TILED))
+        eager = events(lambda: fps_eager(p, k - 1))
+        per = tiled["median_ms"] / (k - 1)   # k selections are k - 1 distance updates
+        return {"n": n, "iterations_timed": k - 1, "tiled_call": tiled, "tiled_ms_per_iteration": round(per, 4),
+                "implied_GB_per_s_of_28_bytes_per_point": round(n * 28 / (per * 1e-3) / 1e9, 1), "eager_torch_loop": eager,
+                "eager_ms_per_iteration": round(eager["median_ms"] / (k - 1), 4), "eager_over_tiled": round(eager["median_ms"] / tiled["median_ms"], 3)}
+
+    rec = {"what": "cloud", "device": torch.cuda.get_device_name(0), "B": 1, "HW": [H, W], "percentile": 0, "max_num_points": max_num_points,
+           "tiles": {"combine": _lib.CLOUD_TILE, "sort": _lib.CLOUD_SORT_TILE, "fps": _lib.CLOUD_FPS_TILE, "fps_one_max": _lib.CLOUD_FPS_ONE_MAX},
+           "sizes": {}}
+    g = torch.Generator(device=DEV).manual_seed(0)
+    rnd = lambda *s: torch.rand(*s, generator=g, device=DEV)  # noqa: E731
+    L = H * W
+    for pos, n in enumerate(sizes):
+        conf = 1.0 + 20.0 * rnd(n, L) ** 2
+        pts = torch.randn(n, L, 3, generator=g, device=DEV) * torch.tensor([4.0, 1.5, 3.0], device=DEV)   # an unbounded scene: most voxels of the box stay empty
+        img = rnd(n, 3, L) * 2 - 1
+        thr = conf.amin(dim=1)                                           # percentile 0: the minimum, handed to both sides
+        ranks = [percentile_indexes(L, 0)] * n
+        lists = ([conf[i] for i in range(n)], [pts[i] for i in range(n)], [img[i] for i in range(n)], [None] * n, [(H, W)] * n, ranks)
+        product = lambda: post_ops.cloud_combine(*lists, thresholds=thr)  # noqa: E731
+
+        def eager_combine():
+            mask = conf > thr[:, None]
+            col = ((img + 1.0) * 127.5).to(torch.uint8).transpose(1, 2)
+            return pts[mask], col[mask]
+
+        once_ms(product)
+        once_ms(eager_combine)
+        tp, te = [], []
+        for _ in range(5):   # alternating
+            tp.append(once_ms(product)[0])
+            te.append(once_ms(eager_combine)[0])
+        ev_p, ev_e = events(product), events(eager_combine)
+        cp, cc = product()
+        ep, ec = eager_combine()
+        assert torch.equal(cp, ep) and torch.equal(cc, ec)
+        del ep, ec, conf, img, lists
+        torch.cuda.empty_cache()
+        m = cp.shape[0]
+        combine = {"points": m, "product_wall": stats(tp), "eager_wall": stats(te), "product_stream": ev_p, "eager_stream": ev_e,
+                   "eager_over_product_wall": round(statistics.median(te) / statistics.median(tp), 3),
+                   "eager_over_product_stream": round(ev_e["median_ms"] / ev_p["median_ms"], 3)}
+
+        print(f"cloud: N = {n}: combine done ({m} points)", file=sys.stderr, flush=True)
+        # ---- voxel
+        lo, hi, bad = post_ops.cloud_bounds(cp)
+        vs = cloud.heuristic_voxel_size(lo, hi, max_num_points)
+        bits = cloud.voxel_key_bits(lo, hi, vs)
+        l = _lib.lib()
+        ws_bytes = l.f3r_cloud_voxel_workspace_bytes(m)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
+        nv = torch.empty(1, dtype=torch.int32, device=DEV)
+        bout = torch.empty(8, dtype=torch.int32, device=DEV)
+        mb = (ctypes.c_double * 3)(*lo)
+        st = _lib.stream_ptr
+        sort = lambda b: _lib.check(l.f3r_cloud_voxel_sort(_lib.ptr(cp), m, mb, vs, (ctypes.c_int * 3)(*b), _lib.ptr(ws), ws_bytes, _lib.ptr(nv), st()), "sort")  # noqa: E731
+        t_bounds = events(lambda: _lib.check(l.f3r_cloud_bounds(_lib.ptr(cp), m, _lib.ptr(bout), st()), "bounds"))
+        t_nosort = events(lambda: sort([0, 0, 0]))
+        t_sort = events(lambda: sort(bits))
+        n_vox = int(nv.item())
+        op, oc = torch.empty((n_vox, 3), device=DEV), torch.empty((n_vox, 3), dtype=torch.uint8, device=DEV)
+        ocnt = torch.empty(n_vox, dtype=torch.int32, device=DEV)
+        t_sums = events(lambda: _lib.check(l.f3r_cloud_voxel_sums(_lib.ptr(cp), _lib.ptr(cc), m, n_vox, _lib.ptr(ws), ws_bytes, _lib.ptr(op), _lib.ptr(oc),
+                                                                  _lib.ptr(ocnt), st()), "sums"))
+        max_count = int(ocnt.max().item())
+        del ws, op, oc, ocnt
+        torch.cuda.empty_cache()
+        whole = lambda: post_ops.cloud_voxel_down_sample(cp, cc, vs, (lo, hi, bad))  # noqa: E731
+
+        def eager_voxel():
+            p64 = cp.double()
+            idx = torch.floor((p64 - (torch.tensor(lo, dtype=torch.float64, device=DEV) - 0.5 * vs)) / vs).long()
+            key = (idx[:, 0] << (bits[1] + bits[2])) | (idx[:, 1] << bits[2]) | idx[:, 2]
+            uniq, inv, cnt = torch.unique(key, return_inverse=True, return_counts=True)
+            sp = torch.zeros((uniq.shape[0], 3), dtype=torch.float64, device=DEV).index_add_(0, inv, p64)
+            sc = torch.zeros((uniq.shape[0], 3), dtype=torch.float64, device=DEV).index_add_(0, inv, cc.double() / 255.0)
+            c = cnt.double()[:, None]
+            return (sp / c).float(), (sc / c * 255.0).to(torch.uint8), cnt
+
+        once_ms(whole)
+        once_ms(eager_voxel)
+        tw, tev = [], []
+        for _ in range(5):
+            tw.append(once_ms(whole)[0])
+            tev.append(once_ms(eager_voxel)[0])
+        assert eager_voxel()[2].shape[0] == n_vox
+        voxel = {"points": m, "voxel_size": vs, "key_bits": bits, "passes": cloud.voxel_sort_passes(bits), "voxels": n_vox, "largest_voxel": max_count,
+                 "bounds_stream": t_bounds, "keys_heads_scan_starts_stream": t_nosort, "voxel_sort_whole_stream": t_sort,
+                 "sort_passes_stream_ms": round(t_sort["median_ms"] - t_nosort["median_ms"], 3), "sums_stream": t_sums,
+                 "voxel_down_sample_wall": stats(tw), "eager_unique_index_add_wall": stats(tev),
+                 "eager_over_product_wall": round(statistics.median(tev) / statistics.median(tw), 3)}
+        if pos == 0:   # the numpy restatement on this machine's CPU
+            hp, hc = cp.cpu().numpy(), cc.cpu().numpy()
+            t0 = time.perf_counter()
+            ref = R.voxel_down_sample(hp, hc, vs)
+            voxel["cpu_numpy_restatement_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+            voxel["cpu_over_product_wall"] = round(voxel["cpu_numpy_restatement_ms"] / statistics.median(tw), 1)
+            got = whole()
+            voxel["equals_cpu_restatement"] = bool(np.array_equal(got["points"].cpu().numpy(), ref[0]) and np.array_equal(got["colors"].cpu().numpy(), ref[1])
+                                                   and np.array_equal(got["counts"].cpu().numpy(), ref[2]))
+            del hp, hc, ref, got
+        torch.cuda.empty_cache()
+
+        print(f"cloud: N = {n}: voxel done ({n_vox} voxels)", file=sys.stderr, flush=True)
+        # ---- farthest point
+        fps = {"full_cloud": fps_rates(cp)}
+        if pos == 0:
+            fps["one_million"] = fps_rates(cp[:1_000_000].contiguous())
+            small = cp[:_lib.CLOUD_FPS_ONE_MAX].contiguous()
+            k1 = 257
+            one = events(lambda: post_ops.cloud_fps(small, k1, 0, _lib.F3R_FPS_ONE))
+            til = events(lambda: post_ops.cloud_fps(small, k1, 0, _lib.F3R_FPS_TILED))
+            fps["one_workgroup"] = {"n": small.shape[0], "iterations_timed": k1 - 1, "call": one, "ms_per_iteration": round(one["median_ms"] / (k1 - 1), 5),
+                                    "tiled_same_input_ms_per_iteration": round(til["median_ms"] / (k1 - 1), 5)}
+        rec["sizes"][str(n)] = {"combine": combine, "voxel": voxel, "farthest_point": fps}
+        del cp, cc, pts
+        torch.cuda.empty_cache()
+    line = json.dumps(rec)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+
+
 def bench_posemetric(sizes=(320, 1500), H=512, W=512, out_path="profiles/r07_pose_metric_bench.jsonl"):
     """camera_pose_metrics (RRA / RTA / mAA from f3r_pose_pair_metrics) at B = 1 next to estimate_poses at the same view count in the same
     run: the metric stage is O(pairs) trigonometry on a few hundred kilobytes of poses and must stay below 5 % of the PnP stage.  Wall
@@ -1013,6 +1193,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if args.what == "sky":  # sky detection alone and inside assemble_scene, next to the numpy restatement on the CPU
         bench_sky()
+        sys.exit(0)
+    if args.what == "cloud":  # point-cloud export: combine, voxel and farthest-point downsampling next to torch-eager and the CPU restatement
+        bench_cloud(sizes=tuple(int(v) for v in args.views.split(",")) if args.views != "20,100" else (100, 320))
         sys.exit(0)
     if args.what == "skydetect":  # the detection kernels alone at N = 100 (both sets), for a profiler run of its own
         bench_sky(sizes=(100,), detect_only=True)
