@@ -238,7 +238,8 @@ __global__ __launch_bounds__(AT_NW * 64, 2) void attn_kernel(const f3r_attn_args
           }
     }
     // causal: keys beyond a row's own position are masked; a tile that lies entirely beyond the wave's rows is masked whole (its P are
-    // exactly 0: it costs its MFMAs but changes nothing -- the first tile of a launch always holds a visible key for every row)
+    // exactly 0: it costs its MFMAs but changes nothing -- the first tile of a launch always holds a visible key for every row: f3r_attn_fwd
+    // refuses a fresh launch whose first key lies after its first query)
     if (CAUSAL && pos_cur + (AT_KB - 1) > wave_q0) {  // the tile reaches past the first row of this wave (wave-uniform)
 #pragma unroll
       for (int qb = 0; qb < QPW; ++qb) {
@@ -434,6 +435,16 @@ extern "C" int f3r_attn_fwd(const f3r_attn_args* args, f3r_stream_t stream) {
     total += a.seg_len[s];
   }
   F3R_REQUIRE(total > 0, "f3r_attn_fwd: no keys");
+  if (a.causal && !a.state_in) {
+    // attn_kernel<causal> masks with -1e30 and takes its first softmax reference from tile 0: key 0 of that tile must be visible to every row
+    // (a row with nothing visible there would re-base onto the mask value: -inf and NaN in fp16, P = 1 for the masked keys in bf16)
+    int first = 0;
+    while (a.seg_len[first] == 0) ++first;
+    F3R_REQUIRE(a.seg_pos0[first] <= a.q_pos0,
+                "f3r_attn_fwd: causal launch without carried state whose first key (seg_pos0[%d] = %lld) lies after its first query (q_pos0 = %lld): "
+                "the first key of a fresh launch must be visible to every query row (start from the shard that holds the queries, resume over the others)",
+                first, (long long)a.seg_pos0[first], (long long)a.q_pos0);
+  }
   F3R_REQUIRE(a.kv_group >= 0 && (a.kv_group <= 1 || a.n_heads % a.kv_group == 0), "f3r_attn_fwd: kv_group %d does not divide n_heads %d", a.kv_group, a.n_heads);
   const int kv_heads = a.kv_group > 1 ? a.n_heads / a.kv_group : a.n_heads;
   F3R_REQUIRE(a.ldk >= kv_heads * hd * qkp, "f3r_attn_fwd: ldk < kv heads * head_dim");

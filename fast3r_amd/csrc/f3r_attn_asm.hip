@@ -53,7 +53,12 @@ int hd_index(int hd) {
     if (kHd[i] == hd) return i;
   return -1;
 }
-int wave_rows(int hd, int qk_planes = 1) { return (hd == 64 && qk_planes < 2) ? 128 : 64; }  // query rows of a wave (32 x the query blocks per wave)
+int qpw(int hd, int qk_planes = 1) { return (hd == 64 && qk_planes < 2) ? 4 : 2; }   // 32-query blocks per wave: AttnGen.QPW of csrc/asm/attn_gen.py
+constexpr int kQ256Qpw = 2;                                                            // ... of the 256-query form of head_dim 64: AttnGen(head_dim=64, qpw=2)
+int wave_rows(int hd, int qk_planes = 1) { return 32 * qpw(hd, qk_planes); }          // query rows of a wave: 128 at head_dim 64, 64 otherwise
+// query rows of a wave of the form a launch runs on.  A wave whose rows would run past the last query works on the LAST rows of that many
+// instead (attn_gen.py: s_sub_u32 tq, QW / s_min_u32): with fewer query rows than this the subtraction wraps and the wave reads and writes past tq.
+int form_wave_rows(int hd, int qk_planes, bool q256) { return q256 ? 32 * kQ256Qpw : wave_rows(hd, qk_planes); }
 
 struct DevKernels {
   bool tried = false;
@@ -203,6 +208,12 @@ static int64_t tail_split_rows(const f3r_attn_args& a, int hd, int qkp) {
   if (nqb_main * hb / cus > 8) return 0;
   const int64_t r = (nqb - nqb_main) * hb;   // items of the last round (< cus)
   if (2 * r > cus) return 0;                 // the tail would need two rounds of 256-query items: 1.28 > 1
+  // the tail is a launch of its own: it needs at least one wave's rows of the form that takes it (use_q256 above: the 256-query form, 64 rows).
+  // A shorter one -- tq = 8192 + 40 at 16 heads -- stays in ONE launch of all the query blocks, whose partial last workgroup handles any number of
+  // rows (use_q256 picks its form like any other launch's).
+  f3r_attn_args t = a;
+  t.tq = a.tq - nqb_main * 512;
+  if (t.tq < form_wave_rows(hd, qkp, use_q256(t, hd, qkp))) return 0;
   return nqb_main * 512;
 }
 
@@ -230,6 +241,9 @@ static int launch_one(const f3r_attn_args& a, hipStream_t stream) {
   const int hd = a.head_dim == 0 ? 64 : a.head_dim;
   const int qkp = a.qk_planes >= 2 ? a.qk_planes : 1;
   const bool q256 = use_q256(a, hd, qkp);
+  // (f3r_attn_asm_eligible checks the caller's tq; this one guards every launch the rules above derive from it)
+  F3R_REQUIRE(a.tq >= form_wave_rows(hd, qkp, q256), "f3r_attn_fwd: a hand-scheduled launch of %lld query rows, fewer than the %d of one wave", (long long)a.tq,
+              form_wave_rows(hd, qkp, q256));
   hipFunction_t fn = get_fn(a.dtype, hd, q256 ? -256 : qkp);
   if (!fn) {
     f3r_set_error("f3r_attn_fwd: the embedded hand-scheduled kernel could not be loaded on this device");
@@ -268,7 +282,7 @@ static int launch_one(const f3r_attn_args& a, hipStream_t stream) {
   // Work stealing (f3r_attn_args.sched_counter): one persistent workgroup per CU takes (q block, head, batch) items from a shared counter, so
   // the XCDs -- which the hardware feeds round-robin by workgroup id whatever their clocks -- finish together.  Worth it from two rounds of
   // workgroups on; the kernel's magic-number division needs item x period < 2^32.
-  const int64_t wg_rows = q256 ? 256 : 4 * wave_rows(hd, qkp);
+  const int64_t wg_rows = 4 * form_wave_rows(hd, qkp, q256);
   const unsigned nx = (unsigned)((a.tq + wg_rows - 1) / wg_rows);
   unsigned gx = nx, gy = (unsigned)a.n_heads, gz = (unsigned)a.batch;
   const uint64_t n_work = (uint64_t)nx * gy * gz, nxy = (uint64_t)nx * gy;

@@ -250,6 +250,16 @@ size_t f3r_block_workspace_bytes_ex(int64_t tokens, int D, int kv_dim, int hidde
  *   k_seg[s]  : [batch][seg_len[s]][ldk]
  *   vt_seg[s] : [batch][heads*64][ldvt[s]]  (V transposed, as written by the F3R_EPI_QKV epilogue)
  *   o  : [batch][tq][ldo]
+ *
+ * What a launch may touch (every kernel form; tests/test_attn_geometry_gpu.py holds each of them to it with every buffer between NaN patterns
+ * and sentinel words):
+ *   q      read: rows [0, tq) of each sequence, columns [0, n_heads * head_dim * planes) (planes = 2 with qk_planes 2 / 3, else 1).  Never the gap
+ *          columns up to ldq, the rows between two sequences when q_batch_stride > tq * ldq, or anything before / behind the buffer.
+ *   k_seg  read: rows [0, seg_len[s]) of each sequence, the columns of the K / V heads.  Never a row behind seg_len[s] or a gap column.
+ *   vt_seg read: rows [0, kv_heads * head_dim), columns [0, round_up(seg_len[s], 64)); the caller zeroes [seg_len[s], round_up(seg_len[s], 64)).
+ *          Columns from round_up(seg_len[s], 64) to ldvt[s] are never read (a short segment next to a long one under one ldvt has such columns).
+ *   o      written: rows [0, tq) x columns [0, n_heads * head_dim) of each sequence, nothing else; with state_out, nothing at all.
+ *   st_o / st_ml  read (state_in) and written (state_out): rows [0, batch * tq), nothing else.
  */
 typedef struct f3r_attn_args {
   const void* q;
@@ -286,7 +296,11 @@ typedef struct f3r_attn_args {
   int32_t kv_group;
   /* Causal attention (F.scaled_dot_product_attention(..., is_causal=True), components/llama.py:239): key at sequence position j is
      visible to the query at position i iff j <= i.  Positions are GLOBAL token indices: query row r of this launch sits at
-     q_pos0 + r, key row r of segment s at seg_pos0[s] + r (the view-sharded path attends over shards that start anywhere). */
+     q_pos0 + r, key row r of segment s at seg_pos0[s] + r (the view-sharded path attends over shards that start anywhere).
+     One precondition: a launch WITHOUT state_in must see its first key from every query row -- seg_pos0[first non-empty segment] <= q_pos0;
+     anything else is F3R_ERR_ARG.  The kernel takes its first softmax reference from the first key tile, and a row with nothing visible there
+     would take it from the mask value.  A sharded caller therefore starts from the shard that holds its queries (its first key sits AT q_pos0)
+     and resumes (state_in) over the other shards in any order, hidden ones included. */
   int32_t causal;
   int64_t q_pos0;
   int64_t seg_pos0[F3R_MAX_SEG];

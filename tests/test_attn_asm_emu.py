@@ -61,11 +61,11 @@ def test_emulated_kernel_counts_its_rebases():
 
 
 @pytest.mark.parametrize("kw", [dict(tq=200, wg=(0, 1, 0), tiles=2), dict(tq=1000, wg=(1, 0, 0), tiles=[1, 2], split=True, spike=True),
-                                dict(tq=640, wg=(1, 1, 0), tiles=3, dtype="bf16", tol=5e-3)])
+                                dict(tq=640, wg=(1, 1, 0), tiles=3, dtype="bf16", tol=5e-3), dict(tq=128, wg=(0, 0, 0), tiles=2)])
 def test_emulated_partial_last_workgroup(kw):
     """a query count that is not a multiple of 512 (layout 2): the waves that would run past the end work on the last 128 rows and store
     only the rows they own -- the output / state buffers hold exactly tq rows, so a store past the end is an emulator error, and a row
-    nobody wrote stays NaN"""
+    nobody wrote stays NaN.  tq = 128 is the smallest legal launch of this form: one wave's rows, the other three waves moved onto them"""
     import emu_attn
     err = emu_attn.run_case(kw.get("dtype", "f16"), kw["tiles"], n_heads=2, wgs=(kw["wg"],), spike=kw.get("spike", False),
                             split_state=kw.get("split", False), layout=2, tq=kw["tq"])
@@ -203,10 +203,12 @@ def test_emulated_three_product_form_parks_its_state_per_sequence(corr):
 
 @pytest.mark.parametrize("kw", [dict(n_tiles=1), dict(n_tiles=3), dict(n_tiles=6, spike=True), dict(dtype="bf16", n_tiles=4, spike=True, tol=5e-3),
                                 dict(n_tiles=[2, 1, 3], spike=True), dict(n_tiles=[2, 3], split_state=True), dict(tq=300, q_blocks=2, wgs=((1, 0, 0), (0, 1, 0))),
-                                dict(kv_shift=1, n_heads=4, batch=2, wgs=((0, 3, 1),)), dict(tq=700, n_heads=1, n_tiles=[1, 1], split_state=True, wgs=((0, 0, 0), (2, 0, 0)), steal=3)])
+                                dict(kv_shift=1, n_heads=4, batch=2, wgs=((0, 3, 1),)), dict(tq=700, n_heads=1, n_tiles=[1, 1], split_state=True, wgs=((0, 0, 0), (2, 0, 0)), steal=3),
+                                dict(tq=64, wgs=((0, 0, 0),), n_tiles=2)])
 def test_emulated_head_dim_64_with_256_query_work_items(kw):
     """AttnGen(head_dim=64, qpw=2) (round 6, kernels f3r_attn_asm_q256_*): the head_dim-64 kernel with two query blocks per wave -- 256-query work items
-    for launches whose 512-query items do not fill the chip evenly (f3r_attn_asm.hip use_q256).  Same state layout as every other kernel."""
+    for launches whose 512-query items do not fill the chip evenly (f3r_attn_asm.hip use_q256).  Same state layout as every other kernel.
+    tq = 64 is the smallest legal launch of this form (one wave's rows: what the tail of a split last round must have at least)."""
     import emu_attn
     kw = dict(kw)
     tol = kw.pop("tol", 6e-4)
