@@ -14,3 +14,4 @@ from .scene import Scene, assemble_scene, generate_ply_bytes, save_ply  # noqa: 
 from .mesh import Mesh, build_mesh, cat_meshes, generate_mesh_ply_bytes, pts3d_to_trimesh, save_mesh_ply  # noqa: F401
 from .cloud import combine_points, downsample_cloud, export_combined_ply, farthest_point_down_sample, voxel_down_sample  # noqa: F401
 from .sky import detect_sky_mask, detect_sky_masks, label_components  # noqa: F401
+from .render import Camera, birdseye_camera, pinhole_camera, render_cumulative_pts3d_viz, render_points  # noqa: F401

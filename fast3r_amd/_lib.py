@@ -27,6 +27,7 @@ F3R_INDEX_I32, F3R_INDEX_I64 = 0, 1
 # F3R_CLOUD_TILE: pixels per workgroup of the combine kernels; F3R_CLOUD_SORT_TILE: keys per workgroup of the voxel sort; F3R_CLOUD_FPS_TILE:
 # points per tile of the tiled farthest-point path; F3R_CLOUD_FPS_ONE_MAX: the most points its one-workgroup path takes
 CLOUD_TILE, CLOUD_SORT_TILE, CLOUD_FPS_TILE, CLOUD_FPS_ONE_MAX = 1024, 2048, 1024, 8192
+RENDER_CENTER_PARTS = 1024  # F3R_RENDER_CENTER_PARTS: rows of the scratch f3r_render_center takes
 F3R_FPS_AUTO, F3R_FPS_ONE, F3R_FPS_TILED = 0, 1, 2
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
@@ -183,11 +184,23 @@ SYMBOLS = {
     "f3r_cloud_fps": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_i64, ctypes.c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_vp]),
     "f3r_cloud_mark": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_vp]),
     "f3r_cloud_gather": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "f3r_render_clear": (ctypes.c_int, [_c_vp, ctypes.c_int, ctypes.c_int, _c_vp]),
+    "f3r_render_splat": (ctypes.c_int, [_c_vp, _c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                        _c_vp, _c_vp]),
+    "f3r_render_resolve": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, _c_vp, _c_vp, _c_vp]),
+    "f3r_render_center": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp]),
 }
 
 # entry points added after ABI_VERSION: {symbol: the f3r_version() that first exports it}.  lib() binds one only when the loaded library
 # reports that version; entry() is the one place that tells a caller of a later symbol to rebuild an older library.
 SYMBOL_SINCE = {name: 420 for name in SYMBOLS if name.startswith("f3r_cloud_")}
+SYMBOL_SINCE_430 = {name: 430 for name in SYMBOLS if name.startswith("f3r_render_")}  # the point-splat renderer
+
+
+def symbol_since(name: str) -> int:
+    """the f3r_version() that first exports `name`: the one lookup of lib() and entry() over the tables above (0: ABI_VERSION has it)"""
+    return SYMBOL_SINCE.get(name, SYMBOL_SINCE_430.get(name, 0))
+
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")
 if os.environ.get("F3R_LAB_LIB"):  # measurement builds only (tools/lab: kernels with ablation bits); never set by the product or the tests
@@ -199,7 +212,7 @@ class F3RError(RuntimeError):
     pass
 
 
-ABI_VERSION = 410  # the oldest f3r_version() lib() accepts; entry points of a later version are listed in SYMBOL_SINCE and reached through entry()
+ABI_VERSION = 410  # the oldest f3r_version() lib() accepts; entry points of a later version are listed in SYMBOL_SINCE / SYMBOL_SINCE_430 and reached through entry()
 
 
 def lib():
@@ -219,7 +232,7 @@ def lib():
         if l.f3r_version() < ABI_VERSION:
             raise F3RError(f"{LIB_PATH} is version {l.f3r_version()}, this host code needs >= {ABI_VERSION}: rebuild it (fast3r_amd/csrc/build.sh)")
         for name in SYMBOLS:
-            if SYMBOL_SINCE.get(name, 0) <= l.f3r_version():
+            if symbol_since(name) <= l.f3r_version():
                 bind(name)
         if l.f3r_sizeof(0) != ctypes.sizeof(GemmArgs) or l.f3r_sizeof(1) != ctypes.sizeof(AttnArgs) or l.f3r_sizeof(2) != ctypes.sizeof(AttnF32Args):
             raise F3RError("fast3r_amd/_lib.py struct layout does not match include/f3r.h "
@@ -234,9 +247,9 @@ def library_version() -> int:
 
 
 def entry(name: str):
-    """The bound entry point `name` of the loaded library; F3RError if that library predates it (SYMBOL_SINCE)."""
+    """The bound entry point `name` of the loaded library; F3RError if that library predates it (symbol_since)."""
     l = lib()
-    have, need = library_version(), SYMBOL_SINCE.get(name, 0)
+    have, need = library_version(), symbol_since(name)
     if have < need:
         raise F3RError(f"{LIB_PATH} is version {have}, {name} needs >= {need}: rebuild it (fast3r_amd/csrc/build.sh)")
     return getattr(l, name)

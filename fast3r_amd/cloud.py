@@ -39,13 +39,14 @@ SAMPLING_STRATEGIES = ("uniform", "voxel", "farthest_point")
 
 
 def combine_points(output_or_preds, views=None, *, pts3d_key_to_visualize="pts3d_local_aligned_to_global", conf_key_to_visualize="conf_local",
-                   min_conf_thr_percentile=0, flip_axes=False, sample=0):
+                   min_conf_thr_percentile=0, flip_axes=False, sample=0, return_offsets=False):
     """The first half of `export_combined_ply`: per view the pixels with conf > np.percentile(conf, min_conf_thr_percentile) -- strictly:
     at percentile 0 the minimum pixels drop, and a view of constant confidence keeps nothing; a view with a NaN confidence gets a NaN
     threshold and contributes nothing -- their colours trunc((img + 1.0f) * 127.5f) (two rounded fp32 operations, saturated), with
     `flip_axes` (x, y, z) -> (x, z, -y), stacked in view order then pixel order.  Takes what `inference()` returns ({'preds', 'views'}, host
     tensors: uploaded here) or (preds, views) with device tensors; views may differ in H x W.  -> (points (M, 3) fp32, colors (M, 3)
-    uint8) on the device, or (None, None) when nothing is kept.  Input tensors are never written."""
+    uint8) on the device, or (None, None) when nothing is kept.  With return_offsets a third entry follows: the end offset of every view in
+    the cloud (ascending Python ints; a view that keeps nothing repeats its predecessor's).  Input tensors are never written."""
     preds, views = preds_and_views(output_or_preds, views, "combine_points", "point colours")
     if not 0 <= min_conf_thr_percentile <= 100:
         raise ValueError(f"combine_points: min_conf_thr_percentile = {min_conf_thr_percentile} outside [0, 100]")
@@ -64,7 +65,7 @@ def combine_points(output_or_preds, views=None, *, pts3d_key_to_visualize="pts3d
         pts.append(fp32_on(pred[pts_key][sample], dev, (H * W, 3)))
         img.append(fp32_on(view["img"][sample], dev, (3, H * W)))   # the (3, H, W) planes as stored: nothing is permuted
         ranks.append(percentile_indexes(H * W, min_conf_thr_percentile))
-    return post_ops.cloud_combine(conf, pts, img, [None] * len(pts), shapes, ranks, flip_axes=flip_axes)
+    return post_ops.cloud_combine(conf, pts, img, [None] * len(pts), shapes, ranks, flip_axes=flip_axes, return_offsets=return_offsets)
 
 
 def _device_cloud(points, colors, who):

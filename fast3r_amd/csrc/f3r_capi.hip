@@ -24,7 +24,7 @@ int f3r_check_launch(const char* what) {
   return F3R_OK;
 }
 
-extern "C" int f3r_version(void) { return 420; /* 0.4.2: + point-cloud export (include/f3r.h f3r_version) */ }
+extern "C" int f3r_version(void) { return 430; /* 0.4.3: + point-splat renderer (include/f3r.h f3r_version) */ }
 
 extern "C" int f3r_wall_clock_khz(void) {
   int dev = 0, khz = 0;

@@ -1,5 +1,5 @@
 """Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
-loss, scene assembly, sky detection, mesh export and point-cloud export.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+loss, scene assembly, sky detection, mesh export, point-cloud export and the point-splat renderer.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
 out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
 """
 import ctypes
@@ -455,13 +455,15 @@ def mesh_ply_pack(vertices, faces, face_colors):
 
 
 # ------------------------------------------------------------------------------------------------------------------- point-cloud export
-def cloud_combine(conf, pts, img, mask, shapes, ranks, *, flip_axes=False, thresholds=None):
+def cloud_combine(conf, pts, img, mask, shapes, ranks, *, flip_axes=False, thresholds=None, return_offsets=False):
     """The kept pixels of a list of views as one cloud (f3r_mesh_threshold, then f3r_cloud_combine_count / _write, include/f3r.h).  Lists
     over views of GPU tensors, as mesh_build takes them: conf (H W,) fp32 or None (no threshold test), pts (H W, 3) fp32, img (3, H W) fp32
     planes or (H W, 3) uint8 colours, mask (H W,) uint8 (nonzero = keep) or None; shapes[i] = (H, W); ranks[i] = (k_lo, k_hi, gamma) of
     scene.percentile_indexes (ignored without conf).  A pixel is kept iff conf > the view's threshold and its mask byte is nonzero.
     thresholds: a (V,) fp32 device tensor to use instead of computing them.  -> (points (M, 3) fp32, colors (M, 3) uint8) on the device
-    in view order then pixel order, or (None, None) when nothing is kept.  The host reads back one word: the total."""
+    in view order then pixel order, or (None, None) when nothing is kept.  The host reads back one word: the total.  With return_offsets a
+    third entry follows: the V end offsets of the views in the cloud (ascending Python ints, read from the tile scan: V words read back
+    instead of one)."""
     V = len(pts)
     if V < 1 or not (len(conf) == len(img) == len(mask) == len(shapes) == len(ranks) == V):
         raise ValueError("cloud_combine: need one conf, pts, img, mask, shape and rank entry per view, and at least one view")
@@ -520,15 +522,19 @@ def cloud_combine(conf, pts, img, mask, shapes, ranks, *, flip_axes=False, thres
             check(l.f3r_mesh_threshold(ptr(table), V, ptr(thr), ptr(small[V:]), stream_ptr()), "f3r_mesh_threshold")
         thr_ptr = ptr(thr) if have_conf else None
         check(count(ptr(table), V, n_tiles, thr_ptr, ptr(scan), stream_ptr()), "f3r_cloud_combine_count")
-        total = int(scan[n_tiles].item()) & 0xffffffff
+        if return_offsets:  # the scan at a view's first tile is the view's first slot: the next view's is its end
+            ends = [int(e) & 0xffffffff for e in scan[torch.tensor(starts[1:], device=dev)].tolist()]
+            total = ends[-1]
+        else:
+            total = int(scan[n_tiles].item()) & 0xffffffff
         if total == 0:
-            return None, None
+            return (None, None, ends) if return_offsets else (None, None)
         out_p = torch.empty((total, 3), dtype=f32, device=dev)
         out_c = torch.empty((total, 3), dtype=u8, device=dev)
         check(write(ptr(table), V, n_tiles, thr_ptr, ptr(scan), int(bool(flip_axes)), ptr(out_p), ptr(out_c), stream_ptr()),
               "f3r_cloud_combine_write")
     del keep, table  # the launches are stream-ordered before the caching allocator can hand these blocks out again
-    return out_p, out_c
+    return (out_p, out_c, ends) if return_offsets else (out_p, out_c)
 
 
 def _cloud_points(points, who, colors=None):
@@ -678,3 +684,90 @@ def cloud_gather(points, colors, index):
         check(fn(ptr(points), ptr(colors), ptr(index), int(index.dtype == torch.int64), n, m, ptr(out_p), ptr(out_c), stream_ptr()),
               "f3r_cloud_gather")
     return out_p, out_c
+
+
+# ------------------------------------------------------------------------------------------------------------------- point-splat renderer
+def _render_viewport(width, height, who):
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or width * height >= 2 ** 31:
+        raise ValueError(f"{who}: viewport {width} x {height}; need width, height >= 1 and width * height < 2^31")
+    return width, height
+
+
+def _render_cloud(points, who, colors=None):
+    require_gpu(points, "points")
+    n = points.shape[0] if points.dim() == 2 else -1
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or not 1 <= n < 2 ** 32:
+        raise ValueError(f"{who}: points must be (1 <= n < 2^32, 3) fp32, got {tuple(points.shape)} {points.dtype}")
+    if colors is not None:
+        require_gpu(colors, "colors")
+        if tuple(colors.shape) != (n, 3) or colors.dtype != torch.uint8 or colors.device != points.device:
+            raise ValueError(f"{who}: colors must be ({n}, 3) uint8 on {points.device}, got {tuple(colors.shape)} {colors.dtype} on {colors.device}")
+        colors = colors.contiguous()
+    return points.contiguous(), colors, n
+
+
+def render_keys(width, height, device):
+    """A cleared key buffer (f3r_render_clear): int64 (height, width) on `device`, every word all ones -- no point anywhere"""
+    fn = _lib.entry("f3r_render_clear")
+    width, height = _render_viewport(width, height, "render_keys")
+    keys = torch.empty((height, width), dtype=torch.int64, device=device)
+    require_gpu(keys, "keys")
+    with torch.cuda.device(keys.device):
+        check(fn(ptr(keys), width, height, stream_ptr()), "f3r_render_clear")
+    return keys
+
+
+def render_splat(points, n0, n1, camera, point_size, keys):
+    """Points [n0, n1) of the cloud (n, 3) fp32 go into `keys` (what render_keys returned; written in place) through `camera`, the 17
+    doubles of include/f3r.h (V row-major, sx, sy, cx, cy, znear) (f3r_render_splat).  Calls accumulate."""
+    fn = _lib.entry("f3r_render_splat")
+    points, _, n = _render_cloud(points, "render_splat")
+    require_gpu(keys, "keys")
+    if keys.dim() != 2 or keys.dtype != torch.int64 or not keys.is_contiguous() or keys.device != points.device:
+        raise ValueError(f"render_splat: keys must be a contiguous (height, width) int64 tensor on {points.device}, got {tuple(keys.shape)} "
+                         f"{keys.dtype} on {keys.device}")
+    height, width = keys.shape
+    _render_viewport(width, height, "render_splat")
+    cam = [float(c) for c in camera]
+    if len(cam) != 17:
+        raise ValueError(f"render_splat: camera must hold 17 numbers (V, sx, sy, cx, cy, znear), got {len(cam)}")
+    with torch.cuda.device(points.device):
+        check(fn(ptr(points), n, int(n0), int(n1), (ctypes.c_double * 17)(*cam), float(point_size), width, height, ptr(keys),
+                 stream_ptr()), "f3r_render_splat")
+
+
+def render_resolve(keys, colors, background=(255, 255, 255), *, return_depth=False):
+    """keys (height, width) int64 and the cloud's colours (n, 3) uint8 -> the (height, width, 3) uint8 picture, row 0 at the top, and with
+    return_depth the (height, width) fp32 depth, +inf where no point landed (f3r_render_resolve)"""
+    fn = _lib.entry("f3r_render_resolve")
+    require_gpu(keys, "keys")
+    require_gpu(colors, "colors")
+    n = colors.shape[0] if colors.dim() == 2 else -1
+    if (keys.dim() != 2 or keys.dtype != torch.int64 or not keys.is_contiguous() or colors.dim() != 2 or colors.shape[1] != 3
+            or colors.dtype != torch.uint8 or colors.device != keys.device or not 1 <= n < 2 ** 32):
+        raise ValueError(f"render_resolve: keys contiguous (height, width) int64 and colors (1 <= n < 2^32, 3) uint8 on one device, got "
+                         f"{tuple(keys.shape)} {keys.dtype} on {keys.device}, {tuple(colors.shape)} {colors.dtype} on {colors.device}")
+    bg = [int(b) for b in background]
+    if len(bg) != 3 or any(not 0 <= b <= 255 for b in bg):
+        raise ValueError(f"render_resolve: background = {background!r}; need three values in [0, 255]")
+    height, width = keys.shape
+    _render_viewport(width, height, "render_resolve")
+    colors = colors.contiguous()
+    image = torch.empty((height, width, 3), dtype=torch.uint8, device=keys.device)
+    depth = torch.empty((height, width), dtype=torch.float32, device=keys.device) if return_depth else None
+    with torch.cuda.device(keys.device):
+        check(fn(ptr(keys), ptr(colors), n, width, height, bg[0] | bg[1] << 8 | bg[2] << 16, ptr(image), ptr(depth), stream_ptr()),
+              "f3r_render_resolve")
+    return (image, depth) if return_depth else image
+
+
+def render_center(points):
+    """The mean of the cloud's coordinates as three Python floats: the fp64 sums of f3r_render_center (a fixed order: two runs give the same
+    bits), each divided by n on the host.  One readback of three doubles."""
+    fn = _lib.entry("f3r_render_center")
+    points, _, n = _render_cloud(points, "render_center")
+    buf = torch.empty((_lib.RENDER_CENTER_PARTS + 1) * 3, dtype=torch.float64, device=points.device)
+    with torch.cuda.device(points.device):
+        check(fn(ptr(points), n, ptr(buf[3:]), ptr(buf), stream_ptr()), "f3r_render_center")
+    return [s / n for s in buf[:3].tolist()]

@@ -48,7 +48,7 @@ typedef enum { F3R_LOSS_DIS = 0, F3R_LOSS_LOG1P = 1 } f3r_loss_dis_mode; /* avg_
 #define F3R_MAX_SEG 8
 
 /* library version (major*10000 + minor*100 + patch) and last error text of the calling thread */
-int f3r_version(void);  /* 420 = 0.4.2 (+ f3r_cloud_combine_count, f3r_cloud_combine_write, f3r_cloud_bounds, f3r_cloud_voxel_workspace_bytes, f3r_cloud_voxel_sort, f3r_cloud_voxel_sums, f3r_cloud_fps_workspace_bytes, f3r_cloud_fps, f3r_cloud_mark, f3r_cloud_gather); 410 = 0.4.1 (+ f3r_mesh_threshold, f3r_mesh_count, f3r_mesh_write, f3r_mesh_ply_pack, f3r_mesh_workspace_bytes); 400 = 0.4.0 (+ f3r_sky_detect, f3r_sky_workspace_bytes); 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
+int f3r_version(void);  /* 430 = 0.4.3 (+ f3r_render_clear, f3r_render_splat, f3r_render_resolve, f3r_render_center); 420 = 0.4.2 (+ f3r_cloud_combine_count, f3r_cloud_combine_write, f3r_cloud_bounds, f3r_cloud_voxel_workspace_bytes, f3r_cloud_voxel_sort, f3r_cloud_voxel_sums, f3r_cloud_fps_workspace_bytes, f3r_cloud_fps, f3r_cloud_mark, f3r_cloud_gather); 410 = 0.4.1 (+ f3r_mesh_threshold, f3r_mesh_count, f3r_mesh_write, f3r_mesh_ply_pack, f3r_mesh_workspace_bytes); 400 = 0.4.0 (+ f3r_sky_detect, f3r_sky_workspace_bytes); 390 = 0.3.9 (+ f3r_scene_*, f3r_ply_pack, f3r_color_range, f3r_color_to_u8); 380 = 0.3.8 (+ f3r_mv_conf_loss, f3r_mv_conf_loss_workspace_bytes); 370 = 0.3.7 (+ f3r_pose_pair_metrics, f3r_pose_error_stats); 360 = 0.3.6 (+ f3r_nn_*, f3r_estimate_normals, f3r_recon_stats, f3r_recon_prepare); 350 = 0.3.5, round 6 (F3R_SPLIT_X3F8, f3r_gemm_args.out_f8 / out_relu_f8 / fin_*, f3r_interp_bilinear_f8); 340 = 0.3.4, round 6 (+ f3r_block_workspace_bytes_ex; the library clears sched_counter per launch); 330 = 0.3.3, round 5 (f3r_attn_args.dbg_counters is uint32[8] incl. two clock sums; f3r_wall_clock_khz); 320 = 0.3.2, round 4 (+ f3r_attn_f32_mfma, head_dim 80 / 128 kernels); 310: f3r_attn_args.dbg_counters, f3r_gemm_args.kernel_sel 6; 300 = round 3; 200 = round 2 */
 const char* f3r_last_error_string(void);
 /* sizeof(f3r_gemm_args) (what == 0) / sizeof(f3r_attn_args) (what == 1) / sizeof(f3r_attn_f32_args) (what == 2): lets a foreign-language binding
    verify its struct layout before the first call; 0 for an unknown `what` */
@@ -738,6 +738,46 @@ int f3r_cloud_fps(const float* points, int64_t n, int64_t num_samples, int64_t s
 int f3r_cloud_mark(const int32_t* selected, int64_t num_samples, int64_t n, uint8_t* mask, f3r_stream_t stream);
 int f3r_cloud_gather(const float* points, const uint8_t* colors, const void* index, int index_i64, int64_t n, int64_t m, float* out_points,
                      uint8_t* out_colors, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Point-splat renderer (ABI 430): the pictures of render_cumulative_pts3d_viz of the reference's notebooks/demo_multiview.ipynb -- there a
+ * pyrender scene of GL points under a perspective camera with zfar = None, one scene and one GL context per frame; here a z-buffered splat
+ * of a device cloud.  Python: fast3r_amd/render.py.  Kernels: fast3r_amd/csrc/f3r_render.hip.
+ * `camera` is a HOST double [17]: V[3][4] row-major, the world-to-eye matrix (eye frame as OpenGL's: x right, y up, looking along -z);
+ *   sx = 1 / (aspect tan(yfov / 2)), sy = 1 / tan(yfov / 2); cx, cy, the principal point's offset in normalised device coordinates (0 for a
+ *   centred camera); znear.  The projection is infinite (no far plane).
+ * The arithmetic of one point (x, y, z) (fp32, widened), in fp64, every operation rounded on its own, in this order:
+ *   e_r = ((V[r][0] x + V[r][1] y) + V[r][2] z) + V[r][3] for r = x, y, z;  d = -e_z;
+ *   p_x = sx e_x + cx d;  p_y = sy e_y + cy d;                              (clip-space x and y; clip-space w is d)
+ *   the point is drawn iff d >= znear and |p_x| <= d and |p_y| <= d and (float)d is finite -- comparisons a NaN fails; a point whose centre
+ *     is outside the frustum is dropped even where its square would reach into the viewport (GL's rule for points);
+ *   x_w = (p_x / d + 1) (W / 2);  y_w = (p_y / d + 1) (H / 2);  h = point_size / 2;
+ *   it covers the columns i with x_w - h <= i + 0.5 and i + 0.5 < x_w + h, and the window rows j likewise with y_w, both within the
+ *     viewport: half-open, so an integer point_size covers that many pixels per axis.  Window row j is image row H - 1 - j.
+ * f3r_render_clear: keys (device uint64 [H][W], image order: row 0 is the top) = all ones, the empty key.
+ * f3r_render_splat: points [n0, n1) of the cloud (device fp32 [n][3]) are min-reduced into keys with 64-bit integer atomics:
+ *   key = ((uint64_t)bits of (float)d << 32) | point index.  The smallest key wins: the nearest point, at equal depth the lowest index
+ *   (GL_LESS for points drawn in index order).  Calls accumulate: after the ranges of views 0 .. i the keys are frame i of the cumulative
+ *   pictures.  A relaxed load of the current key skips the atomic where the point already loses (the minimum is monotone: the result is
+ *   the same).  n0 == n1 launches nothing.
+ * f3r_render_resolve: image (device bytes [H][W][3]) = the colour (device bytes [n][3], unchanged: the point path has no lighting) of the
+ *   point in the key's low word, or background (r | g << 8 | b << 16) where the key is all ones or names no point below n; depth
+ *   (device fp32 [H][W], or null) = the key's high word as a float, +inf where the pixel is empty.
+ * f3r_render_center: out (device double [3]) = the sum of the widened coordinates in a fixed order: min(ceil(n / 2048),
+ *   F3R_RENDER_CENTER_PARTS) workgroups of 256 threads, thread t of workgroup b adds points b 256 + t, (b + G) 256 + t, .. sequentially from
+ *   +0.0, then the xor butterfly over the wave and the waves in order; one workgroup adds the partials (device double
+ *   [F3R_RENDER_CENTER_PARTS][3], scratch) the same way.  The caller divides by n.  The bounding box is f3r_cloud_bounds.
+ * Limits, F3R_ERR_ARG before any launch: null pointers; W or H < 1, W H >= 2^31; n < 1 or n >= 2^32; n0 > n1 or n1 > n; point_size not
+ *   finite or <= 0; znear <= 0; a camera entry that is not finite.  No floating-point atomics: two runs give the same bits; inputs are
+ *   not written to.
+ */
+#define F3R_RENDER_CENTER_PARTS 1024
+int f3r_render_clear(uint64_t* keys, int W, int H, f3r_stream_t stream);
+int f3r_render_splat(const float* points, int64_t n, int64_t n0, int64_t n1, const double* camera, double point_size, int W, int H,
+                     uint64_t* keys, f3r_stream_t stream);
+int f3r_render_resolve(const uint64_t* keys, const uint8_t* colors, int64_t n, int W, int H, uint32_t background, uint8_t* image,
+                       float* depth, f3r_stream_t stream);
+int f3r_render_center(const float* points, int64_t n, double* partials, double* out, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
