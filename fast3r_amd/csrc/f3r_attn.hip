@@ -37,6 +37,7 @@
 // The variant study that led here (90 variants: other workgroup shapes, register staging, software-pipelined bodies, ping-pong,
 // ablations, per-section timers) lives in tools/lab/ and is built only into tools/lab/libf3r_hip_lab.so.
 #include "f3r_common.h"
+#include "f3r_dispatch.h"
 
 namespace {
 
@@ -368,51 +369,28 @@ __global__ __launch_bounds__(AT_NW * 64, 2) void attn_kernel(const f3r_attn_args
 }
 
 template <class T>
-int attn_launch(const f3r_attn_args& a, hipStream_t s) {
+int attn_launch(const f3r_attn_args& a, AttnFamily family, hipStream_t s) {
   const int64_t qblocks = (a.tq + AT_QB - 1) / AT_QB;
   F3R_REQUIRE(qblocks < (1ll << 31) && a.n_heads < 65536 && a.batch < 65536, "f3r_attn_fwd: grid too large");
   dim3 grid((unsigned)qblocks, (unsigned)a.n_heads, (unsigned)a.batch);
-  if (a.causal)
+  if (family == ATTN_HIP_CAUSAL)
     hipLaunchKernelGGL((attn_kernel<T, false, true>), grid, dim3(AT_NW * 64), 0, s, a);
-  else if (a.batch > 1)
+  else if (family == ATTN_HIP_BATCHED)
     hipLaunchKernelGGL((attn_kernel<T, true, false>), grid, dim3(AT_NW * 64), 0, s, a);
   else
     hipLaunchKernelGGL((attn_kernel<T, false, false>), grid, dim3(AT_NW * 64), 0, s, a);
   return f3r_check_launch("f3r_attn_fwd");
 }
 
-}  // namespace
+int attn_head_dim(const f3r_attn_args& a) { return a.head_dim == 0 ? 64 : a.head_dim; }
 
-// Which kernel f3r_attn_fwd takes for these arguments (reporting only: bench.py names the roofline kernel with it).
-extern "C" const char* f3r_attn_kernel_name(const f3r_attn_args* args) {
-  if (!args) return "";
-  const f3r_attn_args& a = *args;
-  const int hd = a.head_dim == 0 ? 64 : a.head_dim;
-  const char* why = "";
-  if (a.qk_planes == 2) return f3r_attn_asm_eligible(a, 0, &why) ? "f3r_attn_asm_qk3_f16 (hand-scheduled, three products per score block, csrc/asm/attn_gen.py)" : "";
-  if (a.qk_planes == 3) return f3r_attn_asm_eligible(a, 0, &why) ? "f3r_attn_asm_qk3f8_f16 (hand-scheduled, three products per score block, the corrections on the fp8 MFMA, csrc/asm/attn_gen.py)" : "";
-  if (a.kernel_sel != 1 && f3r_attn_asm_eligible(a, (a.kernel_sel == 2 || hd != 64) ? 0 : F3R_ATTN_ASM_MIN_KEYS, &why)) {
-    if (hd == 80) return a.dtype == F3R_F16 ? "f3r_attn_asm_d80_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_d80_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
-    if (hd == 128) return a.dtype == F3R_F16 ? "f3r_attn_asm_d128_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_d128_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
-    if (f3r_attn_asm_splits_tail(a))
-      return a.dtype == F3R_F16 ? "f3r_attn_asm_f16 + f3r_attn_asm_q256_f16 for the last round (hand-scheduled, csrc/asm/attn_gen.py)"
-                                : "f3r_attn_asm_bf16 + f3r_attn_asm_q256_bf16 for the last round (hand-scheduled, csrc/asm/attn_gen.py)";
-    if (f3r_attn_asm_uses_q256(a))
-      return a.dtype == F3R_F16 ? "f3r_attn_asm_q256_f16 (hand-scheduled, 256-query work items, csrc/asm/attn_gen.py)" : "f3r_attn_asm_q256_bf16 (hand-scheduled, 256-query work items, csrc/asm/attn_gen.py)";
-    return a.dtype == F3R_F16 ? "f3r_attn_asm_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
-  }
-  if (hd != 64) return "attn_generic_kernel (f3r_attn_generic.hip)";
-  return a.causal ? "attn_kernel<causal> (f3r_attn.hip)" : (a.batch > 1 ? "attn_kernel<batched> (f3r_attn.hip)" : "attn_kernel (f3r_attn.hip)");
-}
-
-extern "C" int f3r_attn_fwd(const f3r_attn_args* args, f3r_stream_t stream) {
-  F3R_REQUIRE(args != nullptr, "f3r_attn_fwd: null args");
-  const f3r_attn_args& a = *args;
+// every argument rule of f3r_attn_fwd
+int attn_validate(const f3r_attn_args& a) {
   F3R_REQUIRE(a.q && a.o, "f3r_attn_fwd: null q/o");
   F3R_REQUIRE(a.dtype == F3R_F16 || a.dtype == F3R_BF16, "f3r_attn_fwd: bad dtype %d", a.dtype);
   F3R_REQUIRE(a.n_heads > 0 && a.batch > 0 && a.tq >= 0, "f3r_attn_fwd: bad sizes");
   F3R_REQUIRE(a.n_seg >= 1 && a.n_seg <= F3R_MAX_SEG, "f3r_attn_fwd: n_seg %d out of range", a.n_seg);
-  const int hd = a.head_dim == 0 ? 64 : a.head_dim;
+  const int hd = attn_head_dim(a);
   F3R_REQUIRE(hd >= 16 && hd <= 128 && hd % 16 == 0, "f3r_attn_fwd: head_dim %d (a multiple of 16 up to 128)", a.head_dim);
   F3R_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldo % 4 == 0, "f3r_attn_fwd: ldq/ldk must be multiples of 8, ldo of 4");
   F3R_REQUIRE(a.qk_planes >= 0 && a.qk_planes <= 3, "f3r_attn_fwd: qk_planes %d", a.qk_planes);
@@ -448,26 +426,48 @@ extern "C" int f3r_attn_fwd(const f3r_attn_args* args, f3r_stream_t stream) {
   F3R_REQUIRE(a.kv_group >= 0 && (a.kv_group <= 1 || a.n_heads % a.kv_group == 0), "f3r_attn_fwd: kv_group %d does not divide n_heads %d", a.kv_group, a.n_heads);
   const int kv_heads = a.kv_group > 1 ? a.n_heads / a.kv_group : a.n_heads;
   F3R_REQUIRE(a.ldk >= kv_heads * hd * qkp, "f3r_attn_fwd: ldk < kv heads * head_dim");
-  if (a.state_in || a.state_out) {
-    F3R_REQUIRE(a.st_o && a.st_ml && (((uintptr_t)a.st_o) & 15) == 0 && (((uintptr_t)a.st_ml) & 15) == 0, "f3r_attn_fwd: state buffers null/misaligned");
-  }
-  F3R_REQUIRE(a.kernel_sel >= 0 && a.kernel_sel <= 2, "f3r_attn_fwd: kernel_sel %d", a.kernel_sel);
-  if (a.tq == 0) return F3R_OK;
+  F3R_REQUIRE(!(a.state_in || a.state_out) || (a.st_o && a.st_ml && al16(a.st_o) && al16(a.st_ml)), "f3r_attn_fwd: state buffers null/misaligned");
+  F3R_REQUIRE(a.kernel_sel >= ATTN_SEL_AUTO && a.kernel_sel <= ATTN_SEL_ASM, "f3r_attn_fwd: kernel_sel %d", a.kernel_sel);
+  return F3R_OK;
+}
+
+}  // namespace
+
+int f3r_attn_plan(const f3r_attn_args& a, AttnPlan* plan) {
+  *plan = AttnPlan{};
+  const int hd = attn_head_dim(a);
+  const bool planes = a.qk_planes >= 2;   // hi + lo planes of Q and K: one kernel per layout reads them, the hand-scheduled three-product one
+  const char* why = "kernel_sel 1";
+  auto unsupported = [&why](const char* fmt) { f3r_set_error(fmt, why); return F3R_ERR_UNSUPPORTED; };
+  // the hand-scheduled one-wave-per-SIMD kernels where the launch allows it (include/f3r.h); head_dim 64 by shape: from F3R_ATTN_ASM_MIN_KEYS keys on
+  const int64_t min_keys = (planes || a.kernel_sel == ATTN_SEL_ASM || hd != 64) ? 0 : F3R_ATTN_ASM_MIN_KEYS;
+  if (a.kernel_sel != ATTN_SEL_HIP && f3r_attn_asm_plan(a, min_keys, plan, &why)) return F3R_OK;
+  if (planes) return unsupported("f3r_attn_fwd: qk_planes 2 / 3 but the launch is not eligible for the hand-scheduled three-product kernel: %s");
+  if (a.kernel_sel == ATTN_SEL_ASM) return unsupported("f3r_attn_fwd: kernel_sel 2 (hand-scheduled kernel) but the launch is not eligible: %s");
+  plan->family = hd != 64 ? ATTN_GENERIC : (a.causal ? ATTN_HIP_CAUSAL : (a.batch > 1 ? ATTN_HIP_BATCHED : ATTN_HIP));
+  return F3R_OK;
+}
+
+// Which kernel f3r_attn_fwd takes for these arguments: the plan it would launch, as text (bench.py names the roofline kernel with it, the geometry
+// suite holds it to the restated launch rules).  "" for a call f3r_attn_plan refuses -- qk_planes 2 / 3 or kernel_sel 2 on a launch the
+// hand-scheduled kernels cannot take, qk_planes 2 / 3 with kernel_sel 1.  (The argument rules are not applied here.)
+extern "C" const char* f3r_attn_kernel_name(const f3r_attn_args* args) {
+  static const char* const hip[] = {"attn_kernel<causal> (f3r_attn.hip)", "attn_kernel<batched> (f3r_attn.hip)", "attn_kernel (f3r_attn.hip)", "attn_generic_kernel (f3r_attn_generic.hip)"};
+  AttnPlan p;
+  if (!args || f3r_attn_plan(*args, &p) != F3R_OK) return "";
+  return p.family == ATTN_ASM ? f3r_attn_asm_name(*args, p) : hip[p.family];   // (by AttnFamily)
+}
+
+extern "C" int f3r_attn_fwd(const f3r_attn_args* args, f3r_stream_t stream) {
+  F3R_REQUIRE(args != nullptr, "f3r_attn_fwd: null args");
+  const f3r_attn_args& a = *args;
+  AttnPlan p;
+  int rc = attn_validate(a);
+  if (rc != F3R_OK || a.tq == 0) return rc;
+  rc = f3r_attn_plan(a, &p);
+  if (rc != F3R_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (a.qk_planes >= 2) {   // hi + lo planes of Q and K: one kernel per layout reads them
-    const char* why = "";
-    if (a.kernel_sel != 1 && f3r_attn_asm_eligible(a, 0, &why)) return f3r_attn_asm_launch(a, s);
-    f3r_set_error("f3r_attn_fwd: qk_planes 2 / 3 but the launch is not eligible for the hand-scheduled three-product kernel: %s", a.kernel_sel == 1 ? "kernel_sel 1" : why);
-    return F3R_ERR_UNSUPPORTED;
-  }
-  if (a.kernel_sel != 1) {  // the hand-scheduled one-wave-per-SIMD kernel where the launch allows it (include/f3r.h)
-    const char* why = "";
-    if (f3r_attn_asm_eligible(a, (a.kernel_sel == 2 || hd != 64) ? 0 : F3R_ATTN_ASM_MIN_KEYS, &why)) return f3r_attn_asm_launch(a, s);
-    if (a.kernel_sel == 2) {
-      f3r_set_error("f3r_attn_fwd: kernel_sel 2 (hand-scheduled kernel) but the launch is not eligible: %s", why);
-      return F3R_ERR_UNSUPPORTED;
-    }
-  }
-  if (hd != 64) return f3r_attn_generic_launch(a, s);
-  return a.dtype == F3R_F16 ? attn_launch<F16>(a, s) : attn_launch<BF16>(a, s);
+  if (p.family == ATTN_ASM) return f3r_attn_asm_launch(a, p, s);
+  if (p.family == ATTN_GENERIC) return f3r_attn_generic_launch(a, s);
+  return a.dtype == F3R_F16 ? attn_launch<F16>(a, p.family, s) : attn_launch<BF16>(a, p.family, s);
 }

@@ -3,13 +3,11 @@
 // hipModuleLaunchKernel on the caller's stream (capturable in a hipGraph like any other launch).  f3r_attn_fwd (f3r_attn.hip)
 // decides per call whether a launch goes here (f3r_attn_args.kernel_sel, include/f3r.h).
 #include <cstddef>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 
 #include "f3r_common.h"
+#include "f3r_dispatch.h"
 
 extern "C" const unsigned char f3r_attn_asm_hsaco[];
 extern "C" const unsigned int f3r_attn_asm_hsaco_len;
@@ -43,114 +41,110 @@ static_assert(sizeof(f3r_attn_asm_args) == 344 && offsetof(f3r_attn_asm_args, se
               offsetof(f3r_attn_asm_args, sched) == 312 && offsetof(f3r_attn_asm_args, n_work) == 320,
               "must match ARG_SIZE / ARG_SEG / ARG_DBG / ARG_SCHED of attn_gen.py");
 
-// The code object is loaded once per DEVICE (hipModule handles are per device context): the only process-wide state of the library
-// besides the per-thread error string.  Any device index: the table grows on demand.
 // The generated kernels: head_dim 64 (512 queries per workgroup), 80 and 128 (256 queries per workgroup); HEAD_DIMS of attn_gen.py
-constexpr int kNumHd = 3;
-constexpr int kHd[kNumHd] = {64, 80, 128};
+constexpr int kNumHd = 3, kHd[kNumHd] = {64, 80, 128};
 int hd_index(int hd) {
   for (int i = 0; i < kNumHd; ++i)
     if (kHd[i] == hd) return i;
   return -1;
 }
-int qpw(int hd, int qk_planes = 1) { return (hd == 64 && qk_planes < 2) ? 4 : 2; }   // 32-query blocks per wave: AttnGen.QPW of csrc/asm/attn_gen.py
-constexpr int kQ256Qpw = 2;                                                            // ... of the 256-query form of head_dim 64: AttnGen(head_dim=64, qpw=2)
-int wave_rows(int hd, int qk_planes = 1) { return 32 * qpw(hd, qk_planes); }          // query rows of a wave: 128 at head_dim 64, 64 otherwise
-// query rows of a wave of the form a launch runs on.  A wave whose rows would run past the last query works on the LAST rows of that many
-// instead (attn_gen.py: s_sub_u32 tq, QW / s_min_u32): with fewer query rows than this the subtraction wraps and the wave reads and writes past tq.
-int form_wave_rows(int hd, int qk_planes, bool q256) { return q256 ? 32 * kQ256Qpw : wave_rows(hd, qk_planes); }
+// The work item of a generated kernel (AttnGen.QPW of csrc/asm/attn_gen.py: 32-query blocks per wave): four at head_dim 64, two everywhere else --
+// and in the q256 form of head_dim 64, AttnGen(head_dim=64, qpw=2), which a plan asks for with ATTN_ITEM_256.  A wave whose rows
+// (attn_item_wave_rows) would run past the last query works on the LAST rows of that many instead (attn_gen.py: s_sub_u32 tq, QW / s_min_u32): with
+// fewer query rows than a wave's the subtraction wraps and the wave reads and writes past tq.
+AttnItem native_item(int hd, int planes) { return (hd == 64 && planes < 2) ? ATTN_ITEM_512 : ATTN_ITEM_256; }
 
-struct DevKernels {
-  bool tried = false;
-  hipModule_t mod = nullptr;
-  hipFunction_t fn[kNumHd][2] = {};  // [head_dim index][F3R_F16, F3R_BF16]
-  hipFunction_t fn_qk3 = nullptr;    // head_dim 64, fp16, Q and K as hi + lo planes (f3r_attn_args.qk_planes = 2)
-  hipFunction_t fn_qk3f8 = nullptr;  // ... with the correction products on the fp8 MFMA (qk_planes = 3)
-  hipFunction_t fn_q256[2] = {};     // head_dim 64 with 256-query work items (two query blocks per wave): small launches (f3r_attn_asm_use_q256)
-};
-std::map<int, DevKernels> g_dev;
-std::mutex g_mu;
+// [head_dim index][F3R_F16, F3R_BF16]; head_dim 64, fp16 with Q and K as hi + lo planes (f3r_attn_args.qk_planes = 2) and with the correction products
+// on the fp8 MFMA (3); head_dim 64 with 256-query work items (two query blocks per wave): small launches (q256_wins)
+F3rCodeObject<10> g_kernels = {f3r_attn_asm_hsaco,
+                               {"f3r_attn_asm_f16", "f3r_attn_asm_bf16", "f3r_attn_asm_d80_f16", "f3r_attn_asm_d80_bf16", "f3r_attn_asm_d128_f16", "f3r_attn_asm_d128_bf16",
+                                "f3r_attn_asm_qk3_f16", "f3r_attn_asm_qk3f8_f16", "f3r_attn_asm_q256_f16", "f3r_attn_asm_q256_bf16"}};
 
-hipFunction_t get_fn(int dtype, int hd, int qk_planes = 1) {
-  int dev = 0;
-  const int hi = hd_index(hd);
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dtype < 0 || dtype > 1 || hi < 0) return nullptr;
-  if (qk_planes >= 2 && (hd != 64 || dtype != F3R_F16)) return nullptr;
-  std::lock_guard<std::mutex> lock(g_mu);
-  DevKernels& d = g_dev[dev];
-  if (!d.tried) {
-    d.tried = true;
-    if (hipModuleLoadData(&d.mod, f3r_attn_asm_hsaco) == hipSuccess) {
-      for (int i = 0; i < kNumHd; ++i)
-        for (int t = 0; t < 2; ++t) {
-          char name[48];
-          if (kHd[i] == 64)
-            snprintf(name, sizeof(name), "f3r_attn_asm_%s", t == F3R_F16 ? "f16" : "bf16");
-          else
-            snprintf(name, sizeof(name), "f3r_attn_asm_d%d_%s", kHd[i], t == F3R_F16 ? "f16" : "bf16");
-          if (hipModuleGetFunction(&d.fn[i][t], d.mod, name) != hipSuccess) d.fn[i][t] = nullptr;
-        }
-      if (hipModuleGetFunction(&d.fn_qk3, d.mod, "f3r_attn_asm_qk3_f16") != hipSuccess) d.fn_qk3 = nullptr;
-      if (hipModuleGetFunction(&d.fn_qk3f8, d.mod, "f3r_attn_asm_qk3f8_f16") != hipSuccess) d.fn_qk3f8 = nullptr;
-      if (hipModuleGetFunction(&d.fn_q256[F3R_F16], d.mod, "f3r_attn_asm_q256_f16") != hipSuccess) d.fn_q256[F3R_F16] = nullptr;
-      if (hipModuleGetFunction(&d.fn_q256[F3R_BF16], d.mod, "f3r_attn_asm_q256_bf16") != hipSuccess) d.fn_q256[F3R_BF16] = nullptr;
-    }
-    (void)hipGetLastError();
-  }
-  if (qk_planes == -256) return hd == 64 ? d.fn_q256[dtype] : nullptr;   // (internal code: the 256-query form of the head_dim-64 kernel)
-  return qk_planes == 3 ? d.fn_qk3f8 : qk_planes == 2 ? d.fn_qk3 : d.fn[hi][dtype];
+hipFunction_t get_fn(int dtype, int hi, int planes, AttnItem item) {
+  if (dtype < 0 || dtype > 1 || hi < 0) return nullptr;
+  const bool hd64 = kHd[hi] == 64;
+  if (planes >= 2) return (hd64 && dtype == F3R_F16) ? g_kernels.get(4 + planes) : nullptr;
+  if (item != native_item(kHd[hi], planes)) return hd64 ? g_kernels.get(8 + dtype) : nullptr;   // the 256-query form of the head_dim-64 kernel
+  return g_kernels.get(2 * hi + dtype);
 }
 
 bool pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 
-int num_cus();
-
-// Small launches at head_dim 64: 512-query work items do not always fill the chip -- N = 3 views are 96 items on 256 CUs.  The same kernel with two
-// query blocks per wave (256-query items, f3r_attn_asm_q256_*) has twice the items; an item takes 0.545 of a 512-query item's time on random,
-// sharply attending operands (profiles/r06_attn_q256_vs_q512_items_by_n.jsonl: N = 3 1.78x faster, N = 20 +7.5 %) but ~0.64 inside the model
-// on near-uniform attention, where the 512-query kernel never leaves its fast path (fusion-only N = 20 with default-init weights: 65.6 ms against
-// 63.0 ms, profiles/r06_q256_in_model_ab.jsonl).  So the form is taken only where the round count wins at the in-model ratio: launches of less
-// than HALF a round of 512-query items (N <= 4 views: 24.8 -> 24.3 ms end to end at N = 3).
-bool use_q256(const f3r_attn_args& a, int hd, int qkp) {
-  if (hd != 64 || qkp != 1) return false;
-  static const char* force = getenv("F3R_ATTN_Q256");   // measurement only: "0" = never, "1" = always (tools/kernel_bench.py); the product never sets it
-  if (force && (force[0] == '0' || force[0] == '1')) return force[0] == '1' && get_fn(a.dtype, hd, -256) != nullptr;
-  const int64_t cus = num_cus();
-  const int64_t hb = (int64_t)a.n_heads * a.batch;
-  const int64_t n512 = (a.tq + 511) / 512 * hb, n256 = (a.tq + 255) / 256 * hb;
+// Small launches at head_dim 64 on 256-query items (f3r_attn_asm_q256_*: twice the items, 0.64 of a 512-query item's time each inside the model):
+// taken where the round count wins at that ratio, i.e. below HALF a round of 512-query items.  Measurements: docs/kernels.md, "How a call picks its kernel".
+bool q256_wins(int64_t tq, int64_t hb, int64_t cus) {
+  const int64_t n512 = (tq + 511) / 512 * hb, n256 = (tq + 255) / 256 * hb;
   const double t512 = (double)((n512 + cus - 1) / cus), t256 = 0.64 * (double)((n256 + cus - 1) / cus);
-  return t256 < 0.97 * t512 && get_fn(a.dtype, hd, -256) != nullptr;
+  return t256 < 0.97 * t512;
 }
 
-int num_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8) cus = 256;
-  return cus;
+// The last, partly filled round of a head_dim-64 launch as a SECOND launch on 256-query items, when its r items are at most half a round: 2 r <= cus
+// items of 0.64 round time instead of a whole round (docs/kernels.md).  The main launch keeps whole query blocks x all heads x all batches, so its item
+// count is a multiple of cus exactly when its block count is a multiple of cus / gcd(cus, heads x batch).  -> the rows of the main launch, 0: one launch
+int64_t tail_split_rows(int64_t tq, int64_t hb, int64_t cus) {
+  const int64_t nqb = (tq + 511) / 512;
+  if (nqb * hb <= cus) return 0;   // less than a round: q256_wins decides for the whole launch
+  int64_t x = cus, y = hb;
+  while (y) { const int64_t t = x % y; x = y; y = t; }
+  const int64_t g = cus / x;       // query blocks per whole number of rounds
+  const int64_t nqb_main = nqb / g * g;
+  if (nqb_main == 0 || nqb_main == nqb) return 0;
+  if (nqb_main * hb / cus > 8) return 0;     // long launches: work stealing inside ONE launch beats a chip-wide join between two
+  const int64_t r = (nqb - nqb_main) * hb;   // items of the last round (< cus)
+  if (2 * r > cus) return 0;                 // the tail would need two rounds of 256-query items: 1.28 > 1
+  return nqb_main * 512;
+}
+
+// The launches of an eligible call: their rows and work items.  Every rule and measurement switch about the FORM of a hand-scheduled launch is
+// here, evaluated once per call; f3r_attn_asm_launch executes what this leaves in the plan and f3r_attn_asm_name formats it.
+void plan_launches(const f3r_attn_args& a, AttnPlan& p) {
+  const int hd = kHd[p.hd_index];
+  p.main.rows = a.tq;
+  p.main.item = native_item(hd, p.planes);
+  if (p.main.item != ATTN_ITEM_512 || get_fn(a.dtype, p.hd_index, p.planes, ATTN_ITEM_256) == nullptr) return;
+  // measurement only (tools/kernel_bench.py; the product never sets them): F3R_ATTN_Q256 = "0" never / "1" always the 256-query form, in one launch;
+  // F3R_ATTN_TAIL_SPLIT = "0": no second launch
+  static const char* force = getenv("F3R_ATTN_Q256");
+  static const char* split = getenv("F3R_ATTN_TAIL_SPLIT");
+  if (force && (force[0] == '0' || force[0] == '1')) {
+    if (force[0] == '1') p.main.item = ATTN_ITEM_256;
+    return;
+  }
+  const int64_t cus = f3r_device_cus(), hb = (int64_t)a.n_heads * a.batch;
+  // two launches: not with a carried softmax state (the sharded path compares its two-launch form against one launch), not with CUs reserved
+  const bool may_split = !(split && split[0] == '0') && !a.state_in && !a.state_out && a.reserve_cus <= 0;
+  const int64_t rows = may_split ? tail_split_rows(a.tq, hb, cus) : 0;
+  if (rows > 0) {
+    // the tail is a launch of its own: it needs at least one wave's rows of the form that takes it.  A shorter one -- tq = 8192 + 40 at 16 heads --
+    // stays in ONE launch of all the query blocks, whose partial last workgroup handles any number of rows
+    const AttnItem item = q256_wins(a.tq - rows, hb, cus) ? ATTN_ITEM_256 : ATTN_ITEM_512;
+    if (a.tq - rows >= attn_item_wave_rows(item)) {
+      p.main.rows = rows;   // (whole rounds of 512-query items: q256_wins never holds for them)
+      p.tail.rows = a.tq - rows;
+      p.tail.item = item;
+      return;
+    }
+  }
+  if (q256_wins(a.tq, hb, cus)) p.main.item = ATTN_ITEM_256;
 }
 
 }  // namespace
 
-// does an (eligible) launch take the 256-query form of the head_dim-64 kernel?  (f3r_attn_kernel_name)
-bool f3r_attn_asm_uses_q256(const f3r_attn_args& a) {
+// Can the hand-scheduled kernels take this launch?  *why names the first obstacle; an eligible launch leaves with its complete ATTN_ASM plan.
+bool f3r_attn_asm_plan(const f3r_attn_args& a, int64_t min_keys, AttnPlan* plan, const char** why) {
+  *why = "";
   const int hd = a.head_dim == 0 ? 64 : a.head_dim;
-  return use_q256(a, hd, a.qk_planes >= 2 ? a.qk_planes : 1);
-}
-
-// Can the hand-scheduled kernel take this launch?  *why names the first obstacle.
-bool f3r_attn_asm_eligible(const f3r_attn_args& a, int64_t min_keys, const char** why) {
-  static const char* none = "";
-  *why = none;
-  const int hd = a.head_dim == 0 ? 64 : a.head_dim;
-  if (hd_index(hd) < 0) { *why = "no generated kernel for this head_dim (64, 80, 128)"; return false; }
+  const int hi = hd_index(hd);
+  if (hi < 0) { *why = "no generated kernel for this head_dim (64, 80, 128)"; return false; }
   const int qkp = a.qk_planes >= 2 ? a.qk_planes : 1;
   if (qkp >= 2 && (hd != 64 || a.dtype != F3R_F16)) { *why = "qk_planes 2 / 3 need head_dim 64 and fp16"; return false; }
-  const int64_t wrows = wave_rows(hd, qkp);
+  const int64_t wrows = attn_item_wave_rows(native_item(hd, qkp));
   if (a.causal) { *why = "causal mask"; return false; }
   if (!a.q_prescaled) { *why = "q not pre-scaled"; return false; }
   if (a.tq < wrows) { *why = "fewer query rows than one wave takes (128 at head_dim 64, 64 otherwise)"; return false; }
   if (a.kv_group > 1 && !pow2(a.kv_group)) { *why = "kv_group not a power of two"; return false; }
   // (the three-product kernels index the parked state by sequence: rows [z tq, (z + 1) tq) -- they park it on every launch; the others at batch 1 only)
-  if ((a.state_in || a.state_out) && a.batch != 1 && a.qk_planes < 2) { *why = "carried softmax state with batch > 1"; return false; }
+  if ((a.state_in || a.state_out) && a.batch != 1 && qkp < 2) { *why = "carried softmax state with batch > 1"; return false; }
   int first = -1;
   int64_t keys = 0;
   for (int s = 0; s < a.n_seg; ++s) {
@@ -175,84 +169,43 @@ bool f3r_attn_asm_eligible(const f3r_attn_args& a, int64_t min_keys, const char*
   if (a.tq >= (1ll << 31) || a.n_heads >= 65536 || a.batch >= 65536) { *why = "grid too large"; return false; }
   // a code object that does not load on this device makes the launch INELIGIBLE (kernel_sel 0 then takes the general HIP kernel,
   // kernel_sel 2 reports why) instead of failing every fusion-attention call of the process
-  if (get_fn(a.dtype, hd, qkp) == nullptr) { *why = "the embedded code object could not be loaded on this device"; return false; }
+  if (get_fn(a.dtype, hi, qkp, native_item(hd, qkp)) == nullptr) { *why = "the embedded code object could not be loaded on this device"; return false; }
+  plan->family = ATTN_ASM;
+  plan->hd_index = hi;
+  plan->planes = qkp;
+  plan_launches(a, *plan);
   return true;
 }
 
-// The last, partly filled round of a head_dim-64 launch as 256-query items (round 6).  A launch of n 512-query items on `cus` persistent workgroups
-// takes ceil(n / cus) round times whatever the remainder r = n mod cus is: N = 20 views are 640 items = 2.5 rounds, N = 100 are 3 200 = 12.5 -- half
-// the chip idles through the last round.  When r <= cus / 2 the query blocks of that remainder go to a SECOND launch, which the rule above (use_q256)
-// then runs on the 256-query form: 2 r <= cus items of 0.64 round time each, i.e. the launch pair costs floor(n / cus) + 0.64 instead of
-// floor(n / cus) + 1 (fusion-only N = 20: -12 % on paper, -5.8 % measured; N = 320 is 40 full rounds and is left alone).  The main
-// launch keeps whole query blocks x all heads x all batches, so its item count is a multiple of cus exactly when its block count is a multiple of
-// cus / gcd(cus, heads x batch).  Not with a carried softmax state (the sharded path compares its two-launch form against one launch), not
-// with CUs reserved.  F3R_ATTN_TAIL_SPLIT=0 (measurement only) switches it off.
-static int64_t tail_split_rows(const f3r_attn_args& a, int hd, int qkp) {
-  if (hd != 64 || qkp != 1 || a.state_in || a.state_out || a.reserve_cus > 0) return 0;
-  static const char* off = getenv("F3R_ATTN_TAIL_SPLIT");
-  if (off && off[0] == '0') return 0;
-  static const char* force = getenv("F3R_ATTN_Q256");
-  if (force && (force[0] == '0' || force[0] == '1')) return 0;
-  if (get_fn(a.dtype, hd, -256) == nullptr) return 0;
-  const int64_t cus = num_cus(), hb = (int64_t)a.n_heads * a.batch;
-  const int64_t nqb = (a.tq + 511) / 512;
-  if (nqb * hb <= cus) return 0;   // less than a round: use_q256 decides for the whole launch
-  int64_t x = cus, y = hb;
-  while (y) { const int64_t t = x % y; x = y; y = t; }
-  const int64_t g = cus / x;       // query blocks per whole number of rounds
-  const int64_t nqb_main = nqb / g * g;
-  if (nqb_main == 0 || nqb_main == nqb) return 0;
-  // long launches: the end of the first launch is a chip-wide join, and the XCDs' clocks differ by up to 6 % under the power cap -- work stealing
-  // inside ONE launch lets the fast ones take the last round's items instead.  Measured at N = 100 (12 whole rounds + 128 items): 33.44 ms against
-  // 33.41 ms for one launch (profiles/r06_attn_last_round_split_ab.jsonl); fusion-only N = 20 (2 + 128): 1.540 against 1.635 ms.
-  if (nqb_main * hb / cus > 8) return 0;
-  const int64_t r = (nqb - nqb_main) * hb;   // items of the last round (< cus)
-  if (2 * r > cus) return 0;                 // the tail would need two rounds of 256-query items: 1.28 > 1
-  // the tail is a launch of its own: it needs at least one wave's rows of the form that takes it (use_q256 above: the 256-query form, 64 rows).
-  // A shorter one -- tq = 8192 + 40 at 16 heads -- stays in ONE launch of all the query blocks, whose partial last workgroup handles any number of
-  // rows (use_q256 picks its form like any other launch's).
-  f3r_attn_args t = a;
-  t.tq = a.tq - nqb_main * 512;
-  if (t.tq < form_wave_rows(hd, qkp, use_q256(t, hd, qkp))) return 0;
-  return nqb_main * 512;
+const char* f3r_attn_asm_name(const f3r_attn_args& a, const AttnPlan& p) {
+  const bool h = a.dtype == F3R_F16;
+  if (p.planes == 2) return "f3r_attn_asm_qk3_f16 (hand-scheduled, three products per score block, csrc/asm/attn_gen.py)";
+  if (p.planes == 3) return "f3r_attn_asm_qk3f8_f16 (hand-scheduled, three products per score block, the corrections on the fp8 MFMA, csrc/asm/attn_gen.py)";
+  if (kHd[p.hd_index] == 80) return h ? "f3r_attn_asm_d80_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_d80_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
+  if (kHd[p.hd_index] == 128) return h ? "f3r_attn_asm_d128_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_d128_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
+  if (p.tail.rows > 0)
+    return h ? "f3r_attn_asm_f16 + f3r_attn_asm_q256_f16 for the last round (hand-scheduled, csrc/asm/attn_gen.py)"
+             : "f3r_attn_asm_bf16 + f3r_attn_asm_q256_bf16 for the last round (hand-scheduled, csrc/asm/attn_gen.py)";
+  if (p.main.item == ATTN_ITEM_256)
+    return h ? "f3r_attn_asm_q256_f16 (hand-scheduled, 256-query work items, csrc/asm/attn_gen.py)" : "f3r_attn_asm_q256_bf16 (hand-scheduled, 256-query work items, csrc/asm/attn_gen.py)";
+  return h ? "f3r_attn_asm_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
 }
 
-bool f3r_attn_asm_splits_tail(const f3r_attn_args& a) {
-  const int hd = a.head_dim == 0 ? 64 : a.head_dim;
-  return tail_split_rows(a, hd, a.qk_planes >= 2 ? a.qk_planes : 1) > 0;
-}
-
-static int launch_one(const f3r_attn_args& a, hipStream_t stream);
-
-int f3r_attn_asm_launch(const f3r_attn_args& a, hipStream_t stream) {
-  const int hd = a.head_dim == 0 ? 64 : a.head_dim;
-  const int64_t rows = tail_split_rows(a, hd, a.qk_planes >= 2 ? a.qk_planes : 1);
-  if (rows <= 0) return launch_one(a, stream);
-  f3r_attn_args m = a, t = a;
-  m.tq = rows;
-  t.tq = a.tq - rows;
-  t.q = (const char*)a.q + rows * a.ldq * 2;
-  t.o = (char*)a.o + rows * a.ldo * 2;
-  const int rc = launch_one(m, stream);
-  return rc != F3R_OK ? rc : launch_one(t, stream);
-}
-
-static int launch_one(const f3r_attn_args& a, hipStream_t stream) {
-  const int hd = a.head_dim == 0 ? 64 : a.head_dim;
-  const int qkp = a.qk_planes >= 2 ? a.qk_planes : 1;
-  const bool q256 = use_q256(a, hd, qkp);
-  // (f3r_attn_asm_eligible checks the caller's tq; this one guards every launch the rules above derive from it)
-  F3R_REQUIRE(a.tq >= form_wave_rows(hd, qkp, q256), "f3r_attn_fwd: a hand-scheduled launch of %lld query rows, fewer than the %d of one wave", (long long)a.tq,
-              form_wave_rows(hd, qkp, q256));
-  hipFunction_t fn = get_fn(a.dtype, hd, q256 ? -256 : qkp);
+// one launch of the plan: query rows [row0, row0 + l.rows) on the work item l.item
+static int launch_one(const f3r_attn_args& a, const AttnPlan& p, int64_t row0, const AttnAsmLaunch& l, hipStream_t stream) {
+  const int hd = kHd[p.hd_index];
+  const int wave_rows = attn_item_wave_rows(l.item);
+  // (f3r_attn_asm_plan checks the caller's tq against a wave's rows; this one guards every launch of the plan)
+  F3R_REQUIRE(l.rows >= wave_rows, "f3r_attn_fwd: a hand-scheduled launch of %lld query rows, fewer than the %d of one wave", (long long)l.rows, wave_rows);
+  hipFunction_t fn = get_fn(a.dtype, p.hd_index, p.planes, l.item);
   if (!fn) {
     f3r_set_error("f3r_attn_fwd: the embedded hand-scheduled kernel could not be loaded on this device");
     return F3R_ERR_LAUNCH;
   }
   f3r_attn_asm_args k;
   memset(&k, 0, sizeof(k));
-  k.q = a.q;
-  k.o = a.o;
+  k.q = (const char*)a.q + row0 * a.ldq * 2;
+  k.o = (char*)a.o + row0 * a.ldo * 2;
   k.ldq_b = (uint32_t)(a.ldq * 2);
   k.ldk_b = (uint32_t)(a.ldk * 2);
   k.ldo_b = (uint32_t)(a.ldo * 2);
@@ -266,7 +219,7 @@ static int launch_one(const f3r_attn_args& a, hipStream_t stream) {
   k.st_ml = a.st_ml;
   k.st_o_ld_b = (uint32_t)a.n_heads * (uint32_t)hd * 4u;
   k.st_ml_ld_b = (uint32_t)a.n_heads * 16u;
-  k.tq = (uint32_t)a.tq;
+  k.tq = (uint32_t)l.rows;
   k.dbg = a.dbg_counters;
   for (int s = 0; s < a.n_seg; ++s) {
     if (a.seg_len[s] == 0) continue;
@@ -282,11 +235,11 @@ static int launch_one(const f3r_attn_args& a, hipStream_t stream) {
   // Work stealing (f3r_attn_args.sched_counter): one persistent workgroup per CU takes (q block, head, batch) items from a shared counter, so
   // the XCDs -- which the hardware feeds round-robin by workgroup id whatever their clocks -- finish together.  Worth it from two rounds of
   // workgroups on; the kernel's magic-number division needs item x period < 2^32.
-  const int64_t wg_rows = 4 * form_wave_rows(hd, qkp, q256);
-  const unsigned nx = (unsigned)((a.tq + wg_rows - 1) / wg_rows);
+  const int64_t wg_rows = 4 * wave_rows;
+  const unsigned nx = (unsigned)((l.rows + wg_rows - 1) / wg_rows);
   unsigned gx = nx, gy = (unsigned)a.n_heads, gz = (unsigned)a.batch;
   const uint64_t n_work = (uint64_t)nx * gy * gz, nxy = (uint64_t)nx * gy;
-  unsigned cus = (unsigned)num_cus();
+  unsigned cus = (unsigned)f3r_device_cus();
   // f3r_attn_args.reserve_cus: leave that many CUs to whatever else must become resident while this launch runs (a rank's local-shard launch
   // next to the exchange of the other ranks' K / V^T); the persistent form is then taken whenever there are more items than workgroups
   const unsigned reserve = a.reserve_cus > 0 ? (unsigned)a.reserve_cus : 0u;
@@ -318,4 +271,9 @@ static int launch_one(const f3r_attn_args& a, hipStream_t stream) {
     return F3R_ERR_LAUNCH;
   }
   return f3r_check_launch("f3r_attn_fwd(asm)");
+}
+
+int f3r_attn_asm_launch(const f3r_attn_args& a, const AttnPlan& p, hipStream_t stream) {
+  const int rc = launch_one(a, p, 0, p.main, stream);
+  return (rc != F3R_OK || p.tail.rows == 0) ? rc : launch_one(a, p, p.main.rows, p.tail, stream);
 }

@@ -90,31 +90,6 @@ __device__ __forceinline__ typename T::vec8 as_vec8(u32x4 v) {
   return __builtin_bit_cast(typename T::vec8, v);
 }
 
-// f3r_gemm256.hip: the 256x256-tile kernel behind f3r_gemm for large regular shapes
-bool f3r_gemm256_eligible(const f3r_gemm_args& a);   // can take the problem at all
-bool f3r_gemm256_preferred(const f3r_gemm_args& a);  // ... and is expected to be faster than the 128-tile kernel
-int f3r_gemm256_max_conv_k_tiles();                   // records of its K-tile table in LDS (TileCfg::TAB_ENTRIES): the most K-tiles a 3x3 convolution may have
-int f3r_gemm256_launch(const f3r_gemm_args& a, hipStream_t stream, int stagger);
-int f3r_gemm256_lab(const f3r_gemm_args& a, hipStream_t stream);  // -DF3R_GEMM_LAB builds only (tools/lab)
-
-// f3r_gemm_asm.hip: the hand-scheduled GEMM kernels (csrc/asm/gemm_gen.py) behind f3r_gemm
-bool f3r_gemm_asm_eligible(const f3r_gemm_args& a, const char** why);
-bool f3r_gemm_asm_preferred(int64_t tiles);  // does a launch of that many 256 x 256 tiles fill the persistent grid well enough?
-int f3r_gemm_asm_launch(const f3r_gemm_args& a, hipStream_t stream);
-bool f3r_gemm_asm_f8_eligible(const f3r_gemm_args& a, const char** why);   // F3R_SPLIT_W2F8: the kernels with the low plane in fp8
-int f3r_gemm_asm_f8_launch(const f3r_gemm_args& a, hipStream_t stream);
-bool f3r_gemm_asm_qkv_eligible(const f3r_gemm_args& a, const char** why);  // the QKV projection without rotary embedding, as two launches
-int f3r_gemm_asm_qkv_launch(const f3r_gemm_args& a, hipStream_t stream);
-
-// f3r_attn_asm.hip: the hand-scheduled attention kernel (csrc/asm/attn_gen.py) behind f3r_attn_fwd
-bool f3r_attn_asm_eligible(const f3r_attn_args& a, int64_t min_keys, const char** why);
-int f3r_attn_asm_launch(const f3r_attn_args& a, hipStream_t stream);
-bool f3r_attn_asm_uses_q256(const f3r_attn_args& a);   // the 256-query form of the head_dim-64 kernel (small launches)
-bool f3r_attn_asm_splits_tail(const f3r_attn_args& a); // two launches: whole rounds of 512-query items + the last, partly filled round as 256-query items
-
-// f3r_attn_generic.hip: head_dim != 64
-int f3r_attn_generic_launch(const f3r_attn_args& a, hipStream_t stream);
-
 // host-side error plumbing (f3r_capi.cpp)
 void f3r_set_error(const char* fmt, ...);
 int f3r_check_launch(const char* what);

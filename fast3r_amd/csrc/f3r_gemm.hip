@@ -14,9 +14,10 @@
 // makes every epilogue access (bias, residual, fp32/lowp stores) a 16 B / 8 B vector along n.  The V
 // third of the QKV epilogue swaps the roles so that a lane owns 4 consecutive tokens of one channel
 // and can write V transposed (vt[d][token]) with 8 B stores.
-#include <stdlib.h>
+#include <stdio.h>
 
 #include "f3r_common.h"
+#include "f3r_dispatch.h"
 #include "f3r_gemm_epi.h"
 
 namespace {
@@ -296,87 +297,56 @@ int dispatch(const f3r_gemm_args& a, hipStream_t stream) {
     case F3R_EPI_QKV: return glds ? launch<T, F3R_A_PLAIN, F3R_EPI_QKV, 1>(a, stream) : launch<T, F3R_A_PLAIN, F3R_EPI_QKV, 0>(a, stream);
     case F3R_EPI_CONVT: return launch<T, F3R_A_PLAIN, F3R_EPI_CONVT, 0>(a, stream);
   }
-  f3r_set_error("f3r_gemm: bad epi %d", a.epi);
-  return F3R_ERR_ARG;
+  F3R_REQUIRE(false, "f3r_gemm: bad epi %d", a.epi);
 }
 
-inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-inline bool al8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
-
-}  // namespace
-
-extern "C" int f3r_gemm(const f3r_gemm_args* args, f3r_stream_t stream) {
-  F3R_REQUIRE(args != nullptr, "f3r_gemm: null args");
-  const f3r_gemm_args& a = *args;
+// Every argument rule of f3r_gemm, each written once.  F3R_SPLIT_W2F8 (rows of [K fp16 | K fp8] on both operands, one kernel family: f3r_gemm_asm.hip) has a block
+// for what that layout alone asks; a C caller reaches the hand-scheduled epilogues only through here, so after it W2F8 meets the same epilogue rules as every split.
+int gemm_validate(const f3r_gemm_args& a) {
   F3R_REQUIRE(a.A && a.W, "f3r_gemm: null operand");
   F3R_REQUIRE(a.M >= 0 && a.N > 0, "f3r_gemm: bad M/N (%lld, %d)", (long long)a.M, a.N);
   F3R_REQUIRE(a.split >= F3R_SPLIT_NONE && a.split <= F3R_SPLIT_X3F8, "f3r_gemm: bad split %d", a.split);
-  if (a.split == F3R_SPLIT_W2F8) {  // rows of [K fp16 | K fp8] on both operands: one kernel family takes them (f3r_gemm_asm.hip), nothing else does
+  const bool w2f8 = a.split == F3R_SPLIT_W2F8;
+  if (w2f8) {  // 16-byte rows in and out, one output, fp16, no lab forms; the operand mode and everything else its kernels cannot do is for their eligibility to say
     F3R_REQUIRE(al16(a.A) && al16(a.W) && a.w_scale && (((uintptr_t)a.w_scale) & 3) == 0, "f3r_gemm: W2F8 needs 16-byte aligned A / W and w_scale");
     F3R_REQUIRE(a.K > 0 && a.K % 128 == 0 && a.Kpad == a.K, "f3r_gemm: W2F8 needs K = Kpad, a multiple of 128 (got %d / %d)", a.K, a.Kpad);
     F3R_REQUIRE(a.lda % 8 == 0 && a.lda * 2 >= (int64_t)a.K * 3, "f3r_gemm: W2F8 rows are [K fp16 | K fp8]: lda %lld must be >= 3 K / 2", (long long)a.lda);
-    F3R_REQUIRE(a.epi != F3R_EPI_GENERIC || a.out_f32 || a.out_lp, "f3r_gemm: no output");
     F3R_REQUIRE(!a.out_f8 && !a.out_relu_f8 && !a.fin_w, "f3r_gemm: W2F8 launches write one output (no out_f8 / out_relu_f8 / fin_w)");
-    // the checks the other splits get further down (a C caller reaches the hand-scheduled epilogues only through here: ADVICE r5)
-    F3R_REQUIRE((a.kernel_sel >= 0 && a.kernel_sel <= 7) || a.kernel_sel == 9, "f3r_gemm: bad kernel_sel %d", a.kernel_sel);
     F3R_REQUIRE(a.dtype == F3R_F16, "f3r_gemm: W2F8 corrects fp16 planes only (dtype %d)", a.dtype);
     F3R_REQUIRE(a.act >= F3R_ACT_NONE && a.act <= F3R_ACT_RELU, "f3r_gemm: bad act %d", a.act);
-    F3R_REQUIRE(a.N % 4 == 0 && (!a.bias || al16(a.bias)), "f3r_gemm: N %d must be a multiple of 4, bias 16-byte aligned", a.N);
     if (a.epi == F3R_EPI_GENERIC) {
-      F3R_REQUIRE(!a.out_f32 || (al16(a.out_f32) && a.ldo_f32 % 4 == 0 && a.ldo_f32 >= a.N), "f3r_gemm: out_f32 alignment/ld");
-      F3R_REQUIRE(!a.out_lp || (al16(a.out_lp) && a.ldo_lp % 8 == 0 && a.ldo_lp >= a.N), "f3r_gemm: out_lp alignment/ld");
-      F3R_REQUIRE(!a.res_f32 || (al16(a.res_f32) && a.ldr_f32 % 4 == 0 && a.ldr_f32 >= a.N), "f3r_gemm: res_f32 alignment/ld");
-    }
-    const char* why = "";
-    if (a.epi == F3R_EPI_QKV) {
-      F3R_REQUIRE(a.qkv_dq != 0 || a.N % 3 == 0, "f3r_gemm: QKV with three equal parts needs N %% 3 == 0 (got %d)", a.N);
-      {
-        const int Dq = a.qkv_dq ? a.qkv_dq : a.N / 3;
-        F3R_REQUIRE(Dq > 0 && Dq % 64 == 0 && a.N > Dq && (a.N - Dq) % 128 == 0, "f3r_gemm: QKV parts must be whole 64-wide heads (N %d, q %d)", a.N, Dq);
-      }  // q | k with the low plane in fp8, V^T (swapped operand roles) on two fp16 planes from W_aux
-      F3R_REQUIRE(a.q && a.k && a.vt && a.W_aux && al16(a.W_aux) && a.seq_len > 0 && a.M % a.seq_len == 0 && a.ldvt >= a.seq_len && a.act == F3R_ACT_NONE,
-                  "f3r_gemm: W2F8 QKV needs q, k, vt, W_aux (16-byte aligned), seq_len dividing M, no activation");
-      if (a.rope_cos) F3R_REQUIRE(a.rope_sin && a.rope_w > 0 && al16(a.rope_cos) && al16(a.rope_sin), "f3r_gemm: RoPE tables");
-      if (!f3r_gemm_asm_qkv_eligible(a, &why)) {
-        f3r_set_error("f3r_gemm: split W2F8 QKV but the launch is not eligible for the hand-scheduled kernel: %s", why);
-        return F3R_ERR_UNSUPPORTED;
-      }
-      return f3r_gemm_asm_qkv_launch(a, (hipStream_t)stream);
-    }
-    if (!f3r_gemm_asm_f8_eligible(a, &why)) {
-      f3r_set_error("f3r_gemm: split W2F8 (fp8 low plane) but the launch is not eligible for the hand-scheduled kernel: %s", why);
-      return F3R_ERR_UNSUPPORTED;
-    }
-    return f3r_gemm_asm_f8_launch(a, (hipStream_t)stream);
-  }
-  // the fp8 output planes and the fused DPT tail belong to the GENERIC epilogue (every other epilogue would silently ignore them)
-  F3R_REQUIRE(a.epi == F3R_EPI_GENERIC || (!a.out_f8 && !a.out_relu_f8 && !a.fin_w), "f3r_gemm: out_f8 / out_relu_f8 / fin_w need the generic epilogue (epi %d)", a.epi);
-  const int planes = a.split ? 2 : 1;
-  F3R_REQUIRE(a.Kpad > 0 && a.Kpad % (64 * planes) == 0, "f3r_gemm: Kpad %d must be a positive multiple of %d", a.Kpad, 64 * planes);
-  const int Kpad1 = a.Kpad / planes;
-  F3R_REQUIRE((a.split != F3R_SPLIT_X3 && a.split != F3R_SPLIT_X3F8) || (a.A_lo && al16(a.A_lo) && !a.a_relu), "f3r_gemm: X3 / X3F8 split needs A_lo (16-byte aligned) and no a_relu");
-  if (a.split == F3R_SPLIT_X3F8)  // fp16 high planes + fp8 correction planes: the 3x3 convolutions of the DPT head on the 256-tile kernel only
-    F3R_REQUIRE(a.a_mode == F3R_A_CONV3X3 && a.dtype == F3R_F16 && a.conv_C % 128 == 0 && a.w_scale && (((uintptr_t)a.w_scale) & 3) == 0,
-                "f3r_gemm: X3F8 needs a 3x3 convolution with conv_C %% 128 == 0 (got %d), fp16 planes and w_scale", a.conv_C);
-  F3R_REQUIRE((a.kernel_sel >= 0 && a.kernel_sel <= 7) || a.kernel_sel == 9 || a.kernel_sel >= 16, "f3r_gemm: bad kernel_sel %d", a.kernel_sel);
-  F3R_REQUIRE(a.N % 4 == 0, "f3r_gemm: N %d must be a multiple of 4", a.N);
-  F3R_REQUIRE(al16(a.A) && al16(a.W), "f3r_gemm: A/W must be 16-byte aligned");
-  F3R_REQUIRE(a.dtype == F3R_F16 || a.dtype == F3R_BF16, "f3r_gemm: bad dtype %d", a.dtype);
-  if (a.a_mode == F3R_A_PLAIN) {
-    F3R_REQUIRE(a.K > 0 && a.K % 8 == 0 && a.K <= Kpad1, "f3r_gemm: K %d must be a multiple of 8 and <= Kpad", a.K);
-    F3R_REQUIRE(a.lda % 8 == 0 && a.lda >= a.K, "f3r_gemm: lda %lld must be a multiple of 8 and >= K", (long long)a.lda);
-  } else if (a.a_mode == F3R_A_CONV3X3) {
-    F3R_REQUIRE(a.conv_C > 0 && a.conv_C % 8 == 0, "f3r_gemm: conv_C %d must be a multiple of 8", a.conv_C);
-    F3R_REQUIRE(Kpad1 == 9 * ((a.conv_C + 63) / 64) * 64, "f3r_gemm: conv Kpad %d != 9*roundup(C,64) per plane", a.Kpad);
-    F3R_REQUIRE(a.epi == F3R_EPI_GENERIC, "f3r_gemm: conv3x3 supports only the generic epilogue");
-    F3R_REQUIRE(a.conv_stride == 1 || a.conv_stride == 2, "f3r_gemm: conv stride %d", a.conv_stride);
-    F3R_REQUIRE(a.conv_OH == (a.conv_H + 2 - 3) / a.conv_stride + 1 && a.conv_OW == (a.conv_W + 2 - 3) / a.conv_stride + 1,
-                "f3r_gemm: conv output dims inconsistent");
-    F3R_REQUIRE(a.conv_OH > 0 && a.conv_OW > 0 && a.M % ((int64_t)a.conv_OH * a.conv_OW) == 0, "f3r_gemm: conv M not a multiple of OH*OW");
+      F3R_REQUIRE(!a.out_lp || (al16(a.out_lp) && a.ldo_lp % 8 == 0), "f3r_gemm: out_lp alignment/ld");
+      F3R_REQUIRE(!a.res_f32 || a.ldr_f32 >= a.N, "f3r_gemm: res_f32 alignment/ld");
+    }  // QKV: q | k with the low plane in fp8, V^T (swapped operand roles) on two fp16 planes from W_aux
+    F3R_REQUIRE(a.epi != F3R_EPI_QKV || (a.W_aux && al16(a.W_aux)), "f3r_gemm: W2F8 QKV needs W_aux (16-byte aligned)");
   } else {
-    f3r_set_error("f3r_gemm: bad a_mode %d", a.a_mode);
-    return F3R_ERR_ARG;
+    // the fp8 output planes and the fused DPT tail belong to the GENERIC epilogue (every other epilogue would silently ignore them)
+    F3R_REQUIRE(a.epi == F3R_EPI_GENERIC || (!a.out_f8 && !a.out_relu_f8 && !a.fin_w), "f3r_gemm: out_f8 / out_relu_f8 / fin_w need the generic epilogue (epi %d)", a.epi);
+    const int planes = a.split ? 2 : 1;
+    F3R_REQUIRE(a.Kpad > 0 && a.Kpad % (64 * planes) == 0, "f3r_gemm: Kpad %d must be a positive multiple of %d", a.Kpad, 64 * planes);
+    const int Kpad1 = a.Kpad / planes;
+    F3R_REQUIRE((a.split != F3R_SPLIT_X3 && a.split != F3R_SPLIT_X3F8) || (a.A_lo && al16(a.A_lo) && !a.a_relu), "f3r_gemm: X3 / X3F8 split needs A_lo (16-byte aligned) and no a_relu");
+    if (a.split == F3R_SPLIT_X3F8)  // fp16 high planes + fp8 correction planes: the 3x3 convolutions of the DPT head on the 256-tile kernel only
+      F3R_REQUIRE(a.a_mode == F3R_A_CONV3X3 && a.dtype == F3R_F16 && a.conv_C % 128 == 0 && a.w_scale && (((uintptr_t)a.w_scale) & 3) == 0,
+                  "f3r_gemm: X3F8 needs a 3x3 convolution with conv_C %% 128 == 0 (got %d), fp16 planes and w_scale", a.conv_C);
+    F3R_REQUIRE(al16(a.A) && al16(a.W), "f3r_gemm: A/W must be 16-byte aligned");
+    F3R_REQUIRE(a.dtype == F3R_F16 || a.dtype == F3R_BF16, "f3r_gemm: bad dtype %d", a.dtype);
+    if (a.a_mode == F3R_A_PLAIN) {
+      F3R_REQUIRE(a.K > 0 && a.K % 8 == 0 && a.K <= Kpad1, "f3r_gemm: K %d must be a multiple of 8 and <= Kpad", a.K);
+      F3R_REQUIRE(a.lda % 8 == 0 && a.lda >= a.K, "f3r_gemm: lda %lld must be a multiple of 8 and >= K", (long long)a.lda);
+    } else if (a.a_mode == F3R_A_CONV3X3) {
+      F3R_REQUIRE(a.conv_C > 0 && a.conv_C % 8 == 0, "f3r_gemm: conv_C %d must be a multiple of 8", a.conv_C);
+      F3R_REQUIRE(Kpad1 == 9 * ((a.conv_C + 63) / 64) * 64, "f3r_gemm: conv Kpad %d != 9*roundup(C,64) per plane", a.Kpad);
+      F3R_REQUIRE(a.epi == F3R_EPI_GENERIC, "f3r_gemm: conv3x3 supports only the generic epilogue");
+      F3R_REQUIRE(a.conv_stride == 1 || a.conv_stride == 2, "f3r_gemm: conv stride %d", a.conv_stride);
+      F3R_REQUIRE(a.conv_OH == (a.conv_H + 2 - 3) / a.conv_stride + 1 && a.conv_OW == (a.conv_W + 2 - 3) / a.conv_stride + 1,
+                  "f3r_gemm: conv output dims inconsistent");
+      F3R_REQUIRE(a.conv_OH > 0 && a.conv_OW > 0 && a.M % ((int64_t)a.conv_OH * a.conv_OW) == 0, "f3r_gemm: conv M not a multiple of OH*OW");
+    } else F3R_REQUIRE(false, "f3r_gemm: bad a_mode %d", a.a_mode);
   }
+  F3R_REQUIRE((a.kernel_sel >= GEMM_SEL_AUTO && a.kernel_sel <= GEMM_SEL_AUTO_NO_ASM) || a.kernel_sel == GEMM_SEL_ASM_SKEW || (a.kernel_sel >= GEMM_SEL_LAB && !w2f8),
+              "f3r_gemm: bad kernel_sel %d", a.kernel_sel);
+  F3R_REQUIRE(a.N % 4 == 0, "f3r_gemm: N %d must be a multiple of 4", a.N);
   if (a.epi == F3R_EPI_GENERIC) {
     F3R_REQUIRE(a.out_f32 || a.out_lp || a.fin_w, "f3r_gemm: no output");
     F3R_REQUIRE(!a.out_f32 || (al16(a.out_f32) && a.ldo_f32 % 4 == 0 && a.ldo_f32 >= a.N), "f3r_gemm: out_f32 alignment/ld");
@@ -391,61 +361,112 @@ extern "C" int f3r_gemm(const f3r_gemm_args* args, f3r_stream_t stream) {
                   "f3r_gemm: the fused head tail writes fin_pts / fin_conf only");
     }
     F3R_REQUIRE(!a.res_f32 || (al16(a.res_f32) && a.ldr_f32 % 4 == 0), "f3r_gemm: res_f32 alignment/ld");
-    F3R_REQUIRE(!a.res_lp || (al8(a.res_lp) && a.ldr_lp % 4 == 0), "f3r_gemm: res_lp alignment/ld");
-    F3R_REQUIRE(!a.res_lp2 || (al8(a.res_lp2) && a.ldr_lp2 % 4 == 0), "f3r_gemm: res_lp2 alignment/ld");
-    F3R_REQUIRE((!a.res_lp_lo || (a.res_lp && al8(a.res_lp_lo))) && (!a.res_lp2_lo || (a.res_lp2 && al8(a.res_lp2_lo))), "f3r_gemm: low residual planes need their high planes");
-    F3R_REQUIRE((!a.out_lp_lo || (a.out_lp && al8(a.out_lp_lo))) && (!a.out_relu || (al8(a.out_relu) && a.ldo_lp % 4 == 0 && a.ldo_lp >= a.N)) &&
-                (!a.out_relu_lo || (a.out_relu && al8(a.out_relu_lo))), "f3r_gemm: out_lp_lo / out_relu alignment");
-    F3R_REQUIRE(!a.rowadd || (al16(a.rowadd) && a.rowadd_div > 0), "f3r_gemm: rowadd alignment/div");
-    const int64_t ld_max = 1ll << 26;  // the epilogues address a row as 32-bit byte offsets: 15 rows * ld * 4 B < 2^32
-    F3R_REQUIRE((!a.out_f32 || a.ldo_f32 < ld_max) && (!a.out_lp || a.ldo_lp < ld_max) && (!a.res_f32 || (a.ldr_f32 >= 0 && a.ldr_f32 < ld_max)) &&
-                (!a.res_lp || (a.ldr_lp >= 0 && a.ldr_lp < ld_max)) && (!a.res_lp2 || (a.ldr_lp2 >= 0 && a.ldr_lp2 < ld_max)), "f3r_gemm: row strides must be < 2^26 elements");
-    F3R_REQUIRE(!a.bias || al16(a.bias), "f3r_gemm: bias alignment");
+    if (!w2f8) {  // (W2F8 has none of these terms: a launch that passes one is for f3r_gemm_asm_f8_eligible to refuse as unsupported)
+      F3R_REQUIRE(!a.res_lp || (al8(a.res_lp) && a.ldr_lp % 4 == 0), "f3r_gemm: res_lp alignment/ld");
+      F3R_REQUIRE(!a.res_lp2 || (al8(a.res_lp2) && a.ldr_lp2 % 4 == 0), "f3r_gemm: res_lp2 alignment/ld");
+      F3R_REQUIRE((!a.res_lp_lo || (a.res_lp && al8(a.res_lp_lo))) && (!a.res_lp2_lo || (a.res_lp2 && al8(a.res_lp2_lo))), "f3r_gemm: low residual planes need their high planes");
+      F3R_REQUIRE((!a.out_lp_lo || (a.out_lp && al8(a.out_lp_lo))) && (!a.out_relu || (al8(a.out_relu) && a.ldo_lp % 4 == 0 && a.ldo_lp >= a.N)) &&
+                  (!a.out_relu_lo || (a.out_relu && al8(a.out_relu_lo))), "f3r_gemm: out_lp_lo / out_relu alignment");
+      F3R_REQUIRE(!a.rowadd || (al16(a.rowadd) && a.rowadd_div > 0), "f3r_gemm: rowadd alignment/div");
+      const int64_t ld_max = 1ll << 26;  // the epilogues address a row as 32-bit byte offsets: 15 rows * ld * 4 B < 2^32
+      F3R_REQUIRE((!a.out_f32 || a.ldo_f32 < ld_max) && (!a.out_lp || a.ldo_lp < ld_max) && (!a.res_f32 || (a.ldr_f32 >= 0 && a.ldr_f32 < ld_max)) &&
+                  (!a.res_lp || (a.ldr_lp >= 0 && a.ldr_lp < ld_max)) && (!a.res_lp2 || (a.ldr_lp2 >= 0 && a.ldr_lp2 < ld_max)), "f3r_gemm: row strides must be < 2^26 elements");
+    }
   } else if (a.epi == F3R_EPI_QKV) {
     const int Dq = a.qkv_dq ? a.qkv_dq : a.N / 3;
     F3R_REQUIRE(a.qkv_dq != 0 || a.N % 3 == 0, "f3r_gemm: QKV with three equal parts needs N %% 3 == 0 (got %d)", a.N);
     F3R_REQUIRE(Dq > 0 && Dq % 64 == 0 && a.N > Dq && (a.N - Dq) % 128 == 0, "f3r_gemm: QKV parts must be whole 64-wide heads (N %d, q %d)", a.N, Dq);
-    F3R_REQUIRE(a.q && a.k && a.vt && al8(a.q) && al8(a.k) && al8(a.vt), "f3r_gemm: QKV outputs null/misaligned");
+    // (W2F8 stores 16 bytes: an output its kernels cannot address is for f3r_gemm_asm_qkv_eligible to refuse as unsupported)
+    F3R_REQUIRE(a.q && a.k && a.vt && (w2f8 || (al8(a.q) && al8(a.k) && al8(a.vt))), "f3r_gemm: QKV outputs null/misaligned");
     F3R_REQUIRE(a.seq_len > 0 && a.M % a.seq_len == 0 && a.ldvt >= a.seq_len, "f3r_gemm: QKV seq_len/ldvt");
     F3R_REQUIRE(a.act == F3R_ACT_NONE, "f3r_gemm: QKV has no activation");
-    F3R_REQUIRE(!a.bias || al16(a.bias), "f3r_gemm: bias alignment");
     if (a.rope_cos) F3R_REQUIRE(a.rope_sin && a.rope_w > 0 && al16(a.rope_cos) && al16(a.rope_sin), "f3r_gemm: RoPE tables");
-  } else if (a.epi == F3R_EPI_CONVT) {
+  } else if (a.epi == F3R_EPI_CONVT && !w2f8) {
     F3R_REQUIRE(a.out_lp && al8(a.out_lp), "f3r_gemm: CONVT needs out_lp");
     F3R_REQUIRE(a.ct_s > 0 && a.ct_cout > 0 && a.ct_cout % 4 == 0 && a.N == a.ct_s * a.ct_s * a.ct_cout, "f3r_gemm: CONVT N != s*s*cout");
     F3R_REQUIRE(a.ct_h > 0 && a.ct_w > 0 && a.M % ((int64_t)a.ct_h * a.ct_w) == 0, "f3r_gemm: CONVT M not a multiple of h*w");
-    F3R_REQUIRE(!a.bias || al16(a.bias), "f3r_gemm: bias alignment");
   }
-  hipStream_t s = (hipStream_t)stream;
-  // kernel_sel: 0 = by shape (256-tile kernel for the large, regular problems), 1 = 128-tile kernel, 2 / 3 = 256-tile kernel with /
-  // without the staggered wave rows (measurement; an ineligible shape is an error, not a silent fallback)
-  if (a.kernel_sel >= 16) return f3r_gemm256_lab(a, s);
+  F3R_REQUIRE(!a.bias || al16(a.bias), "f3r_gemm: bias alignment");
+  return F3R_OK;
+}
+
+}  // namespace
+
+int f3r_gemm_plan(const f3r_gemm_args& a, GemmPlan* plan) {
+  GemmPlan& p = *plan = GemmPlan{};
+  const int sel = a.kernel_sel;
+  const bool qkv = a.epi == F3R_EPI_QKV;
+  const char* why = "";
+  auto unsupported = [&why](const char* fmt) { f3r_set_error(fmt, why); return F3R_ERR_UNSUPPORTED; };
+  p.skew = sel == GEMM_SEL_ASM_SKEW;
+  if (a.split == F3R_SPLIT_W2F8) {  // one kernel family takes these rows (f3r_gemm_asm.hip): no second path, no fallback
+    p.family = qkv ? GEMM_ASM_QKV : GEMM_ASM_F8;
+    if (qkv ? f3r_gemm_asm_qkv_eligible(a, &why) : f3r_gemm_asm_f8_eligible(a, &why)) return F3R_OK;
+    return unsupported(qkv ? "f3r_gemm: split W2F8 QKV but the launch is not eligible for the hand-scheduled kernel: %s"
+                           : "f3r_gemm: split W2F8 (fp8 low plane) but the launch is not eligible for the hand-scheduled kernel: %s");
+  }
+  if (sel >= GEMM_SEL_LAB) {
+    p.family = GEMM_LAB;
+    p.lab = sel - GEMM_SEL_LAB;
+    return F3R_OK;
+  }
+  // the forms of the 256-tile kernel that kernel_sel 2 - 5 stand for
+  const bool forced256 = sel >= GEMM_SEL_256_STAGGER && sel <= GEMM_SEL_256_ALL_TILES;
+  p.stagger = sel != GEMM_SEL_256_LOCKSTEP;
+  p.all_tiles = sel == GEMM_SEL_256_ALL_TILES;
+  p.halves = f3r_gemm256_halves(a, sel == GEMM_SEL_256_NARROW ? 1 : (forced256 ? 2 : 0));
   if (a.split == F3R_SPLIT_X3F8 || a.fin_w) {  // one kernel family takes these (f3r_gemm256_f8.hip): no second path, no fallback
-    if (!f3r_gemm256_eligible(a)) {
-      f3r_set_error("f3r_gemm: split X3F8 / fin_w but the launch is not eligible for the 256-tile kernel (conv_C %% 64 (X3F8: 128) == 0, "
-                    "N %% 128 == 0 (fin_w: N == 128), operand below 4 GiB, at most %d K-tiles: 9 conv_C / 64 per plane product, of which X3 has three and "
-                    "X3F8 the equivalent of two)", f3r_gemm256_max_conv_k_tiles());
-      return F3R_ERR_UNSUPPORTED;
-    }
-    return f3r_gemm256_launch(a, s, 1);
+    p.family = GEMM_256_F8FIN;
+    p.stagger = true;
+    p.merged = p.all_tiles && a.split == F3R_SPLIT_X3F8 && a.fin_w;
+    if (f3r_gemm256_eligible(a)) return F3R_OK;
+    f3r_set_error("f3r_gemm: split X3F8 / fin_w but the launch is not eligible for the 256-tile kernel (conv_C %% 64 (X3F8: 128) == 0, "
+                  "N %% 128 == 0 (fin_w: N == 128), operand below 4 GiB, at most %d K-tiles: 9 conv_C / 64 per plane product, of which X3 has three and "
+                  "X3F8 the equivalent of two)", f3r_gemm256_max_conv_k_tiles());
+    return F3R_ERR_UNSUPPORTED;
   }
-  // 6 = the hand-scheduled one-wave-per-SIMD kernel (csrc/asm/gemm_gen.py), an ineligible launch is an error; 0 takes it for the launches
-  // it is built for (the transformer's big linear layers: enough full 256 x 256 tiles to fill its persistent grid, f3r_gemm_asm_preferred);
-  // 7 = automatic WITHOUT it
-  if (a.kernel_sel == 6 || a.kernel_sel == 0 || a.kernel_sel == 9) {
-    const char* why = "";
-    // (QKV = two launches: q | k with 2/3 of the tiles, V^T with 1/3; the smaller one decides)
-    if (a.epi == F3R_EPI_QKV && f3r_gemm_asm_qkv_eligible(a, &why) && (a.kernel_sel == 6 || a.kernel_sel == 9 || f3r_gemm_asm_preferred((a.M / 256) * (a.N / 3 / 256))))
-      return f3r_gemm_asm_qkv_launch(a, s);
-    const bool ok = a.epi != F3R_EPI_QKV && f3r_gemm_asm_eligible(a, &why);
-    if ((a.kernel_sel == 6 || a.kernel_sel == 9) && !ok) {
-      f3r_set_error("f3r_gemm: kernel_sel 6 (hand-scheduled kernel) but the launch is not eligible: %s", why);
-      return F3R_ERR_UNSUPPORTED;
-    }
-    if (ok && (a.kernel_sel == 6 || a.kernel_sel == 9 || f3r_gemm_asm_preferred((a.M / 256) * (a.N / 256)))) return f3r_gemm_asm_launch(a, s);
+  // the hand-scheduled kernel: forced, or by shape where enough full 256 x 256 tiles fill its persistent grid (QKV = two launches: the smaller one, V^T, decides)
+  if (sel == GEMM_SEL_AUTO || sel == GEMM_SEL_ASM || sel == GEMM_SEL_ASM_SKEW) {
+    const bool forced = sel != GEMM_SEL_AUTO;
+    p.family = qkv ? GEMM_ASM_QKV : GEMM_ASM;
+    const bool ok = qkv ? f3r_gemm_asm_qkv_eligible(a, &why) : f3r_gemm_asm_eligible(a, &why);
+    if (ok && (forced || f3r_gemm_asm_preferred((a.M / 256) * (qkv ? a.N / 3 / 256 : a.N / 256)))) return F3R_OK;
+    if (forced) return unsupported("f3r_gemm: kernel_sel 6 (hand-scheduled kernel) but the launch is not eligible: %s");
   }
-  const int sel = a.kernel_sel == 7 ? 0 : a.kernel_sel;
-  if (sel >= 2) F3R_REQUIRE(f3r_gemm256_eligible(a), "f3r_gemm: kernel_sel %d but the shape is not eligible for the 256-tile kernel", sel);
-  if (sel >= 2 || (sel == 0 && f3r_gemm256_eligible(a) && f3r_gemm256_preferred(a))) return f3r_gemm256_launch(a, s, sel != 3);
-  return a.dtype == F3R_F16 ? dispatch<F16>(a, s) : dispatch<BF16>(a, s);
+  // the 256-tile kernel: forced, or by shape for the large, regular problems; the 128-tile kernel takes everything else
+  p.family = GEMM_128;
+  if (sel != GEMM_SEL_128) {
+    const bool ok = f3r_gemm256_eligible(a);
+    F3R_REQUIRE(!forced256 || ok, "f3r_gemm: kernel_sel %d but the shape is not eligible for the 256-tile kernel", sel);
+    if (forced256 || (ok && f3r_gemm256_preferred(a))) p.family = GEMM_256;
+  }
+  return F3R_OK;
+}
+
+const char* f3r_gemm_plan_name(const f3r_gemm_args& a) {
+  static const char* const family[] = {"gemm_kernel 128x128 (f3r_gemm.hip)", "gemm256_kernel", "gemm256_kernel (x3f8 / fused tail)", "f3r_gemm_asm",
+                                       "f3r_gemm_asm (w2f8)", "f3r_gemm_asm (qkv pair)", "gemm256_lab_kernel"};   // by GemmFamily
+  static thread_local char name[96];
+  GemmPlan p;
+  if (gemm_validate(a) != F3R_OK || f3r_gemm_plan(a, &p) != F3R_OK) return "";
+#ifndef F3R_GEMM_LAB
+  if (p.family == GEMM_LAB) return "";   // (f3r_gemm256_lab refuses it)
+#endif
+  if (p.family == GEMM_256 || p.family == GEMM_256_F8FIN)
+    snprintf(name, sizeof(name), "%s 256x%d %s%s%s", family[p.family], 128 * p.halves, p.stagger ? "staggered" : "lock-step", p.all_tiles ? ", one tile per workgroup" : "",
+             p.merged ? ", merged schedule" : "");
+  else
+    snprintf(name, sizeof(name), "%s%s", family[p.family], p.skew ? ", start skew" : "");
+  return name;
+}
+
+extern "C" int f3r_gemm(const f3r_gemm_args* args, f3r_stream_t stream) {
+  F3R_REQUIRE(args != nullptr, "f3r_gemm: null args");
+  const f3r_gemm_args& a = *args;
+  GemmPlan p;
+  int rc = gemm_validate(a);
+  if (rc == F3R_OK) rc = f3r_gemm_plan(a, &p);
+  if (rc != F3R_OK) return rc;
+  if (p.family == GEMM_128) return a.dtype == F3R_F16 ? dispatch<F16>(a, (hipStream_t)stream) : dispatch<BF16>(a, (hipStream_t)stream);
+  return p.family >= GEMM_ASM && p.family <= GEMM_ASM_QKV ? f3r_gemm_asm_launch(a, (hipStream_t)stream, p) : f3r_gemm256_launch(a, (hipStream_t)stream, p);
 }

@@ -2,8 +2,9 @@
 // (the bf16 ones live in f3r_gemm256_bf16.hip so that the two halves compile in parallel).
 #include "f3r_gemm256_impl.h"
 
-int f3r_gemm256_run_bf16(const f3r_gemm_args& a, hipStream_t stream, int stagger);  // f3r_gemm256_bf16.hip
-int f3r_gemm256_run_conv_f8_fin(const f3r_gemm_args& a, hipStream_t stream);         // f3r_gemm256_f8.hip
+int f3r_gemm256_run_bf16(const f3r_gemm_args& a, hipStream_t stream, const GemmPlan& plan);         // f3r_gemm256_bf16.hip
+int f3r_gemm256_run_conv_f8_fin(const f3r_gemm_args& a, hipStream_t stream, const GemmPlan& plan);  // f3r_gemm256_f8.hip
+int f3r_gemm256_lab(const f3r_gemm_args& a, hipStream_t stream, int lab);                           // f3r_gemm256_bf16.hip: -DF3R_GEMM_LAB builds only (tools/lab)
 
 // Whether the 256-tile kernel takes this (already validated) problem: everything its LDS-DMA staging cannot express -- K tails, ragged
 // channel counts, strided or pre-activated conv operands, small or narrow outputs, convolutions with more K-tiles than the K-tile table
@@ -41,14 +42,11 @@ bool f3r_gemm256_eligible(const f3r_gemm_args& a) {
 
 int f3r_gemm256_max_conv_k_tiles() { return TileCfg<1>::TAB_ENTRIES; }
 
-// Whether the 256-tile kernel (in the tile form tile_halves picks) is also the FASTER choice: one workgroup per CU, so with few tiles or
-// an unlucky tail round the 128-tile kernel (2 workgroups per CU, 4x the tiles) fills the chip better -- see tile_score.
-bool f3r_gemm256_preferred(const f3r_gemm_args& a) { return score_256(a, tile_halves(a)) >= score_128(a); }
-
-int f3r_gemm256_launch(const f3r_gemm_args& a, hipStream_t stream, int stagger) {
+int f3r_gemm256_launch(const f3r_gemm_args& a, hipStream_t stream, const GemmPlan& plan) {
+  if (plan.family == GEMM_LAB) return f3r_gemm256_lab(a, stream, plan.lab);
   const int64_t tiles = ((a.M + BM - 1) / BM) * ((a.N + 127) / 128);
   if (tiles <= 0) return F3R_OK;
   F3R_REQUIRE(tiles < (1ll << 31), "f3r_gemm: grid too large");
-  if (a.split == F3R_SPLIT_X3F8 || a.fin_w) return f3r_gemm256_run_conv_f8_fin(a, stream);
-  return a.dtype == F3R_F16 ? dispatch256<F16>(a, stream, stagger) : f3r_gemm256_run_bf16(a, stream, stagger);
+  if (plan.family == GEMM_256_F8FIN) return f3r_gemm256_run_conv_f8_fin(a, stream, plan);
+  return a.dtype == F3R_F16 ? dispatch256<F16>(a, stream, plan) : f3r_gemm256_run_bf16(a, stream, plan);
 }

@@ -28,9 +28,8 @@
 // Operand roles, epilogues, the split-precision K segments and the LDS swizzle are those of f3r_gemm.hip; the implicit-GEMM 3x3
 // convolution stages its operand by LDS-DMA too (buffer_load ... lds): out-of-image taps use an out-of-range offset and arrive as zeros.
 #pragma once
-#include <atomic>
-
 #include "f3r_common.h"
+#include "f3r_dispatch.h"
 #include "f3r_gemm_epi.h"
 
 
@@ -57,22 +56,6 @@ inline int conv_k_tiles(const f3r_gemm_args& a) {
   const int nk1 = Kpad1 / BK;
   const int nk8 = nk1 / 2;
   return a.split == F3R_SPLIT_X3F8 ? nk1 + 2 * nk8 : nseg * nk1;
-}
-
-inline int f3r_num_cus() {  // CUs of the CURRENT device, rounded down to a multiple of 8 (XCDs); cached per device index
-  constexpr int MAXD = 64;
-  static std::atomic<int> cache[MAXD];  // zero-initialised; a racing first call computes the same value twice
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-  if (dev >= 0 && dev < MAXD) {
-    const int c = cache[dev].load(std::memory_order_relaxed);
-    if (c) return c;
-  }
-  int cu = 0;
-  if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 8) cu = 256;
-  const int n = cu / 8 * 8;
-  if (dev >= 0 && dev < MAXD) cache[dev].store(n, std::memory_order_relaxed);
-  return n;
 }
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -741,7 +724,7 @@ __global__ __launch_bounds__(NT, 1) void gemm256_kernel(const f3r_gemm_args p) {
 }
 
 template <class T, int A_MODE, int EPI, int STAGGER, int ADDSRC, int NH, bool F8 = false, bool FIN = false, bool MERGED = false, int LAB = 0>
-int launch256(const f3r_gemm_args& a, hipStream_t stream) {
+int launch256(const f3r_gemm_args& a, hipStream_t stream, bool all_tiles) {
   static bool attr_set = false;  // benign race: idempotent
   auto kern = gemm256_kernel<T, A_MODE, EPI, STAGGER, ADDSRC, NH, F8, FIN, MERGED, LAB>;
   constexpr int LDS_BYTES = TileCfg<NH>::LDS_BYTES, BN = TileCfg<NH>::BN;
@@ -750,41 +733,19 @@ int launch256(const f3r_gemm_args& a, hipStream_t stream) {
     attr_set = true;
   }
   const int64_t tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-  // one resident workgroup per CU (128 / 144 KiB of LDS): a persistent grid of at most that many workgroups; kernel_sel 5 asks for the
-  // one-tile-per-workgroup form (measurements)
-  const int64_t grid = (a.kernel_sel == 5 || tiles <= f3r_num_cus()) ? tiles : f3r_num_cus();
+  // one resident workgroup per CU (128 / 144 KiB of LDS): a persistent grid of at most that many workgroups, or (GemmPlan::all_tiles,
+  // measurements) the one-tile-per-workgroup form
+  const int64_t grid = (all_tiles || tiles <= f3r_num_cus()) ? tiles : f3r_num_cus();
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), LDS_BYTES, stream, a);
   return f3r_check_launch("f3r_gemm(256)");
 }
 
-// 256-wide tiles when N fills them; 128-wide tiles when N is an odd multiple of 128 (no half-empty tile) -- QKV needs the wide tile
-// Which tile form fills the 256 CUs best.  score = (fraction of the last round's slots that do work, over all rounds) x (relative
-// main-loop efficiency of the form: 256x256 1.0, 256x128 0.82, 128x128 with two workgroups per CU 0.72 -- tools/kernel_bench.py
-// --what gemmsmall / gemm, profiles/r02_kernel_microbench_gemm_small.jsonl).  E.g. 8 views (M = 8192, N = 1024): 128 tiles of 256^2 = half a
-// round (0.50), 256 tiles of 256x128 = one full round (0.82), 512 tiles of 128^2 = one full round (0.72) -> 256x128.
-inline float tile_score(int64_t tiles, int slots, float eff) {
-  if (tiles <= 0) return 0.f;
-  const int64_t rounds = (tiles + slots - 1) / slots;
-  return eff * (float)tiles / (float)(rounds * slots);
-}
-inline float score_256(const f3r_gemm_args& a, int nh) {
-  return tile_score(((a.M + 255) / 256) * ((a.N + 128 * nh - 1) / (128 * nh)), 256, nh == 2 ? 1.0f : 0.82f);
-}
-inline float score_128(const f3r_gemm_args& a) { return tile_score(((a.M + 127) / 128) * ((a.N + 127) / 128), 512, 0.72f); }
-
-inline int tile_halves(const f3r_gemm_args& a) {
-  if (a.epi == F3R_EPI_QKV) return 2;
-  if (a.N % 256 != 0 || a.kernel_sel == 4) return 1;
-  if (a.kernel_sel == 2 || a.kernel_sel == 3 || a.kernel_sel == 5) return 2;
-  return score_256(a, 1) > score_256(a, 2) ? 1 : 2;
-}
-
 template <class T>
-int dispatch256(const f3r_gemm_args& a, hipStream_t stream, int stagger) {
-#define F3R_L256H(AM, EP, AD, NHV) (stagger ? launch256<T, AM, EP, 1, AD, NHV>(a, stream) : launch256<T, AM, EP, 0, AD, NHV>(a, stream))
+int dispatch256(const f3r_gemm_args& a, hipStream_t stream, const GemmPlan& plan) {
+#define F3R_L256H(AM, EP, AD, NHV) (plan.stagger ? launch256<T, AM, EP, 1, AD, NHV>(a, stream, plan.all_tiles) : launch256<T, AM, EP, 0, AD, NHV>(a, stream, plan.all_tiles))
 #define F3R_L256(AM, EP, AD) (nh == 2 ? F3R_L256H(AM, EP, AD, 2) : F3R_L256H(AM, EP, AD, 1))
   const int add = gemm_additive_pattern(a);
-  const int nh = tile_halves(a);
+  const int nh = plan.halves;
   if (a.a_mode == F3R_A_CONV3X3) return add == F3R_ADD_RES_LP ? F3R_L256(F3R_A_CONV3X3, F3R_EPI_GENERIC, F3R_ADD_RES_LP) : F3R_L256(F3R_A_CONV3X3, F3R_EPI_GENERIC, F3R_ADD_NONE);
   switch (a.epi) {
     case F3R_EPI_GENERIC:
