@@ -28,6 +28,36 @@ Structure (MI355X_MICROARCH.md "one wave per SIMD"; cdna_hip_programming.md appe
 LDS: ring of 4 tile slots x [K 8 KB | V^T 8 KB] (16-byte chunks XOR-swizzled by (row >> 1) & 7, K rows fed through pi = swap(bit 2, bit 3)),
 filled by global_load_lds_dwordx4.  One s_barrier per 64-key tile.
 
+The LDS ring, and one barrier per G tiles (AttnGen(tiles_per_barrier=G, pf=..., nslot=...); kernels f3r_attn_asm_{f16,bf16}_grp).  Each wave stages a
+quarter of every tile, so the four waves must meet -- but only often enough for the two rules below, not at every tile: between two barriers they
+drift freely.  (Measured, DESIGN.md section 6: what a boundary costs is the wait + barrier itself, in issue slots of the one wave a SIMD has, not
+jitter that would average out over a longer group: G = 2 realises 1.06 % of the 1.55 - 2.1 % the stream gains without any barrier, and only in the
+unrolled form below.)  Tile boundaries are numbered by the tile being entered (s_t counts the tiles of a work item from 0); the boundary of tile b carries the
+s_waitcnt vmcnt + s_barrier iff b is a multiple of G, and the prologue's barrier is that of tile 0.
+  * What a wave reads.  Computing tile t it reads tile t (K half 1 and V^T k-steps 0, 1 in stage A, V^T k-steps 2, 3 in stage B) and, in stage B, K half
+    0 of tile t + 1.  The V^T reads of stage B are requested before the boundary and retire at the first lgkmcnt(0) of tile t + 1.
+  * What a wave writes.  The LDS-DMA of tile x (into slot x mod nslot) is issued during tile x - pf (tiles 0 .. pf - 1 in the prologue), NP pieces per
+    wave and tile, retired in order; past the last tile the stream re-issues the last tile (same count, next slot), so the counts below hold to the end.
+  * Read after write.  Between the barrier of tile b = j G and the next one a wave reads tiles b .. b + G (the last one: K half 0 of tile b + G in stage
+    B of tile b + G - 1).  All of them must have landed for EVERY wave's quarter before the barrier of tile b, so each wave waits for its own pieces of
+    tiles .. b + G in front of it.  It has then issued tiles .. b - 1 + pf: the wait is vmcnt(NP (pf - 1 - G)) -- NP (pf - 2) at G = 1 -- in the
+    loop and in the prologue alike, and G + 1 <= pf.
+  * Write after read.  Between those two barriers the fastest wave gets to the end of tile b + G - 1 and has issued the LDS-DMA of tiles .. b + G - 1 + pf,
+    which may land at once.  The slowest wave has passed the barrier of tile b: it still reads tile b and has the stage-B V^T reads of tile b - 1 in
+    flight.  Tile b + G - 1 + pf must not share a slot with tile b: pf + G <= nslot.  This is the NON-STRICT form: counting the in-flight reads of tile
+    b - 1 as well would ask for pf + G <= nslot - 1.  The kernels have always taken the non-strict one (G = 1: pf <= nslot - 1, which the fp8-correction
+    kernel ships as pf = 3 on four slots): those reads were ISSUED by the slow wave before it arrived at the barrier of tile b, the LDS serves a CU's
+    reads in issue order within ~100 cycles, and the write that could hit their slot is issued by another wave only after it has left that barrier AND
+    walked G - 1 further tiles (2048 matrix-pipe cycles each), then makes a round trip to L2 before it touches LDS.  At G >= 2 the margin is wider than at
+    the shipped G = 1.  tests/test_attn_grouped_emu.py restates both rules as a model of the ring and holds the constructor's assertion to it.
+  * nslot = 4 admits G = 1 only (pf in 2 .. 3); nslot = 8: G = 1 (pf 2 .. 7), G = 2 (pf 3 .. 6), G = 3 (pf 4 .. 5); G = 4 would need 5 <= pf <= 4.
+  * The loop body is unrolled G times and the boundary of its last copy carries the wait and the barrier (grouped_loop): no counter, no branch.  Every
+    work item and every launch enters the loop at tile 0, and every wave of a workgroup walks the same tiles (a partial last workgroup re-aims its rows
+    at the last query rows, it does not leave): the barrier is uniform over the workgroup.  Nothing else
+    changes: the re-base path, seg_hop / next_segment_block, state park / resume, the work-stealing FETCH block (its own barriers say that every wave is
+    done with the ring), the counter block and the prologue's ring fill are the same instructions at every G.
+  * Head_dim 64, one product, 512-query items only: eight slots of the other kernels do not fit into 160 KiB.
+
 (Round 3 built this in two steps: a first layout with bias-step MFMAs, then this one; round 4 folded the shared argument block / register
 names of the first into this file and deleted its scheduler -- git history has it.)
 
@@ -106,7 +136,7 @@ s_mixrel = S(51)   # head_dim 80: LDS destination of the wave's mixed piece rela
 
 class AttnGen:
     def __init__(self, dtype="f16", rowsum="pkadd", big_gap=None, k8_gap=2, name=None, ablate=(), cvt="rne", dma_aux="", dma_start=8, dma_step=None, pf=None, nslot=4,
-                 fold="dot", head_dim=64, qk_planes=1, corr="f16", qk3_queues=True, k_hoist=True, qpw=None):
+                 fold="dot", head_dim=64, qk_planes=1, corr="f16", qk3_queues=True, k_hoist=True, qpw=None, tiles_per_barrier=1):
         assert dtype in ("f16", "bf16")
         assert head_dim in (64, 80, 128), "head widths with a generated kernel"
         # qk_planes = 2 (round 6, precision "robust"): Q and K rows hold [hi (64) | lo (64)] fp16 per head (x = hi + lo to ~22 bits) and Q K^T runs
@@ -153,8 +183,14 @@ class AttnGen:
             # tiles the LDS-DMA runs ahead.  The fp8-correction kernel walks a tile in 1536 matrix-pipe cycles instead of 2048: one tile of lead does
             # not cover an L2 round trip any more (measured on one box, profiles/r06_attn_qk3f8_prefetch_hoist_ab.jsonl: 2 -> 3 tiles +2.8 %)
             pf = 3 if corr == "f8" else 2
-        assert nslot in (4, 8) and 2 <= pf <= nslot - 1   # slots t, t+1 are read while t+2 .. t+pf land
+            if tiles_per_barrier > 1:
+                pf = tiles_per_barrier + 1
+        G = self.G = int(tiles_per_barrier)
+        # One s_barrier per G tiles (header: "The LDS ring").  G = 1 is the rule this line always held: 2 <= pf <= nslot - 1
+        assert nslot in (4, 8) and G >= 1 and G + 1 <= pf and pf + G <= nslot, "LDS ring: G + 1 <= pf (read after write) and pf + G <= nslot (write after read)"
         assert D == 64 or nslot == 4
+        # the grouped form exists for the 512-query kernel of head_dim 64 only (the other slots do not fit eight times into 160 KiB)
+        assert G == 1 or (D == 64 and qk_planes == 1 and self.QPW == 4)
         self.pf, self.nslot = pf, nslot
         self.fold = fold  # pkadd: how a stage's packed fp16 partial sums join the fp32 row sum: "dot" = v_dot2c, "mix" = 2 x v_fma_mix_f32
         self.LDS_X = nslot * self.SLOT     # one dword behind the ring: the work item a persistent workgroup fetched (wave 0 -> all waves)
@@ -211,6 +247,8 @@ class AttnGen:
         self.big_gap, self.k8_gap = (tuple(big_gap) if isinstance(big_gap, (tuple, list)) else (int(big_gap),)), k8_gap
         self.ablate = set(ablate)  # timing experiments only (wrong results): nosoftmax, nodma, nobarrier, nok8, noexp, nocvt, nosum
         self.name = name or (f"f3r_attn_asm_q256_{dtype}" if (D == 64 and qk_planes == 1 and self.QPW == 2) else f"f3r_attn_asm_qk3f8_{dtype}" if corr == "f8" else f"f3r_attn_asm_qk3_{dtype}" if qk_planes == 2 else f"f3r_attn_asm_{dtype}" if D == 64 else f"f3r_attn_asm_d{D}_{dtype}")
+        if name is None and G > 1:
+            self.name += "_grp"    # f3r_attn_asm_{f16,bf16}_grp: the grouped-barrier form on the 8-slot ring
         self.p = Program(self.name)
         if dtype == "f16":
             self.MFMA, self.MFMA8 = "v_mfma_f32_32x32x16_f16", "v_mfma_f32_32x32x8_f16"
@@ -543,7 +581,10 @@ class AttnGen:
             self.emit_all(self.seg_hop(i))
         e("s_add_u32", s_m0base, s_m0base, Lit(self.SLOT), comment="tile pf -> slot pf")
         self.emit_all(self.delta_for_tile())
-        e("s_waitcnt", f"vmcnt({self.NP * (self.pf - 2)})", comment="tiles 0 and 1 have landed")
+        if self.G == 1:
+            e("s_waitcnt", f"vmcnt({self.NP * (self.pf - 2)})", comment="tiles 0 and 1 have landed")
+        else:   # the barrier of tile 0 opens the first group: everything read before the barrier of tile G, i.e. tiles 0 .. G
+            e("s_waitcnt", f"vmcnt({self.NP * (self.pf - 1 - self.G)})", comment=f"tiles 0 .. {self.G} have landed")
         e("s_barrier")
         # ---- Q K^T(0) with no fillers, then the K fragments of half 1
         for ds in range(NK):
@@ -655,7 +696,7 @@ class AttnGen:
             e("s_mov_b32", s_seg_left, n_i)
             e("s_branch", self.L("SEG_DONE"))
         self.lab("SEG_DONE")
-        for code in range(self.pf + 1):
+        for code in range(self.pf + self.G):
             e("s_cmp_eq_u32", s_hopret, code)
             e("s_cbranch_scc1", self.L(f"HOPRET_{code}"))
         e("s_endpgm")
@@ -765,8 +806,8 @@ class AttnGen:
         regs = [KCUR + c for c in range(4)] + [VCUR, VCUR + 1] + ([self.KREM] if self.KREM is not None else []) if is_a else [VCUR + 2, VCUR + 3]
         return [I("v_add_u32", V(r), s_delta, V(r)) for r in regs]
 
-    def stage(self, kind):
-        """kind: 'A_first' (h = 0: Q K^T(1) only, the softmax of half 0 is the forced re-base), 'A' (h even), 'B' (h odd), 'B_last'
+    def stage(self, kind, hop_code=None):
+        """hop_code: the return code of this stage's segment hop (stage B; default pf, the unrolled loop of the grouped form: pf + copy).  kind: 'A_first' (h = 0: Q K^T(1) only, the softmax of half 0 is the forced re-base), 'A' (h even), 'B' (h odd), 'B_last'
         (no Q K^T).  Matrix-pipe order: P V(h-1) [2 QPW NDB MFMAs], then Q K^T(h+1) [QPW NK]."""
         I = self.I
         NK, NDB = self.NK, self.NDB
@@ -809,7 +850,7 @@ class AttnGen:
             dma = []
         tail += self.addr_tail(is_a)
         if kind == "B" and "nodma" not in self.ablate:
-            tail += self.seg_hop(self.pf)   # the stream advance of this stage may have used up the current K/V segment
+            tail += self.seg_hop(self.pf if hop_code is None else hop_code)   # the stream advance of this stage may have used up the current K/V segment
         flow = self.softmax_flow(e_cur) if do_sm else []
         if "nosoftmax" in self.ablate:
             flow = []
@@ -1134,19 +1175,9 @@ class AttnGen:
         self.lab("F_END")
         e("s_endpgm")
 
-    # ------------------------------------------------------------------ whole kernel
-    def build(self):
-        p, e = self.p, self.e
-        self.resume_labels = {0: [(0, "RESUME_A_FIRST"), (1, "RESUME_A")], 1: [(2, "RESUME_B"), (3, "RESUME_B_LAST")]}
-        self.prologue()
-        # ---- tile 0, stage A: Q K^T(1) only; the softmax of half 0 is the forced re-base
-        self.stage("A_first")
-        e("s_mov_b32", s_ret, 0)
-        e("s_branch", self.L("RARE_0"))
-        self.lab("RESUME_A_FIRST")
-        e("s_cmp_lt_u32", s_t, s_ntm1)
-        e("s_cbranch_scc0", self.L("LAST_B"))
-        p.items.append(Ins("s_nop", (0,), {}, "loop alignment"))
+    def plain_loop(self):
+        """one tile per trip: stage B of tile t, the boundary of tile t + 1 with its wait and barrier, stage A of tile t + 1"""
+        e = self.e
         self.lab("LOOP")
         self.stage("B")
         self.emit_all(self.check_block("RARE_1", 2))
@@ -1170,6 +1201,64 @@ class AttnGen:
         self.lab("RESUME_A")
         e("s_cmp_lt_u32", s_t, s_ntm1)
         e("s_cbranch_scc1", self.L("LOOP"))
+
+    def grouped_loop(self):
+        """G tiles per trip (header, "The LDS ring"): the loop body is unrolled G times and only the boundary of its LAST copy -- the one that enters a
+        tile whose index is a multiple of G: every work item and every launch enters the loop at tile 0 -- carries the wait and the barrier.  No
+        counter and no branch decide it (with one wave per SIMD every extra instruction at a boundary is an issue slot the matrix pipe waits for: a
+        first form that counted boundaries down in a scalar register and branched around the barrier gave most of the gain back), so the barrier
+        is uniform over the workgroup by construction: every wave walks the same tiles (a partial workgroup re-aims its rows, it does not leave).
+        A copy leaves for LAST_B when its tile was the last one; each copy has its own resume points of the re-base path and its own return code
+        of the segment hop."""
+        e = self.e
+        G = self.G
+        self.lab("LOOP")
+        for k in range(G):
+            code_a, code_b = (1, 2) if k == 0 else (2 + 2 * k, 3 + 2 * k)
+            self.stage("B", hop_code=self.pf + k)
+            self.emit_all(self.check_block("RARE_1", code_b))
+            self.emit_all(self.l_adds())
+            self.lab("RESUME_B" if k == 0 else f"RESUME_B_{k}")
+            if k == G - 1 and "nobarrier" not in self.ablate:
+                e("s_waitcnt", f"vmcnt({self.NP * (self.pf - 1 - G)})", comment=f"this wave's pieces of tiles .. t+1+{G} have landed")
+                e("s_barrier")
+            e("s_add_u32", s_t, s_t, 1)
+            e("s_add_u32", S(40), s_t, self.pf)
+            e("s_and_b32", S(40), S(40), self.nslot - 1)
+            self.mul_const(S(40), S(40), self.SLOT)
+            e("s_lshl_b32", S(41), s_wid, 11)
+            e("s_add_u32", s_m0base, S(40), S(41), comment="LDS-DMA destination of tile t+pf")
+            self.emit_all(self.delta_for_tile())
+            self.stage("A")
+            self.emit_all(self.check_block("RARE_0", code_a))
+            self.emit_all(self.l_adds())
+            self.lab("RESUME_A" if k == 0 else f"RESUME_A_{k}")
+            e("s_cmp_lt_u32", s_t, s_ntm1)
+            if k < G - 1:
+                e("s_cbranch_scc0", self.L("LAST_B"))
+            else:
+                e("s_cbranch_scc1", self.L("LOOP"))
+
+    # ------------------------------------------------------------------ whole kernel
+    def build(self):
+        p, e = self.p, self.e
+        self.resume_labels = {0: [(0, "RESUME_A_FIRST"), (1, "RESUME_A")], 1: [(2, "RESUME_B"), (3, "RESUME_B_LAST")]}
+        for k in range(1, self.G):   # the further copies of the grouped form's unrolled loop
+            self.resume_labels[0].append((2 + 2 * k, f"RESUME_A_{k}"))
+            self.resume_labels[1].append((3 + 2 * k, f"RESUME_B_{k}"))
+        self.prologue()
+        # ---- tile 0, stage A: Q K^T(1) only; the softmax of half 0 is the forced re-base
+        self.stage("A_first")
+        e("s_mov_b32", s_ret, 0)
+        e("s_branch", self.L("RARE_0"))
+        self.lab("RESUME_A_FIRST")
+        e("s_cmp_lt_u32", s_t, s_ntm1)
+        e("s_cbranch_scc0", self.L("LAST_B"))
+        p.items.append(Ins("s_nop", (0,), {}, "loop alignment"))
+        if self.G > 1:
+            self.grouped_loop()
+        else:
+            self.plain_loop()
         self.lab("LAST_B")
         self.stage("B_last")
         self.emit_all(self.check_block("RARE_1", 3))
@@ -1280,14 +1369,21 @@ def module_text(gens):
 HEAD_DIMS = (64, 80, 128)
 
 
-def product_generators(**kw):
-    """the kernels of the library: head_dim 64 first (f3r_attn_asm_{f16,bf16}), then f3r_attn_asm_d{80,128}_{f16,bf16}"""
+# f3r_attn_asm_{f16,bf16}_grp as the library ships them: the best of the admissible settings (profiles/attn_grouped_barrier_ab.jsonl, runs 3 and 4:
+# G = 2 beats G = 3, pf 3 .. 6 lie within 0.07 % of each other)
+GROUPED_RING = dict(tiles_per_barrier=2, pf=4, nslot=8)
+
+
+def product_generators(ring=None, **kw):
+    """the kernels of the library: head_dim 64 first (f3r_attn_asm_{f16,bf16}), then f3r_attn_asm_d{80,128}_{f16,bf16}, ... and last the grouped-barrier
+    form f3r_attn_asm_{f16,bf16}_grp.  ring (measurement builds): dict(tiles_per_barrier, pf, nslot) for EVERY 512-query head_dim-64 kernel of the
+    module, the plain symbols and the _grp ones, so that an A/B measures that ring whichever of the two the host picks; the other kernels keep theirs"""
     gens = []
     q3 = kw.pop("qk3_queues", True)
     kh = kw.pop("k_hoist", True)
     for hd in HEAD_DIMS:
         for dt in ("f16", "bf16"):
-            g = AttnGen(dt, head_dim=hd, **kw)
+            g = AttnGen(dt, head_dim=hd, **(dict(kw, name=f"f3r_attn_asm_{dt}", **ring) if (ring and hd == 64) else kw))
             g.build()
             gens.append(g)
     # round 6, precision "robust": head_dim 64 with Q and K as hi + lo fp16 planes, three products per Q K^T block (f3r_attn_asm_qk3_f16)
@@ -1300,6 +1396,10 @@ def product_generators(**kw):
         gens.append(g)
     for corr in ("f16", "f8"):   # f3r_attn_asm_qk3_f16 (three fp16 products) and f3r_attn_asm_qk3f8_f16 (the corrections on the block-scaled fp8 MFMA)
         g = AttnGen("f16", head_dim=64, qk_planes=2, corr=corr, qk3_queues=q3, k_hoist=kh, **kw3)
+        g.build()
+        gens.append(g)
+    for dt in ("f16", "bf16"):   # long key sequences on 512-query items (f3r_attn_asm.hip F3R_ATTN_GROUPED_MIN_KEYS): one barrier per group of tiles, 8-slot ring
+        g = AttnGen(dt, head_dim=64, **dict(kw, name=f"f3r_attn_asm_{dt}_grp", **(ring or GROUPED_RING)))
         g.build()
         gens.append(g)
     return gens
@@ -1320,13 +1420,19 @@ def main():
     ap.add_argument("--dma-step", type=int, default=6)
     ap.add_argument("--fold", default="dot")
     ap.add_argument("--layout", type=int, default=2, help="(accepted for old scripts; there is one layout)")
-    ap.add_argument("--pf", type=int, default=None)
-    ap.add_argument("--nslot", type=int, default=4)
+    ap.add_argument("--pf", type=int, default=None, help="tiles the LDS-DMA runs ahead (with --tiles-per-barrier / --nslot 8: of the 512-query head_dim-64 kernels only)")
+    ap.add_argument("--nslot", type=int, default=4, help="LDS ring slots; 8: the 512-query head_dim-64 kernels only (the other slots do not fit eight times)")
+    ap.add_argument("--tiles-per-barrier", type=int, default=None,
+                    help="G: one s_barrier per G key tiles in every 512-query head_dim-64 kernel of the module, the _grp symbols included (1 with --nslot 4: all of them the plain form)")
     ap.add_argument("--qk3-queues", type=int, default=1, help="three-product kernels: 0 = in-order filler placement (measurement)")
     ap.add_argument("--k-hoist", type=int, default=1, help="fp8-correction kernel: 0 = K fragments requested in the stage that multiplies them (measurement)")
     a = ap.parse_args()
     bg = None if a.big_gap is None else (tuple(int(x) for x in a.big_gap.split(",")) if "," in a.big_gap else int(a.big_gap))
-    gens = product_generators(rowsum=a.rowsum, big_gap=bg, k8_gap=a.k8_gap, ablate=[x for x in a.ablate.split(",") if x], cvt=a.cvt,
+    ring = None
+    if a.tiles_per_barrier is not None or a.nslot == 8:
+        ring = dict(tiles_per_barrier=a.tiles_per_barrier or 1, pf=a.pf, nslot=a.nslot)
+        a.pf, a.nslot = None, 4
+    gens = product_generators(ring=ring, rowsum=a.rowsum, big_gap=bg, k8_gap=a.k8_gap, ablate=[x for x in a.ablate.split(",") if x], cvt=a.cvt,
                               dma_aux=a.dma_aux, dma_start=a.dma_start, dma_step=a.dma_step, pf=a.pf, nslot=a.nslot, fold=a.fold, qk3_queues=bool(a.qk3_queues), k_hoist=bool(a.k_hoist))
     for g in gens:
         problems = g.p.check_hazards() if not a.ablate else []

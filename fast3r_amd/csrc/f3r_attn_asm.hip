@@ -55,16 +55,19 @@ int hd_index(int hd) {
 AttnItem native_item(int hd, int planes) { return (hd == 64 && planes < 2) ? ATTN_ITEM_512 : ATTN_ITEM_256; }
 
 // [head_dim index][F3R_F16, F3R_BF16]; head_dim 64, fp16 with Q and K as hi + lo planes (f3r_attn_args.qk_planes = 2) and with the correction products
-// on the fp8 MFMA (3); head_dim 64 with 256-query work items (two query blocks per wave): small launches (q256_wins)
-F3rCodeObject<10> g_kernels = {f3r_attn_asm_hsaco,
+// on the fp8 MFMA (3); head_dim 64 with 256-query work items (two query blocks per wave): small launches (q256_wins); head_dim 64 on 512-query items
+// with one barrier per group of key tiles on an 8-slot LDS ring (AttnGen(tiles_per_barrier=...)): long key sequences (F3R_ATTN_GROUPED_MIN_KEYS)
+F3rCodeObject<12> g_kernels = {f3r_attn_asm_hsaco,
                                {"f3r_attn_asm_f16", "f3r_attn_asm_bf16", "f3r_attn_asm_d80_f16", "f3r_attn_asm_d80_bf16", "f3r_attn_asm_d128_f16", "f3r_attn_asm_d128_bf16",
-                                "f3r_attn_asm_qk3_f16", "f3r_attn_asm_qk3f8_f16", "f3r_attn_asm_q256_f16", "f3r_attn_asm_q256_bf16"}};
+                                "f3r_attn_asm_qk3_f16", "f3r_attn_asm_qk3f8_f16", "f3r_attn_asm_q256_f16", "f3r_attn_asm_q256_bf16", "f3r_attn_asm_f16_grp",
+                                "f3r_attn_asm_bf16_grp"}};
 
-hipFunction_t get_fn(int dtype, int hi, int planes, AttnItem item) {
+hipFunction_t get_fn(int dtype, int hi, int planes, AttnItem item, bool grouped = false) {
   if (dtype < 0 || dtype > 1 || hi < 0) return nullptr;
   const bool hd64 = kHd[hi] == 64;
   if (planes >= 2) return (hd64 && dtype == F3R_F16) ? g_kernels.get(4 + planes) : nullptr;
   if (item != native_item(kHd[hi], planes)) return hd64 ? g_kernels.get(8 + dtype) : nullptr;   // the 256-query form of the head_dim-64 kernel
+  if (grouped) return hd64 ? g_kernels.get(10 + dtype) : nullptr;
   return g_kernels.get(2 * hi + dtype);
 }
 
@@ -97,7 +100,7 @@ int64_t tail_split_rows(int64_t tq, int64_t hb, int64_t cus) {
 
 // The launches of an eligible call: their rows and work items.  Every rule and measurement switch about the FORM of a hand-scheduled launch is
 // here, evaluated once per call; f3r_attn_asm_launch executes what this leaves in the plan and f3r_attn_asm_name formats it.
-void plan_launches(const f3r_attn_args& a, AttnPlan& p) {
+void plan_items(const f3r_attn_args& a, AttnPlan& p) {
   const int hd = kHd[p.hd_index];
   p.main.rows = a.tq;
   p.main.item = native_item(hd, p.planes);
@@ -126,6 +129,18 @@ void plan_launches(const f3r_attn_args& a, AttnPlan& p) {
     }
   }
   if (q256_wins(a.tq, hb, cus)) p.main.item = ATTN_ITEM_256;
+}
+
+// From F3R_ATTN_GROUPED_MIN_KEYS keys on (include/f3r.h), a 512-query launch at head_dim 64 (one product) runs the grouped-barrier kernel: f3r_attn_asm_*_grp
+// meets at one s_barrier per TWO 64-key tiles instead of one per tile, on an 8-slot LDS ring (128 KiB); per wave the same instructions on the same
+// numbers, so the results are bit for bit those of f3r_attn_asm_*.  Measured on one box, arms interleaved (profiles/attn_grouped_barrier_ab.jsonl):
+// -1.06 % per launch at 327 680 keys, -1.3 % at 102 400, -1.06 % at 40 960, -0.75 % at 20 480; at 8 192, the shortest launch measured, ahead in
+// all twelve grouped samples (mean -1.2 %, where two product runs in a row differ by 0.8 - 1.7 %): that is the threshold, nothing shorter was measured.
+// The 256-query launches (q256, the split tail) keep their kernel.  docs/kernels.md, "How a call picks its kernel".
+void plan_launches(const f3r_attn_args& a, int64_t keys, AttnPlan& p) {
+  plan_items(a, p);
+  if (kHd[p.hd_index] != 64 || p.planes != 1 || keys < F3R_ATTN_GROUPED_MIN_KEYS) return;
+  p.main.grouped = p.main.item == ATTN_ITEM_512;   // (a split tail is at most half a round of 512-query items: it always takes the 256-query form)
 }
 
 }  // namespace
@@ -173,7 +188,7 @@ bool f3r_attn_asm_plan(const f3r_attn_args& a, int64_t min_keys, AttnPlan* plan,
   plan->family = ATTN_ASM;
   plan->hd_index = hi;
   plan->planes = qkp;
-  plan_launches(a, *plan);
+  plan_launches(a, keys, *plan);
   return true;
 }
 
@@ -183,11 +198,17 @@ const char* f3r_attn_asm_name(const f3r_attn_args& a, const AttnPlan& p) {
   if (p.planes == 3) return "f3r_attn_asm_qk3f8_f16 (hand-scheduled, three products per score block, the corrections on the fp8 MFMA, csrc/asm/attn_gen.py)";
   if (kHd[p.hd_index] == 80) return h ? "f3r_attn_asm_d80_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_d80_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
   if (kHd[p.hd_index] == 128) return h ? "f3r_attn_asm_d128_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_d128_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
+  if (p.tail.rows > 0 && p.main.grouped)   // (a split tail is at most half a round: q256_wins holds for it, it is never a 512-query launch)
+    return h ? "f3r_attn_asm_f16_grp + f3r_attn_asm_q256_f16 for the last round (hand-scheduled, one barrier per group of key tiles, csrc/asm/attn_gen.py)"
+             : "f3r_attn_asm_bf16_grp + f3r_attn_asm_q256_bf16 for the last round (hand-scheduled, one barrier per group of key tiles, csrc/asm/attn_gen.py)";
   if (p.tail.rows > 0)
     return h ? "f3r_attn_asm_f16 + f3r_attn_asm_q256_f16 for the last round (hand-scheduled, csrc/asm/attn_gen.py)"
              : "f3r_attn_asm_bf16 + f3r_attn_asm_q256_bf16 for the last round (hand-scheduled, csrc/asm/attn_gen.py)";
   if (p.main.item == ATTN_ITEM_256)
     return h ? "f3r_attn_asm_q256_f16 (hand-scheduled, 256-query work items, csrc/asm/attn_gen.py)" : "f3r_attn_asm_q256_bf16 (hand-scheduled, 256-query work items, csrc/asm/attn_gen.py)";
+  if (p.main.grouped)
+    return h ? "f3r_attn_asm_f16_grp (hand-scheduled, one barrier per group of key tiles, csrc/asm/attn_gen.py)"
+             : "f3r_attn_asm_bf16_grp (hand-scheduled, one barrier per group of key tiles, csrc/asm/attn_gen.py)";
   return h ? "f3r_attn_asm_f16 (hand-scheduled, csrc/asm/attn_gen.py)" : "f3r_attn_asm_bf16 (hand-scheduled, csrc/asm/attn_gen.py)";
 }
 
@@ -197,7 +218,7 @@ static int launch_one(const f3r_attn_args& a, const AttnPlan& p, int64_t row0, c
   const int wave_rows = attn_item_wave_rows(l.item);
   // (f3r_attn_asm_plan checks the caller's tq against a wave's rows; this one guards every launch of the plan)
   F3R_REQUIRE(l.rows >= wave_rows, "f3r_attn_fwd: a hand-scheduled launch of %lld query rows, fewer than the %d of one wave", (long long)l.rows, wave_rows);
-  hipFunction_t fn = get_fn(a.dtype, p.hd_index, p.planes, l.item);
+  hipFunction_t fn = get_fn(a.dtype, p.hd_index, p.planes, l.item, l.grouped);
   if (!fn) {
     f3r_set_error("f3r_attn_fwd: the embedded hand-scheduled kernel could not be loaded on this device");
     return F3R_ERR_LAUNCH;

@@ -140,7 +140,11 @@ enum AttnItem {     // queries of a work item (a workgroup of four waves) of a h
   ATTN_ITEM_256,    // two: head_dim 80 / 128, the three-product kernels, and the q256 form of the head_dim-64 kernel
 };
 inline int attn_item_wave_rows(AttnItem item) { return item == ATTN_ITEM_512 ? 128 : 64; }
-struct AttnAsmLaunch { int64_t rows = 0; AttnItem item = ATTN_ITEM_512; };   // that many query rows (0: no such launch) on that work item
+struct AttnAsmLaunch {   // that many query rows (0: no such launch) on that work item
+  int64_t rows = 0;
+  AttnItem item = ATTN_ITEM_512;
+  bool grouped = false;   // ATTN_ITEM_512 at head_dim 64, one product: f3r_attn_asm_*_grp, one barrier per group of key tiles (F3R_ATTN_GROUPED_MIN_KEYS, f3r_attn_asm.hip)
+};
 // The launch(es) f3r_attn_fwd makes for an argument block.
 struct AttnPlan {
   AttnFamily family = ATTN_HIP;

@@ -310,7 +310,9 @@ typedef struct f3r_attn_args {
            multiple of 64 keys with one ldvt and one pair of batch strides, at least F3R_ATTN_ASM_MIN_KEYS keys in total, kv_group a
            power of two, batch 1 when the softmax state is carried (state_in / state_out; the state layout is the HIP kernel's, so
            the two kernels can resume each other's launches) -- and the general HIP kernel otherwise;
-       1 = the general HIP kernel;  2 = the hand-scheduled kernel (F3R_ERR_UNSUPPORTED if the launch is not eligible). */
+       1 = the general HIP kernel;  2 = the hand-scheduled kernel (F3R_ERR_UNSUPPORTED if the launch is not eligible).
+     Under 0 and 2 alike, a launch on 512-query items over at least F3R_ATTN_GROUPED_MIN_KEYS keys runs f3r_attn_asm_*_grp: the same arithmetic per
+     wave (results bit for bit those of f3r_attn_asm_*), one s_barrier per group of key tiles on an 8-slot LDS ring instead of one per tile. */
   int32_t kernel_sel;
   /* Width of a head: 0 or 64 = the tuned kernels; any other multiple of 16 up to 128 (the reference's Attention takes any dim //
      num_heads, blocks.py:113-143; its model_scaling_huge.yaml fusion decoder has 80): same layouts with head_dim columns per head
@@ -357,6 +359,7 @@ typedef struct f3r_attn_args {
   int32_t reserve_cus;
 } f3r_attn_args;
 #define F3R_ATTN_ASM_MIN_KEYS 2048
+#define F3R_ATTN_GROUPED_MIN_KEYS 8192
 
 int f3r_attn_fwd(const f3r_attn_args* args, f3r_stream_t stream);
 /* which kernel f3r_attn_fwd takes for `args` (a static string; reporting only) */

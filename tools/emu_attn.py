@@ -35,8 +35,10 @@ def pack_args(q, o, ldq, ldk, ldvt, ldo, segs, q_bs=0, o_bs=0, kv_shift=0, flags
 
 
 def run_case(dtype="f16", n_tiles=3, n_heads=2, wgs=((0, 1, 0),), spike=False, rowsum="pkadd", seed=0, batch=1, kv_shift=0, q_blocks=1,
-             gen_kwargs=None, split_state=False, layout=2, tq=None, counters=None, head_dim=64, steal=0, qk_planes=1, errs=None, corr="f16", finish_state=False, qpw=None):
-    """tq: number of query rows when it is not 512 * q_blocks (layout 2: the last workgroup may be partial; the buffers hold exactly tq
+             gen_kwargs=None, split_state=False, layout=2, tq=None, counters=None, head_dim=64, steal=0, qk_planes=1, errs=None, corr="f16", finish_state=False, qpw=None, outs=None):
+    """outs: a list that receives, per compared work item, the raw 16-bit output buffer as the launches left it (bit comparisons between generator
+    settings on the same operands: same seed, same arguments).
+    tq: number of query rows when it is not 512 * q_blocks (layout 2: the last workgroup may be partial; the buffers hold exactly tq
     rows, so a store past the end raises in the emulator's memory model).  counters: a list that receives the kernel's debug counters
     {re-base block entries, waves, tiles walked} (f3r_attn_args.dbg_counters; layout 2).  steal = G > 0: the work-stealing form -- G
     persistent workgroups share the launch's {next, done} counter (emulated one after the other: the first one takes every item, the others
@@ -147,6 +149,8 @@ def run_case(dtype="f16", n_tiles=3, n_heads=2, wgs=((0, 1, 0),), spike=False, r
             ml = mem.get(st_ml, np.float32, (batch, tq, n_heads, 4)).astype(np.float64)
             l = np.repeat(ml[..., 1] + ml[..., 2], HD, axis=-1)
             og = f32_to_half((so / l).astype(np.float32), dtype)
+        if outs is not None:
+            outs.append(np.array(og, copy=True))
         x, head, b = wg
         kvh = head >> kv_shift
         r1 = min(tq, (x + 1) * WQ)
