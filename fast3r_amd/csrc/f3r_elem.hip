@@ -63,8 +63,8 @@ __global__ void patchify_any_kernel(const float* __restrict__ img, uint16_t* __r
 }
 
 // ------------------------------------------------------------------------------------------ layernorm
-// one wave per row; D % 4 == 0; float4 loads; two-pass (mean, then centred variance) from registers when
-// D <= 2048 (8 float4 per lane), otherwise re-reads the row.
+// one wave per row; D % 4 == 0; float4 loads; two-pass (mean, then centred variance), the row read once and kept in registers at every
+// accepted width: MAXV float4 per lane = 4 (D <= 1024), 8 (D <= 2048) or 32 (D <= 8192), picked by the entry points.
 // ld_lp: row stride of out_lp in elements (D for the plain form).  F8: every row also gets an fp8 (e4m3) copy of the same values, clamped to
 // +-448 (v_cvt_pk_fp8_f32 turns anything larger into NaN: tools/ubench/mfma_scale_probe.py), D elements behind its start (f3r_split W2F8).
 template <class T, int MAXV, bool F8 = false>
