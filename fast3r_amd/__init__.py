@@ -15,3 +15,5 @@ from .mesh import Mesh, build_mesh, cat_meshes, generate_mesh_ply_bytes, pts3d_t
 from .cloud import combine_points, downsample_cloud, export_combined_ply, farthest_point_down_sample, voxel_down_sample  # noqa: F401
 from .sky import detect_sky_mask, detect_sky_masks, label_components  # noqa: F401
 from .render import Camera, birdseye_camera, pinhole_camera, render_cumulative_pts3d_viz, render_points  # noqa: F401
+from .viz import (CAM_COLORS, SceneViz, auto_cam_size, camera_meshes, plot_3d_points_with_estimated_camera_poses,  # noqa: F401
+                  render_mesh)

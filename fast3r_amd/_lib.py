@@ -28,6 +28,7 @@ F3R_INDEX_I32, F3R_INDEX_I64 = 0, 1
 # points per tile of the tiled farthest-point path; F3R_CLOUD_FPS_ONE_MAX: the most points its one-workgroup path takes
 CLOUD_TILE, CLOUD_SORT_TILE, CLOUD_FPS_TILE, CLOUD_FPS_ONE_MAX = 1024, 2048, 1024, 8192
 RENDER_CENTER_PARTS = 1024  # F3R_RENDER_CENTER_PARTS: rows of the scratch f3r_render_center takes
+RASTER_SMALL_PIXELS = 64  # F3R_RASTER_SMALL_PIXELS: the largest pixel box a stage-1 thread of the rasteriser draws itself
 F3R_FPS_AUTO, F3R_FPS_ONE, F3R_FPS_TILED = 0, 1, 2
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
@@ -189,12 +190,18 @@ SYMBOLS = {
                                         _c_vp, _c_vp]),
     "f3r_render_resolve": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, _c_vp, _c_vp, _c_vp]),
     "f3r_render_center": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp]),
+    "f3r_raster_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
+    "f3r_raster_triangles": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_double),
+                                            ctypes.c_int, ctypes.c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_i64, _c_vp]),
 }
 
 # entry points added after ABI_VERSION: {symbol: the f3r_version() that first exports it}.  lib() binds one only when the loaded library
 # reports that version; entry() is the one place that tells a caller of a later symbol to rebuild an older library.
 SYMBOL_SINCE = {name: 420 for name in SYMBOLS if name.startswith("f3r_cloud_")}
 SYMBOL_SINCE_430 = {name: 430 for name in SYMBOLS if name.startswith("f3r_render_")}  # the point-splat renderer
+# entry points gated by presence, not by version (f3r_version() did not move for them): lib() binds one only when the loaded library exports
+# it, and entry() tells the caller of an absent one to rebuild.  The triangle rasteriser
+SYMBOL_IF_PRESENT = frozenset(name for name in SYMBOLS if name.startswith("f3r_raster_"))
 
 
 def symbol_since(name: str) -> int:
@@ -232,6 +239,8 @@ def lib():
         if l.f3r_version() < ABI_VERSION:
             raise F3RError(f"{LIB_PATH} is version {l.f3r_version()}, this host code needs >= {ABI_VERSION}: rebuild it (fast3r_amd/csrc/build.sh)")
         for name in SYMBOLS:
+            if name in SYMBOL_IF_PRESENT and not hasattr(l, name):
+                continue
             if symbol_since(name) <= l.f3r_version():
                 bind(name)
         if l.f3r_sizeof(0) != ctypes.sizeof(GemmArgs) or l.f3r_sizeof(1) != ctypes.sizeof(AttnArgs) or l.f3r_sizeof(2) != ctypes.sizeof(AttnF32Args):
@@ -252,6 +261,8 @@ def entry(name: str):
     have, need = library_version(), symbol_since(name)
     if have < need:
         raise F3RError(f"{LIB_PATH} is version {have}, {name} needs >= {need}: rebuild it (fast3r_amd/csrc/build.sh)")
+    if name in SYMBOL_IF_PRESENT and not hasattr(l, name):
+        raise F3RError(f"{LIB_PATH} does not export {name}: rebuild it (fast3r_amd/csrc/build.sh)")
     return getattr(l, name)
 
 

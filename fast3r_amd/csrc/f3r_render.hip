@@ -12,6 +12,7 @@
 //   partials in a second launch of one workgroup, again per thread, wave_sum, block_sum.  The grid is a function of n alone.
 // Integer atomics only: two runs give the same bits.
 #include "f3r_common.h"
+#include "f3r_pixel.h"  // first_center_ge, shared with the triangle rasteriser
 #include "f3r_prims.h"
 
 #include <algorithm>
@@ -31,17 +32,6 @@ struct Camera {  // the 17 doubles of the entry point, and the viewport
   double half_w, half_h, half_s;  // W / 2, H / 2, point_size / 2
   int W, H;
 };
-
-// the smallest integer i with i + 0.5 >= t, clamped to [0, hi].  i + 0.5 is exact for every i the clamp leaves; the two corrections make
-// the result the comparison's own answer whatever ceil(t - 0.5) rounded to
-__device__ __forceinline__ int first_center_ge(double t, int hi) {
-  if (!(t > 0.5)) return 0;  // pixel 0's centre is already >= t
-  if (t > (double)hi) return hi;
-  double i = ceil(t - 0.5);
-  if ((i - 1.0) + 0.5 >= t) i -= 1.0;
-  if (i + 0.5 < t) i += 1.0;
-  return (int)fmin(fmax(i, 0.0), (double)hi);
-}
 
 __global__ __launch_bounds__(SPLAT_NT) void splat_kernel(const float* __restrict__ p, int64_t n0, int64_t n1, Camera c,
                                                          uint64_t* __restrict__ keys) {

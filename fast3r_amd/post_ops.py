@@ -771,3 +771,58 @@ def render_center(points):
     with torch.cuda.device(points.device):
         check(fn(ptr(points), n, ptr(buf[3:]), ptr(buf), stream_ptr()), "f3r_render_center")
     return [s / n for s in buf[:3].tolist()]
+
+
+# ------------------------------------------------------------------------------------------------------------------- triangle rasteriser
+RASTER_FACES_PER_LAUNCH = 1 << 24  # faces of one launch pair of f3r_raster_triangles: a 64 MB queue, whatever the mesh
+_raster_workspaces = {}  # (device index, stream, bytes) -> the int64 workspace tensor; launches on one stream run in order, so one serves every call on it
+
+
+def raster_workspace(device, faces_per_launch):
+    """The workspace of f3r_raster_triangles for launches of `faces_per_launch` faces on `device`, cached per device, current stream and size.  After a
+    call, word 0 holds the last launch's queue length (its low 32 bits) and word 1 the queue length over all launches of the call."""
+    sizer = _lib.entry("f3r_raster_workspace_bytes")
+    faces_per_launch = int(faces_per_launch)
+    nbytes = sizer(faces_per_launch) if 1 <= faces_per_launch < 2 ** 31 else 0
+    if nbytes == 0:
+        raise ValueError(f"raster_triangles: faces_per_launch = {faces_per_launch}; need 1 <= faces_per_launch < 2^31")
+    device = torch.device(device)
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(index):
+        key = (index, stream_ptr(), nbytes)   # per stream: calls on two streams of one device must not share the queue and its counter
+    if key not in _raster_workspaces:
+        _raster_workspaces[key] = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    return _raster_workspaces[key], nbytes
+
+
+def raster_triangles(vertices, faces, camera, keys, *, f0=0, f1=None, index_base=0, faces_per_launch=RASTER_FACES_PER_LAUNCH):
+    """Triangles [f0, f1) of the mesh (vertices (nv, 3) fp32, faces (nf, 3) int32 or int64) go into `keys` (what render_keys returned;
+    written in place) through `camera`, the 17 doubles of include/f3r.h, as keys (fp32 depth << 32) | (index_base + f)
+    (f3r_raster_triangles).  Calls accumulate, with each other and with render_splat.  f1 = None: nf."""
+    fn = _lib.entry("f3r_raster_triangles")
+    require_gpu(vertices, "vertices")
+    require_gpu(faces, "faces")
+    require_gpu(keys, "keys")
+    nv = vertices.shape[0] if vertices.dim() == 2 else -1
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32 or nv < 1:
+        raise ValueError(f"raster_triangles: vertices must be (nv >= 1, 3) fp32, got {tuple(vertices.shape)} {vertices.dtype}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64) or faces.device != vertices.device:
+        raise ValueError(f"raster_triangles: faces must be (nf, 3) int32 or int64 on {vertices.device}, got {tuple(faces.shape)} {faces.dtype} "
+                         f"on {faces.device}")
+    if keys.dim() != 2 or keys.dtype != torch.int64 or not keys.is_contiguous() or keys.device != vertices.device:
+        raise ValueError(f"raster_triangles: keys must be a contiguous (height, width) int64 tensor on {vertices.device}, got "
+                         f"{tuple(keys.shape)} {keys.dtype} on {keys.device}")
+    height, width = keys.shape
+    _render_viewport(width, height, "raster_triangles")
+    nf = faces.shape[0]
+    f1 = nf if f1 is None else int(f1)
+    cam = [float(c) for c in camera]
+    if len(cam) != 17:
+        raise ValueError(f"raster_triangles: camera must hold 17 numbers (V, sx, sy, cx, cy, znear), got {len(cam)}")
+    if nf == 0 and int(f0) == 0 and f1 == 0:
+        return
+    vertices, faces = vertices.contiguous(), faces.contiguous()
+    ws, nbytes = raster_workspace(vertices.device, faces_per_launch)
+    with torch.cuda.device(vertices.device):
+        check(fn(ptr(vertices), nv, ptr(faces), mesh_index_id(faces.dtype), nf, int(f0), f1, int(index_base), (ctypes.c_double * 17)(*cam),
+                 width, height, ptr(keys), ptr(ws), nbytes, int(faces_per_launch), stream_ptr()), "f3r_raster_triangles")

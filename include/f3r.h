@@ -783,6 +783,52 @@ int f3r_render_resolve(const uint64_t* keys, const uint8_t* colors, int64_t n, i
 int f3r_render_center(const float* points, int64_t n, double* partials, double* out, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Triangle rasteriser: depth-tested, flat-coloured triangles into the key buffer of the point-splat renderer above -- what shows a mesh
+ * (build_mesh) and the camera pyramids of the reference's SceneViz (fast3r/dust3r/viz.py:133-305) without a GL stack.  It writes the keys
+ * the splat writes, so points and triangles share one picture and f3r_render_resolve is unchanged.  Python: fast3r_amd/viz.py.  Kernels:
+ * fast3r_amd/csrc/f3r_raster.hip.  f3r_version() is unchanged: a caller learns whether a library has these entry points by looking for them.
+ * `camera`, `keys`, W, H: as f3r_render_splat takes them.  vertices: device fp32 [nv][3]; faces: device int32 or int64 [nf][3]
+ * (index_dtype: F3R_INDEX_I32 / F3R_INDEX_I64).  Every operation below is fp64 and rounded on its own; only + - * /, comparisons and the
+ * ceil of first_center_ge appear.
+ * Per triangle f in [f0, f1), vertex indices (a, b, c) = faces[f]:
+ *   1. skipped if any index is outside [0, nv); the indices are checked before any vertex is read.
+ *   2. per vertex k, from (x, y, z) (fp32, widened): e_r = ((V[r][0] x + V[r][1] y) + V[r][2] z) + V[r][3];  d_k = -e_z;
+ *      p_x = sx e_x + cx d;  p_y = sy e_y + cy d;  x_k = (p_x / d + 1) (W / 2);  y_k = (p_y / d + 1) (H / 2)      (as the splat).
+ *   3. skipped unless d_k >= znear for all three and all six window coordinates are finite (no comparison passes on a NaN).  There is no
+ *      near-plane clipping: a triangle with a vertex nearer than znear is dropped whole.  The frustum's sides do not drop a triangle.
+ *   4. A = (x1 - x0) (y2 - y0) - (y1 - y0) (x2 - x0); skipped if A == 0 or A is not finite.
+ *   5. the pixel box: columns [i0, i1) with i0 = first(min x_k, W), i1 = min(first(max x_k, W) + 1, W), where first(t, hi) is the
+ *      smallest integer i with i + 0.5 >= t clamped to [0, hi] (the splat's first_center_ge); window rows [j0, j1) likewise with y and H.
+ *      The box ends one past the first centre >= the maximum because edges are inclusive.  Its pixel count is (i1 - i0) (j1 - j0).
+ *   6. r_k = 1 / d_k;  dmin = min(d_k);  dmax = max(d_k).
+ * Per pixel (column i, window row j) of the box, centre (cx, cy) = (i + 0.5, j + 0.5):
+ *   w0 = (x2 - x1) (cy - y1) - (y2 - y1) (cx - x1);  w1 = (x0 - x2) (cy - y2) - (y0 - y2) (cx - x2);
+ *   w2 = (x1 - x0) (cy - y0) - (y1 - y0) (cx - x0);
+ *   covered iff w0, w1, w2 >= 0 when A > 0, or w0, w1, w2 <= 0 when A < 0: edges are inclusive and there is no fill rule (two triangles
+ *     that share an edge may both write the pixel; the key decides); no culling (both windings cover the same pixels);
+ *   inv = (w0 r0 + w1 r1) + w2 r2;  dd = ((w0 + w1) + w2) / inv  (perspective-correct);  dd = dmin unless dd >= dmin;  dd = dmax if
+ *     dd > dmax (so a triangle at constant depth writes exactly that depth);
+ *   key = ((uint64_t)bits of (float)dd << 32) | (index_base + f), min-reduced into keys[H - 1 - j][i] with a 64-bit integer atomicMin
+ *     behind the splat's relaxed early-out load.  With points at indices [0, n) and index_base = n, a point wins over a face at equal
+ *     depth and a lower face over a higher one.
+ * Work distribution: stage 1 runs one thread per triangle; a triangle whose box holds at most F3R_RASTER_SMALL_PIXELS pixels is drawn by
+ *   its thread, a larger one is appended to a queue in the workspace (ballot compaction, one integer atomic per wave).  Stage 2 runs one
+ *   wave per queued triangle, the lanes striding over the box with the same per-pixel code.  The queue's order depends on arrival, the
+ *   keys do not.  [f0, f1) is walked in launches of at most faces_per_launch faces; the queue holds one uint32 slot per face of a launch.
+ * workspace: f3r_raster_workspace_bytes(faces_per_launch) bytes (0 for an invalid faces_per_launch), 8-byte aligned.  After the call its
+ *   first words read { uint32 queue length of the last launch, uint32 0, uint64 queue length over all launches }.
+ * Limits, F3R_ERR_ARG before any launch: null pointers; W or H < 1, W H >= 2^31; nv < 1; an unknown index_dtype; not 0 <= f0 <= f1 <= nf;
+ *   index_base < 0 or index_base + nf >= 2^32; a camera entry that is not finite; znear <= 0; faces_per_launch < 1 or >= 2^31; a workspace
+ *   that is too small or misaligned.  f0 == f1 launches nothing.  No floating-point atomics: two runs give the same bits; inputs are
+ *   not written to.
+ */
+#define F3R_RASTER_SMALL_PIXELS 64
+size_t f3r_raster_workspace_bytes(int64_t faces_per_launch);
+int f3r_raster_triangles(const float* vertices, int64_t nv, const void* faces, int index_dtype, int64_t nf, int64_t f0, int64_t f1,
+                         int64_t index_base, const double* camera, int W, int H, uint64_t* keys, void* workspace, size_t workspace_bytes,
+                         int64_t faces_per_launch, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
  * f3r_resample_u8 is ONE pass of PIL.Image.resize for 8-bit RGB (`_resize_pil_image`, :68-74; Pillow's Resample.c): axis 1 =
  * horizontal ([H][W][3] -> [H][out_size][3]), axis 0 = vertical ([H][W][3] -> [out_size][W][3]); bounds [out_size][2] = {first source
