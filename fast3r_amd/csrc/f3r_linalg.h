@@ -1,6 +1,7 @@
 // Small dense linear algebra in fp64 for the post-processing kernels (one thread per problem): 3x3 SVD, symmetric Jacobi eigen-solver,
-// Cholesky solve.  Header-only; device functions in the library -- with F3R_HOST_BUILD defined the same source compiles as plain C++
-// (tests build f3r_sqpnp.h that way to check the arithmetic on the CPU; the product never does).
+// Cholesky solve, and the Umeyama similarity solve from raw moments that align and evaluate_reconstruction share.  Header-only; device
+// functions in the library -- with F3R_HOST_BUILD defined the same source compiles as plain C++ (tests build this header and f3r_sqpnp.h
+// that way to check the arithmetic on the CPU; the product never does).
 #pragma once
 #ifdef F3R_HOST_BUILD
 #include <cmath>
@@ -14,7 +15,8 @@
 
 namespace f3r_la {
 
-// 3x3 SVD of M by two-sided use of the Jacobi eigen-decomposition of M^T M:  M = U diag(s) V^T, s sorted descending.
+// 3x3 SVD of M:  M = U diag(s) V^T with V from the Jacobi eigen-decomposition of M^T M (columns sorted by eigenvalue, descending) and U, s
+// from M V; U and V are orthonormal whatever the conditioning of M.
 F3R_LA_FN void svd3(const double M[3][3], double U[3][3], double S[3], double V[3][3]) {
   double A[3][3];
   for (int i = 0; i < 3; ++i)
@@ -62,34 +64,50 @@ F3R_LA_FN void svd3(const double M[3][3], double U[3][3], double S[3], double V[
   }
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) V[r][c] = Vs[r][c];
-  // U columns: M v_c / s_c; complete a deficient basis by Gram-Schmidt / cross products
-  const double tol = 1e-12 * fmax(S[0], 1e-300);
+  // U columns: M v_c, made orthogonal to the columns before it (Gram-Schmidt, two passes) and normalised.  The eigenvalues of M^T M
+  // carry the square of M's condition number, so sqrt(ev) of a singular value below ~1e-8 S0 is rounding noise, and M v_c / S_c would be
+  // noise over noise: neither unit length nor orthogonal.  M v_c itself is good to eps * S0.  A column whose remainder is below
+  // RANK_TOL * S0 has no direction of its own: the basis is completed instead (any unit vector orthogonal to u0; u0 x u1), and its singular
+  // value is that remainder.  A small but real third singular value keeps its column, hence its sign for the caller's determinant
+  // correction; a completed third column gives det U = +1, and the sign then multiplies a singular value that is zero to RANK_TOL.
+  constexpr double RANK_TOL = 1e-7;
+  double Un[3][3];  // Un[c] = column c of U
+  double s0 = 0.0;
   for (int c = 0; c < 3; ++c) {
-    for (int r = 0; r < 3; ++r) {
-      double a = 0;
-      for (int k = 0; k < 3; ++k) a += M[r][k] * V[k][c];
-      U[r][c] = (S[c] > tol) ? a / S[c] : 0.0;
+    double u[3];
+    for (int r = 0; r < 3; ++r) u[r] = M[r][0] * V[0][c] + M[r][1] * V[1][c] + M[r][2] * V[2][c];
+    const double full = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    for (int pass = 0; pass < 2; ++pass)
+      for (int p = 0; p < c; ++p) {
+        const double d = u[0] * Un[p][0] + u[1] * Un[p][1] + u[2] * Un[p][2];
+        for (int r = 0; r < 3; ++r) u[r] -= d * Un[p][r];
+      }
+    const double rem = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    if (c == 0) s0 = full;
+    if (rem > RANK_TOL * s0 && rem > 1e-300) {
+      S[c] = full;
+      for (int r = 0; r < 3; ++r) Un[c][r] = u[r] / rem;
+      continue;
+    }
+    S[c] = rem;
+    if (c == 0) {
+      Un[0][0] = 1; Un[0][1] = 0; Un[0][2] = 0;
+    } else if (c == 1) {  // any unit vector orthogonal to u0
+      const double a0 = fabs(Un[0][0]), a1 = fabs(Un[0][1]), a2 = fabs(Un[0][2]);
+      double e[3] = {0, 0, 0};
+      e[(a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2)] = 1.0;
+      const double d = e[0] * Un[0][0] + e[1] * Un[0][1] + e[2] * Un[0][2];
+      for (int r = 0; r < 3; ++r) u[r] = e[r] - d * Un[0][r];
+      const double n = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+      for (int r = 0; r < 3; ++r) Un[1][r] = u[r] / n;
+    } else {  // u2 = u0 x u1
+      Un[2][0] = Un[0][1] * Un[1][2] - Un[0][2] * Un[1][1];
+      Un[2][1] = Un[0][2] * Un[1][0] - Un[0][0] * Un[1][2];
+      Un[2][2] = Un[0][0] * Un[1][1] - Un[0][1] * Un[1][0];
     }
   }
-  auto norm3 = [](double* v0, double* v1, double* v2) {
-    const double n = sqrt(*v0 * *v0 + *v1 * *v1 + *v2 * *v2);
-    if (n > 0) { *v0 /= n; *v1 /= n; *v2 /= n; }
-    return n;
-  };
-  if (S[0] <= tol) { U[0][0] = 1; U[1][0] = 0; U[2][0] = 0; }
-  if (S[1] <= tol) {  // any unit vector orthogonal to u0
-    const double a0 = fabs(U[0][0]), a1 = fabs(U[1][0]), a2 = fabs(U[2][0]);
-    double e[3] = {0, 0, 0};
-    e[(a0 <= a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2)] = 1.0;
-    const double d = e[0] * U[0][0] + e[1] * U[1][0] + e[2] * U[2][0];
-    U[0][1] = e[0] - d * U[0][0]; U[1][1] = e[1] - d * U[1][0]; U[2][1] = e[2] - d * U[2][0];
-    norm3(&U[0][1], &U[1][1], &U[2][1]);
-  }
-  if (S[2] <= tol) {  // u2 = u0 x u1 (the sign is fixed by the determinant correction of the caller)
-    U[0][2] = U[1][0] * U[2][1] - U[2][0] * U[1][1];
-    U[1][2] = U[2][0] * U[0][1] - U[0][0] * U[2][1];
-    U[2][2] = U[0][0] * U[1][1] - U[1][0] * U[0][1];
-  }
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) U[r][c] = Un[c][r];
 }
 
 F3R_LA_FORCE double det3(const double A[3][3]) {
@@ -165,3 +183,32 @@ F3R_LA_FN bool chol_solve(const double A[N][N], const double* b, double* x) {
 }
 
 }  // namespace f3r_la
+
+// Umeyama from raw moments m[17] = {n, sum x (3), sum y (3), sum y_i x_j (9), sum |x|^2} -> (R, t, s) as 13 floats
+// [R row-major (9) | t (3) | s]; the caller has handled n < 3.
+F3R_LA_FN void similarity_from_moments(const double* m, float* o) {
+  const double n = m[0];
+  const double xm[3] = {m[1] / n, m[2] / n, m[3] / n}, ym[3] = {m[4] / n, m[5] / n, m[6] / n};
+  double M[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) M[i][j] = m[7 + i * 3 + j] - n * ym[i] * xm[j];
+  const double sx2 = m[16] - n * (xm[0] * xm[0] + xm[1] * xm[1] + xm[2] * xm[2]);
+  double U[3][3], S[3], V[3][3];
+  f3r_la::svd3(M, U, S, V);
+  const double d = (f3r_la::det3(U) * f3r_la::det3(V) < 0) ? -1.0 : 1.0;
+  double R[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * V[j][0] + U[i][1] * V[j][1] + d * U[i][2] * V[j][2];
+  const double scale = (S[0] + S[1] + d * S[2]) / sx2;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) o[i * 3 + j] = (float)R[i][j];
+    o[9 + i] = (float)(ym[i] - scale * (R[i][0] * xm[0] + R[i][1] * xm[1] + R[i][2] * xm[2]));
+  }
+  o[12] = (float)scale;
+}
+
+F3R_LA_FN void identity_rts(float* o) {
+  for (int i = 0; i < 9; ++i) o[i] = (i % 4 == 0) ? 1.f : 0.f;
+  o[9] = o[10] = o[11] = 0.f;
+  o[12] = 1.f;
+}

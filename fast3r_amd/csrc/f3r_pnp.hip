@@ -15,6 +15,13 @@
 //   E. nearest rotation (3x3 SVD), 6 gated Gauss-Newton steps on the reprojection error (28 fp64 sums per pass)
 //   F. SQPnP (f3r_sqpnp.h) on the points within 5 px of the selected pose: the solver the reference names, on the consensus set, as
 //      OpenCV's solvePnPRansac ends; cam-to-world (:349-350)
+// When B finds no consensus set, C-E are skipped and SQPnP itself runs on ALL masked points (the direct path): with 4 or 5 masked points a
+// 6-point sample cannot be drawn and a DLT on all of them is underdetermined (8 or 10 equations, 12 unknowns: its 4 x 4 matrix is zero up to
+// rounding and its "smallest eigenvector" arbitrary); with masked points on one image line (a one-row image, a mask confined to one row) the world
+// points are coplanar with the camera and every DLT is singular.  One solve at the given focal, or one per grid candidate (one candidate per
+// thread), ranked by inlier count, then truncated cost, then grid order; kept with at least 6 inliers, or with every masked point an inlier
+// when there are fewer than 6 (the reference's RANSAC has one sample to draw from so few points and keeps a model only when it explains the
+// whole sample); otherwise the view fails like one with fewer than 4 points.  F follows as for any other pose.
 // Same algorithm, independently written on torch.linalg: oracle/pnp_oracle.py.  All passes re-read the view's 4 MB from L2.
 #include "f3r_common.h"
 #include "f3r_linalg.h"
@@ -162,6 +169,8 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
   __shared__ Pose cur;
   __shared__ double sh_rows[12];
   __shared__ int sh_best;
+  __shared__ int dir_cnt[PT];  // the direct path: every thread's best candidate
+  __shared__ double dir_cost[PT];
   const int64_t npix = (int64_t)H * W;
   const int64_t prob = blockIdx.x;
   const float* cf = conf + prob * npix;
@@ -175,6 +184,16 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
       focal_out[prob] = __builtin_nanf("");
       inliers_out[prob] = 0;
     }
+  };
+
+  auto write_pose = [&](const Pose& P, int n_inl) {  // cam-to-world = inverse of [R | t] (init_im_poses.py:349-350)
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) pose_o[r * 4 + c] = (float)P.R[c][r];
+      pose_o[r * 4 + 3] = (float)(-(P.R[0][r] * P.t[0] + P.R[1][r] * P.t[1] + P.R[2][r] * P.t[2]));
+    }
+    pose_o[12] = 0.f; pose_o[13] = 0.f; pose_o[14] = 0.f; pose_o[15] = 1.f;
+    focal_out[prob] = (float)P.f;
+    inliers_out[prob] = n_inl;
   };
 
   // ---- A. masked count, centroid, RMS
@@ -268,132 +287,210 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
     if (best_cnt < SAMPLE) best_h = -1;
   }
 
-  // ---- C. moments over the inliers of the best hypothesis (all masked points when there is none) -> DLT rows
-  {
-    for (int k = 0; k < 40; ++k) acc[k] = 0.0;
-    Pose P;
-    if (best_h >= 0) P = hyp[best_h];
+  double best_cnt = 0.0, best_cost = 1e300;
+  Pose best_pose;
+  best_pose.ok = 0;
+  if (best_h < 0) {
+    // ---- direct path: no hypothesis found a consensus set -- fewer than SAMPLE masked points (a DLT on 4 or 5 points is underdetermined:
+    // 8 or 10 equations for 12 unknowns), or every sample degenerate (masked points on one image line are coplanar with the camera, and the
+    // DLT's S0 is singular for them however many there are).  SQPnP solves both, so it runs on ALL masked points: its 40 sums once at focal 1
+    // (the image point enters them as x / f, y / f and (x^2 + y^2) / f^2), then one solve per candidate focal, one candidate per thread, each
+    // scored on all masked points.  Candidates rank by inlier count, then truncated cost, then grid order.  A pose is kept when it has a
+    // consensus set by the rule of B, at least SAMPLE inliers, or, from fewer masked points, all of them (OpenCV's RANSAC has one sample to
+    // draw there and keeps a model only when it explains the whole sample).
+    for (int k = 0; k < f3r_sqpnp::N_SUMS; ++k) acc[k] = 0.0;
     for (int64_t i = tid; i < npix; i += PT) {
       if (!(cf[i] > conf_thr)) continue;
-      const double x = pt[i * 3], y = pt[i * 3 + 1], z = pt[i * 3 + 2];
-      const double px = (double)(int)(i % W) - ppx, py = (double)(int)(i / W) - ppy;
-      if (best_h >= 0) {
+      const double Mn[3] = {(pt[i * 3] - cen[0]) * isig, (pt[i * 3 + 1] - cen[1]) * isig, (pt[i * 3 + 2] - cen[2]) * isig};
+      f3r_sqpnp::accumulate(acc, Mn, (double)(int)(i % W) - ppx, (double)(int)(i / W) - ppy);
+    }
+    block_sum<f3r_sqpnp::N_SUMS, PT>(acc, red, sums);
+    int my_cnt = -1;
+    double my_cost = 1e300;
+    Pose mine;
+    mine.ok = 0;
+    const int n_cand = focal_known ? 1 : n_focals;
+    for (int kc = tid; kc < n_cand; kc += PT) {
+      const double f = focal_known ? (double)focal_in[prob] : grid_focal(kc, Smax, n_focals);
+      const double inv_f = 1.0 / f;
+      for (int k = 0; k < 10; ++k) {
+        acc[k] = sums[k];
+        acc[10 + k] = sums[10 + k] * inv_f;
+        acc[20 + k] = sums[20 + k] * inv_f;
+        acc[30 + k] = sums[30 + k] * inv_f * inv_f;
+      }
+      f3r_sqpnp::Result r;
+      if (!sqpnp_solve(acc, sig * sig, &r)) continue;
+      Pose P;
+      for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) P.R[a][b] = r.R[a][b];
+        P.t[a] = sig * r.t[a] - (r.R[a][0] * cen[0] + r.R[a][1] * cen[1] + r.R[a][2] * cen[2]);
+      }
+      P.f = f;
+      P.ok = 1;
+      int cnt = 0;
+      double cost = 0.0;
+      for (int64_t i = 0; i < npix; ++i) {
+        if (!(cf[i] > conf_thr)) continue;
+        const double x = pt[i * 3], y = pt[i * 3 + 1], z = pt[i * 3 + 2];
+        const double px = (double)(int)(i % W) - ppx, py = (double)(int)(i / W) - ppy;
+        const double zc = P.R[2][0] * x + P.R[2][1] * y + P.R[2][2] * z + P.t[2];
+        const double xc = P.R[0][0] * x + P.R[0][1] * y + P.R[0][2] * z + P.t[0];
+        const double yc = P.R[1][0] * x + P.R[1][1] * y + P.R[1][2] * z + P.t[1];
+        const double ex = f * xc / zc - px, ey = f * yc / zc - py;
+        const double e2 = ex * ex + ey * ey;
+        const bool inl = zc > 0.0 && e2 <= (double)THR2;
+        cnt += inl ? 1 : 0;
+        cost += inl ? e2 : (double)THR2;
+      }
+      if (cnt > my_cnt || (cnt == my_cnt && cost < my_cost)) {
+        my_cnt = cnt;
+        my_cost = cost;
+        mine = P;
+      }
+    }
+    dir_cnt[tid] = my_cnt;
+    dir_cost[tid] = my_cost;
+    __syncthreads();
+    if (tid == 0) {  // thread t holds candidates t, t + PT, ...: scanning the threads in order keeps the earliest candidate among equals
+      int w = -1;
+      for (int t = 0; t < PT; ++t)
+        if (dir_cnt[t] > 0 && (w < 0 || dir_cnt[t] > dir_cnt[w] || (dir_cnt[t] == dir_cnt[w] && dir_cost[t] < dir_cost[w]))) w = t;
+      const double need = n_mask < SAMPLE ? n_mask : (double)SAMPLE;
+      sh_best = (w >= 0 && dir_cnt[w] >= need) ? w : -1;
+    }
+    __syncthreads();
+    if (sh_best < 0) {
+      fail();
+      return;
+    }
+    if (tid == sh_best) cur = mine;
+    __syncthreads();
+    best_pose = cur;
+    best_cnt = dir_cnt[sh_best];
+    best_cost = dir_cost[sh_best];
+  } else {
+    // ---- C. moments over the inliers of the best hypothesis -> DLT rows
+    {
+      for (int k = 0; k < 40; ++k) acc[k] = 0.0;
+      const Pose P = hyp[best_h];
+      for (int64_t i = tid; i < npix; i += PT) {
+        if (!(cf[i] > conf_thr)) continue;
+        const double x = pt[i * 3], y = pt[i * 3 + 1], z = pt[i * 3 + 2];
+        const double px = (double)(int)(i % W) - ppx, py = (double)(int)(i / W) - ppy;
         const double zc = P.R[2][0] * x + P.R[2][1] * y + P.R[2][2] * z + P.t[2];
         const double xc = P.R[0][0] * x + P.R[0][1] * y + P.R[0][2] * z + P.t[0];
         const double yc = P.R[1][0] * x + P.R[1][1] * y + P.R[1][2] * z + P.t[1];
         const double ex = P.f * xc / zc - px, ey = P.f * yc / zc - py;
         if (!(zc > 0.0 && ex * ex + ey * ey <= (double)THR2)) continue;
+        const double Pn[4] = {(x - cen[0]) * isig, (y - cen[1]) * isig, (z - cen[2]) * isig, 1.0};
+        add_moments(acc, Pn, px, py);
       }
-      const double Pn[4] = {(x - cen[0]) * isig, (y - cen[1]) * isig, (z - cen[2]) * isig, 1.0};
-      add_moments(acc, Pn, px, py);
+      block_sum<40, PT>(acc, red, sums);
     }
-    block_sum<40, PT>(acc, red, sums);
-  }
-  if (tid == 0) {
-    double m[40], a[4], b[4], c[4];
-    for (int k = 0; k < 40; ++k) m[k] = sums[k];
-    sh_best = dlt_rows(m, a, b, c) ? 1 : 0;
-    for (int k = 0; k < 4; ++k) { sh_rows[k] = a[k]; sh_rows[4 + k] = b[k]; sh_rows[8 + k] = c[k]; }
-  }
-  __syncthreads();
-  if (!sh_best) {
-    fail();
-    return;
-  }
-
-  // ---- D / E. candidate focals, each: pose from rows -> gated Gauss-Newton -> score
-  int k_lo = 0, k_hi = 0;
-  if (!focal_known) {
-    const double* a = sh_rows;
-    const double* b = sh_rows + 4;
-    const double* c = sh_rows + 8;
-    const double nc = fmax(sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), 1e-30);
-    const double fd = sqrt(fmax(sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]), 1e-30)) / nc;
-    int k0 = (int)llrint(log(fmax(fd, 1e-9) / (0.5 * Smax)) / log(6.0) * (n_focals - 1));
-    k0 = k0 < 0 ? 0 : (k0 > n_focals - 1 ? n_focals - 1 : k0);
-    k_lo = k0 - 1 < 0 ? 0 : k0 - 1;
-    k_hi = k0 + 1 > n_focals - 1 ? n_focals - 1 : k0 + 1;
-  }
-  double best_cnt = 0.0, best_cost = 1e300;
-  Pose best_pose;
-  best_pose.ok = 0;
-  for (int kc = k_lo; kc <= k_hi; ++kc) {
-    const double f = focal_known ? (double)focal_in[prob] : grid_focal(kc, Smax, n_focals);
-    if (tid == 0) pose_from_rows(sh_rows, sh_rows + 4, sh_rows + 8, f, cen, sig, cur);
+    if (tid == 0) {
+      double m[40], a[4], b[4], c[4];
+      for (int k = 0; k < 40; ++k) m[k] = sums[k];
+      sh_best = dlt_rows(m, a, b, c) ? 1 : 0;
+      for (int k = 0; k < 4; ++k) { sh_rows[k] = a[k]; sh_rows[4 + k] = b[k]; sh_rows[8 + k] = c[k]; }
+    }
     __syncthreads();
-    for (int it = 0; it <= N_GN; ++it) {  // N_GN refinement passes, then one scoring pass
-      const Pose P = cur;
-      for (int k = 0; k < 30; ++k) acc[k] = 0.0;
-      for (int64_t i = tid; i < npix; i += PT) {
-        if (!(cf[i] > conf_thr)) continue;
-        const double X = pt[i * 3], Y = pt[i * 3 + 1], Z = pt[i * 3 + 2];
-        const double px = (double)(int)(i % W) - ppx, py = (double)(int)(i / W) - ppy;
-        const double z = P.R[2][0] * X + P.R[2][1] * Y + P.R[2][2] * Z + P.t[2];
-        const double x = P.R[0][0] * X + P.R[0][1] * Y + P.R[0][2] * Z + P.t[0];
-        const double y = P.R[1][0] * X + P.R[1][1] * Y + P.R[1][2] * Z + P.t[1];
-        const double iz = 1.0 / z;
-        const double ex = f * x * iz - px, ey = f * y * iz - py;
-        const double e2 = ex * ex + ey * ey;
-        const bool inl = z > 0.0 && e2 <= (double)THR2;
-        acc[28] += inl ? 1.0 : 0.0;
-        acc[29] += inl ? e2 : (double)THR2;
-        if (!inl || it == N_GN) continue;
-        const double Jx[6] = {-f * x * y * iz * iz, f * (1.0 + x * x * iz * iz), -f * y * iz, f * iz, 0.0, -f * x * iz * iz};
-        const double Jy[6] = {-f * (1.0 + y * y * iz * iz), f * x * y * iz * iz, f * x * iz, 0.0, f * iz, -f * y * iz * iz};
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-#pragma unroll
-          for (int c = r; c < 6; ++c) acc[k++] += Jx[r] * Jx[c] + Jy[r] * Jy[c];
-          acc[21 + r] += Jx[r] * ex + Jy[r] * ey;
+    if (!sh_best) {
+      fail();
+      return;
+    }
+
+    // ---- D / E. candidate focals, each: pose from rows -> gated Gauss-Newton -> score
+    int k_lo = 0, k_hi = 0;
+    if (!focal_known) {
+      const double* a = sh_rows;
+      const double* b = sh_rows + 4;
+      const double* c = sh_rows + 8;
+      const double nc = fmax(sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), 1e-30);
+      const double fd = sqrt(fmax(sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) * sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]), 1e-30)) / nc;
+      int k0 = (int)llrint(log(fmax(fd, 1e-9) / (0.5 * Smax)) / log(6.0) * (n_focals - 1));
+      k0 = k0 < 0 ? 0 : (k0 > n_focals - 1 ? n_focals - 1 : k0);
+      k_lo = k0 - 1 < 0 ? 0 : k0 - 1;
+      k_hi = k0 + 1 > n_focals - 1 ? n_focals - 1 : k0 + 1;
+    }
+    for (int kc = k_lo; kc <= k_hi; ++kc) {
+      const double f = focal_known ? (double)focal_in[prob] : grid_focal(kc, Smax, n_focals);
+      if (tid == 0) pose_from_rows(sh_rows, sh_rows + 4, sh_rows + 8, f, cen, sig, cur);
+      __syncthreads();
+      for (int it = 0; it <= N_GN; ++it) {  // N_GN refinement passes, then one scoring pass
+        const Pose P = cur;
+        for (int k = 0; k < 30; ++k) acc[k] = 0.0;
+        for (int64_t i = tid; i < npix; i += PT) {
+          if (!(cf[i] > conf_thr)) continue;
+          const double X = pt[i * 3], Y = pt[i * 3 + 1], Z = pt[i * 3 + 2];
+          const double px = (double)(int)(i % W) - ppx, py = (double)(int)(i / W) - ppy;
+          const double z = P.R[2][0] * X + P.R[2][1] * Y + P.R[2][2] * Z + P.t[2];
+          const double x = P.R[0][0] * X + P.R[0][1] * Y + P.R[0][2] * Z + P.t[0];
+          const double y = P.R[1][0] * X + P.R[1][1] * Y + P.R[1][2] * Z + P.t[1];
+          const double iz = 1.0 / z;
+          const double ex = f * x * iz - px, ey = f * y * iz - py;
+          const double e2 = ex * ex + ey * ey;
+          const bool inl = z > 0.0 && e2 <= (double)THR2;
+          acc[28] += inl ? 1.0 : 0.0;
+          acc[29] += inl ? e2 : (double)THR2;
+          if (!inl || it == N_GN) continue;
+          const double Jx[6] = {-f * x * y * iz * iz, f * (1.0 + x * x * iz * iz), -f * y * iz, f * iz, 0.0, -f * x * iz * iz};
+          const double Jy[6] = {-f * (1.0 + y * y * iz * iz), f * x * y * iz * iz, f * x * iz, 0.0, f * iz, -f * y * iz * iz};
+          int k = 0;
+  #pragma unroll
+          for (int r = 0; r < 6; ++r) {
+  #pragma unroll
+            for (int c = r; c < 6; ++c) acc[k++] += Jx[r] * Jx[c] + Jy[r] * Jy[c];
+            acc[21 + r] += Jx[r] * ex + Jy[r] * ey;
+          }
         }
-      }
-      block_sum<30, PT>(acc, red, sums);
-      if (it == N_GN) break;
-      if (tid == 0 && sums[28] >= 4.0) {
-        double Hm[6][6], g[6], d[6];
-        int k = 0;
-        for (int r = 0; r < 6; ++r)
-          for (int c = r; c < 6; ++c) { Hm[r][c] = sums[k]; Hm[c][r] = sums[k]; ++k; }
-        for (int r = 0; r < 6; ++r) { Hm[r][r] += 1e-9 * Hm[r][r] + 1e-12; g[r] = -sums[21 + r]; }
-        if (f3r_la::chol_solve<6>(Hm, g, d)) {
-          // dR = exp([w]_x) (Rodrigues), R <- dR R, t <- dR t + dt
-          const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-          const double K[3][3] = {{0, -d[2], d[1]}, {d[2], 0, -d[0]}, {-d[1], d[0], 0}};
-          const double c1 = th < 1e-12 ? 1.0 : sin(th) / th, c2 = th < 1e-12 ? 0.0 : (1.0 - cos(th)) / (th * th);
-          double dR[3][3], Rn[3][3], tn[3];
-          for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-              double kk = 0;
-              for (int q = 0; q < 3; ++q) kk += K[r][q] * K[q][c];
-              dR[r][c] = (r == c ? 1.0 : 0.0) + c1 * K[r][c] + c2 * kk;
+        block_sum<30, PT>(acc, red, sums);
+        if (it == N_GN) break;
+        if (tid == 0 && sums[28] >= 4.0) {
+          double Hm[6][6], g[6], d[6];
+          int k = 0;
+          for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c) { Hm[r][c] = sums[k]; Hm[c][r] = sums[k]; ++k; }
+          for (int r = 0; r < 6; ++r) { Hm[r][r] += 1e-9 * Hm[r][r] + 1e-12; g[r] = -sums[21 + r]; }
+          if (f3r_la::chol_solve<6>(Hm, g, d)) {
+            // dR = exp([w]_x) (Rodrigues), R <- dR R, t <- dR t + dt
+            const double th = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            const double K[3][3] = {{0, -d[2], d[1]}, {d[2], 0, -d[0]}, {-d[1], d[0], 0}};
+            const double c1 = th < 1e-12 ? 1.0 : sin(th) / th, c2 = th < 1e-12 ? 0.0 : (1.0 - cos(th)) / (th * th);
+            double dR[3][3], Rn[3][3], tn[3];
+            for (int r = 0; r < 3; ++r)
+              for (int c = 0; c < 3; ++c) {
+                double kk = 0;
+                for (int q = 0; q < 3; ++q) kk += K[r][q] * K[q][c];
+                dR[r][c] = (r == c ? 1.0 : 0.0) + c1 * K[r][c] + c2 * kk;
+              }
+            for (int r = 0; r < 3; ++r) {
+              for (int c = 0; c < 3; ++c) Rn[r][c] = dR[r][0] * cur.R[0][c] + dR[r][1] * cur.R[1][c] + dR[r][2] * cur.R[2][c];
+              tn[r] = dR[r][0] * cur.t[0] + dR[r][1] * cur.t[1] + dR[r][2] * cur.t[2] + d[3 + r];
             }
-          for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) Rn[r][c] = dR[r][0] * cur.R[0][c] + dR[r][1] * cur.R[1][c] + dR[r][2] * cur.R[2][c];
-            tn[r] = dR[r][0] * cur.t[0] + dR[r][1] * cur.t[1] + dR[r][2] * cur.t[2] + d[3 + r];
-          }
-          for (int r = 0; r < 3; ++r) {
-            for (int c = 0; c < 3; ++c) cur.R[r][c] = Rn[r][c];
-            cur.t[r] = tn[r];
+            for (int r = 0; r < 3; ++r) {
+              for (int c = 0; c < 3; ++c) cur.R[r][c] = Rn[r][c];
+              cur.t[r] = tn[r];
+            }
           }
         }
+        __syncthreads();
+      }
+      const double cnt = sums[28], cost = sums[29];
+      if (cnt > best_cnt || (cnt == best_cnt && cnt > 0 && cost < best_cost)) {
+        best_cnt = cnt;
+        best_cost = cost;
+        best_pose = cur;
+        best_pose.f = f;
+        best_pose.ok = 1;
       }
       __syncthreads();
+      if (focal_known) break;
     }
-    const double cnt = sums[28], cost = sums[29];
-    if (cnt > best_cnt || (cnt == best_cnt && cnt > 0 && cost < best_cost)) {
-      best_cnt = cnt;
-      best_cost = cost;
-      best_pose = cur;
-      best_pose.f = f;
-      best_pose.ok = 1;
+    if (!best_pose.ok || best_cnt < 1.0) {
+      fail();
+      return;
     }
-    __syncthreads();
-    if (focal_known) break;
-  }
-  if (!best_pose.ok || best_cnt < 1.0) {
-    fail();
-    return;
   }
   // ---- F. SQPnP on the consensus set: cv2.solvePnPRansac(..., flags=SOLVEPNP_SQPNP) (init_im_poses.py:335) ends with the named solver on
   // its inliers, so that -- not the Gauss-Newton iterate that selected them -- is the pose the reference returns.  One pass of 40 fp64
@@ -431,15 +528,7 @@ __global__ __launch_bounds__(PT) void pnp_kernel(const float* __restrict__ pts, 
     best_pose = cur;
     best_pose.f = keep_f;
   }
-  if (tid == 0) {  // cam-to-world = inverse of [R | t] (init_im_poses.py:349-350)
-    for (int r = 0; r < 3; ++r) {
-      for (int c = 0; c < 3; ++c) pose_o[r * 4 + c] = (float)best_pose.R[c][r];
-      pose_o[r * 4 + 3] = (float)(-(best_pose.R[0][r] * best_pose.t[0] + best_pose.R[1][r] * best_pose.t[1] + best_pose.R[2][r] * best_pose.t[2]));
-    }
-    pose_o[12] = 0.f; pose_o[13] = 0.f; pose_o[14] = 0.f; pose_o[15] = 1.f;
-    focal_out[prob] = (float)best_pose.f;
-    inliers_out[prob] = (int)best_cnt;
-  }
+  if (tid == 0) write_pose(best_pose, (int)best_cnt);
 }
 
 }  // namespace

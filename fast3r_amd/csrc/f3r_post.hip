@@ -170,7 +170,8 @@ __global__ __launch_bounds__(PNT) void focal_kernel(const float* __restrict__ pt
   }
   if (threadIdx.x == 0) {
     const float lo = min_focal * focal_base, hi = max_focal * focal_base;
-    focal_out[prob] = fminf(fmaxf(focal, lo), hi);  // post_process.py:140-142
+    // post_process.py:140-142; torch's clip keeps a NaN (0 / 0 when every kept point has Z == 0), fmaxf / fminf would return the bound
+    focal_out[prob] = (focal == focal) ? fminf(fmaxf(focal, lo), hi) : focal;
   }
 }
 

@@ -1,7 +1,8 @@
-// The two solvers shared by the post-processing kernels (f3r_post.hip: align / focal; f3r_recon.hip: evaluate_reconstruction):
-// the exact torch.quantile of a block's values by radix select over the order-preserving 32-bit keys of f3r_prims.h, and the
-// Umeyama similarity solve from fp64 raw moments.  The wave and block primitives (keys, ballots, sums, the scan kernel) live in
-// f3r_prims.h, which this header brings along.  Header-only (inline device functions and templates).
+// The quantile solver shared by the post-processing kernels (f3r_post.hip: align / focal; f3r_recon.hip: evaluate_reconstruction): the
+// exact torch.quantile of a block's values by radix select over the order-preserving 32-bit keys of f3r_prims.h.  The other solver they
+// share, the Umeyama similarity solve from fp64 raw moments (similarity_from_moments), is in f3r_linalg.h, which also builds for the host.
+// The wave and block primitives (keys, ballots, sums, the scan kernel) live in f3r_prims.h, which this header brings along.  Header-only
+// (inline device functions and templates).
 #pragma once
 
 #include "f3r_linalg.h"
@@ -60,33 +61,4 @@ __device__ float block_quantile(const float* __restrict__ cf, int64_t n, float q
   }
   __syncthreads();
   return *sh_thr;
-}
-
-// Umeyama from raw moments m[17] = {n, sum x (3), sum y (3), sum y_i x_j (9), sum |x|^2} -> (R, t, s) as 13 floats
-// [R row-major (9) | t (3) | s]; the caller has handled n < 3.
-__device__ inline void similarity_from_moments(const double* m, float* o) {
-  const double n = m[0];
-  const double xm[3] = {m[1] / n, m[2] / n, m[3] / n}, ym[3] = {m[4] / n, m[5] / n, m[6] / n};
-  double M[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) M[i][j] = m[7 + i * 3 + j] - n * ym[i] * xm[j];
-  const double sx2 = m[16] - n * (xm[0] * xm[0] + xm[1] * xm[1] + xm[2] * xm[2]);
-  double U[3][3], S[3], V[3][3];
-  f3r_la::svd3(M, U, S, V);
-  const double d = (f3r_la::det3(U) * f3r_la::det3(V) < 0) ? -1.0 : 1.0;
-  double R[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) R[i][j] = U[i][0] * V[j][0] + U[i][1] * V[j][1] + d * U[i][2] * V[j][2];
-  const double scale = (S[0] + S[1] + d * S[2]) / sx2;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) o[i * 3 + j] = (float)R[i][j];
-    o[9 + i] = (float)(ym[i] - scale * (R[i][0] * xm[0] + R[i][1] * xm[1] + R[i][2] * xm[2]));
-  }
-  o[12] = (float)scale;
-}
-
-__device__ inline void identity_rts(float* o) {
-  for (int i = 0; i < 9; ++i) o[i] = (i % 4 == 0) ? 1.f : 0.f;
-  o[9] = o[10] = o[11] = 0.f;
-  o[12] = 1.f;
 }

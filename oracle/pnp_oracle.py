@@ -13,6 +13,7 @@ the algorithm of the HIP path (f3r_post.hip::pnp_*), written independently on to
        [r1 t1] = S0^-1 S1x c / f, [r2 t2] = S0^-1 S1y c / f;
     2. nearest rotation (SVD) + scale, positive-depth sign;  3. score = points within 5 px;  4. gated Gauss-Newton on the best;
     5. (round 3) SQPnP on the points within 5 px of that pose: the final solve of cv2.solvePnPRansac(SOLVEPNP_SQPNP), restated in oracle/sqpnp.py.
+    6. with 4 or 5 masked points none of 1-4 applies (the DLT is underdetermined): SQPnP on all masked points per candidate focal.
 PARITY UNPINNED against the reference for this row; anchored on ground truth instead (tests/test_pnp.py: known poses are recovered) and
 on HIP == this file.
 """
@@ -122,8 +123,9 @@ def _dlt_rows(S0, S1x, S1y, S2):
     return a1, b1, c
 
 
-def fast_pnp(pts3d, focal, msk, pp=None, num_guessed_focals=100):
-    """init_im_poses.py:300-350.  pts3d (H, W, 3), msk (H, W) bool -> (best_focal, cam_to_world 4x4 fp64 tensor) or (None, None)."""
+def fast_pnp(pts3d, focal, msk, pp=None, num_guessed_focals=100, niter_PnP=100):
+    """init_im_poses.py:300-350.  pts3d (H, W, 3), msk (H, W) bool -> (best_focal, cam_to_world 4x4 fp64 tensor) or (None, None).
+    niter_PnP is the RANSAC iteration count of the reference (:335); here it caps the number of sampled hypotheses at N_HYP, as the HIP path does."""
     if int(msk.sum()) < 4:  # :302-303
         return None, None
     H, W, _ = pts3d.shape
@@ -157,7 +159,7 @@ def fast_pnp(pts3d, focal, msk, pp=None, num_guessed_focals=100):
     # ---- stage 1: N_HYP deterministic 6-point hypotheses, each scored on ALL points (the role RANSAC plays in the reference)
     best = (0, math.inf, None, None, None)
     if int(mflat.sum()) >= SAMPLE:
-        for h in range(N_HYP):
+        for h in range(min(max(int(niter_PnP), 1), N_HYP)):
             idxs = []
             for j in range(SAMPLE):
                 i = sample_index(h, j, npix)
@@ -177,37 +179,54 @@ def fast_pnp(pts3d, focal, msk, pp=None, num_guessed_focals=100):
             score, cost = _count_inliers(R, t, X, px, py, f_h)
             if score > best[0] or (score == best[0] and cost < best[1]):
                 best = (score, cost, R, t, f_h)
-    # ---- stage 2: DLT on the inliers of the best hypothesis (all points when there is none), every candidate focal scored
-    if best[0] >= SAMPLE:
+    if best[0] < SAMPLE:
+        # ---- direct path: no hypothesis found a consensus set -- 4 or 5 masked points (no 6-point sample, and a DLT on all of them is
+        # underdetermined: 8 or 10 equations for 12 unknowns) or every sample degenerate (masked points on one image line are coplanar with
+        # the camera: S0 is singular however many there are).  The named solver copes with both, so it runs on ALL masked points, once per
+        # candidate focal; candidates rank by inlier count, then truncated cost, the earliest among equals.  Kept with a consensus set by
+        # the rule above (>= SAMPLE inliers) or, from fewer masked points, with all of them: cv2.solvePnPRansac can draw only that one
+        # sample there and keeps a model only if it explains the whole sample (oracle/cv2_stub.py: cnt > model_points - 1).
+        best = (0, math.inf, None, None, None)
+        for fc in cands:
+            sol = sqpnp.solve(X.numpy(), torch.stack([px / fc, py / fc], 1).numpy())
+            if sol is None:
+                continue
+            R, t = torch.from_numpy(sol[0]), torch.from_numpy(sol[1])
+            score, cost = _count_inliers(R, t, X, px, py, fc)
+            if score > best[0] or (score == best[0] and cost < best[1]):
+                best = (score, cost, R, t, fc)
+        if best[0] < min(X.shape[0], SAMPLE):
+            return None, None
+        _, _, R, t, f = best
+    else:
+        # ---- stage 2: DLT on the inliers of the best hypothesis, every candidate focal scored
         _, _, R, t, f_h = best
         u, v, z = _project(R, t, X, f_h)
         inl = (((u - px) ** 2 + (v - py) ** 2) <= REPROJ_THR ** 2) & (z > 0)
-    else:
-        inl = torch.ones(X.shape[0], dtype=torch.bool)
-    a1, b1, c = _dlt_rows(*_moments(homog(X[inl]), px[inl], py[inl]))
-    if len(cands) == 1:
-        f = cands[0]
-    else:
-        # the DLT is uncalibrated in disguise: rows 1, 2 come out multiplied by the focal, so |a| / |c| and |b| / |c| estimate it
-        # directly.  Take the grid candidate nearest to their geometric mean, then let the inlier count (the reference's score, :342)
-        # and the truncated cost decide among it and its two neighbours.
-        nc = float(c[:3].norm())
-        f_dlt = math.sqrt(max(float(a1[:3].norm()) * float(b1[:3].norm()), 1e-30)) / max(nc, 1e-30)
-        k0 = cands.index(nearest_cand(f_dlt))
-        best = (0, math.inf, None)
-        for k in range(max(0, k0 - 1), min(len(cands), k0 + 2)):
-            R, t = denorm(*_pose_from_rows(a1, b1, c, cands[k]))
-            R, t = _refine(R, t, X, px, py, cands[k])
-            score, cost = _count_inliers(R, t, X, px, py, cands[k])
-            if score > best[0] or (score == best[0] and cost < best[1]):
-                best = (score, cost, cands[k])
-        if not best[0]:
+        a1, b1, c = _dlt_rows(*_moments(homog(X[inl]), px[inl], py[inl]))
+        if len(cands) == 1:
+            f = cands[0]
+        else:
+            # the DLT is uncalibrated in disguise: rows 1, 2 come out multiplied by the focal, so |a| / |c| and |b| / |c| estimate it
+            # directly.  Take the grid candidate nearest to their geometric mean, then let the inlier count (the reference's score, :342)
+            # and the truncated cost decide among it and its two neighbours.
+            nc = float(c[:3].norm())
+            f_dlt = math.sqrt(max(float(a1[:3].norm()) * float(b1[:3].norm()), 1e-30)) / max(nc, 1e-30)
+            k0 = cands.index(nearest_cand(f_dlt))
+            best = (0, math.inf, None)
+            for k in range(max(0, k0 - 1), min(len(cands), k0 + 2)):
+                R, t = denorm(*_pose_from_rows(a1, b1, c, cands[k]))
+                R, t = _refine(R, t, X, px, py, cands[k])
+                score, cost = _count_inliers(R, t, X, px, py, cands[k])
+                if score > best[0] or (score == best[0] and cost < best[1]):
+                    best = (score, cost, cands[k])
+            if not best[0]:
+                return None, None
+            f = best[2]
+        R, t = denorm(*_pose_from_rows(a1, b1, c, f))
+        if _count_inliers(R, t, X, px, py, f)[0] == 0:
             return None, None
-        f = best[2]
-    R, t = denorm(*_pose_from_rows(a1, b1, c, f))
-    if _count_inliers(R, t, X, px, py, f)[0] == 0:
-        return None, None
-    R, t = _refine(R, t, X, px, py, f)
+        R, t = _refine(R, t, X, px, py, f)
     # ---- stage 3: SQPnP (oracle/sqpnp.py) on the consensus set of that pose -- what cv2.solvePnPRansac(SOLVEPNP_SQPNP) ends with
     u, v, z = _project(R, t, X, f)
     inl = (((u - px) ** 2 + (v - py) ** 2) <= REPROJ_THR ** 2) & (z > 0)
