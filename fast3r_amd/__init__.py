@@ -17,3 +17,5 @@ from .sky import detect_sky_mask, detect_sky_masks, label_components  # noqa: F4
 from .render import Camera, birdseye_camera, pinhole_camera, render_cumulative_pts3d_viz, render_points  # noqa: F401
 from .viz import (CAM_COLORS, SceneViz, auto_cam_size, camera_meshes, plot_3d_points_with_estimated_camera_poses,  # noqa: F401
                   render_mesh)
+from .maps import (colorize_maps, maybe_plot_local_depth_and_conf, plot_confidence_maps, plot_rgb_images,  # noqa: F401
+                   save_pointmaps_and_camera_parameters_to_folder)

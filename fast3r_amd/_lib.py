@@ -30,6 +30,8 @@ CLOUD_TILE, CLOUD_SORT_TILE, CLOUD_FPS_TILE, CLOUD_FPS_ONE_MAX = 1024, 2048, 102
 RENDER_CENTER_PARTS = 1024  # F3R_RENDER_CENTER_PARTS: rows of the scratch f3r_render_center takes
 RASTER_SMALL_PIXELS = 64  # F3R_RASTER_SMALL_PIXELS: the largest pixel box a stage-1 thread of the rasteriser draws itself
 F3R_FPS_AUTO, F3R_FPS_ONE, F3R_FPS_TILED = 0, 1, 2
+MAPS_TILE = 1024  # F3R_MAPS_TILE: pixels per workgroup of the map-picture kernels
+F3R_MAPS_LUT, F3R_MAPS_RGB = 0, 1
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
 
@@ -193,6 +195,7 @@ SYMBOLS = {
     "f3r_raster_workspace_bytes": (ctypes.c_size_t, [_c_i64]),
     "f3r_raster_triangles": (ctypes.c_int, [_c_vp, _c_i64, _c_vp, ctypes.c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_double),
                                             ctypes.c_int, ctypes.c_int, _c_vp, _c_vp, ctypes.c_size_t, _c_i64, _c_vp]),
+    "f3r_maps_colorize": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp]),
 }
 
 # entry points added after ABI_VERSION: {symbol: the f3r_version() that first exports it}.  lib() binds one only when the loaded library
@@ -202,11 +205,17 @@ SYMBOL_SINCE_430 = {name: 430 for name in SYMBOLS if name.startswith("f3r_render
 # entry points gated by presence, not by version (f3r_version() did not move for them): lib() binds one only when the loaded library exports
 # it, and entry() tells the caller of an absent one to rebuild.  The triangle rasteriser
 SYMBOL_IF_PRESENT = frozenset(name for name in SYMBOLS if name.startswith("f3r_raster_"))
+SYMBOL_IF_PRESENT_MAPS = frozenset(name for name in SYMBOLS if name.startswith("f3r_maps_"))  # the map pictures, gated the same way
 
 
 def symbol_since(name: str) -> int:
     """the f3r_version() that first exports `name`: the one lookup of lib() and entry() over the tables above (0: ABI_VERSION has it)"""
     return SYMBOL_SINCE.get(name, SYMBOL_SINCE_430.get(name, 0))
+
+
+def if_present(name: str) -> bool:
+    """is `name` gated by presence: the one lookup of lib() and entry() over the two sets above"""
+    return name in SYMBOL_IF_PRESENT or name in SYMBOL_IF_PRESENT_MAPS
 
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")
@@ -239,7 +248,7 @@ def lib():
         if l.f3r_version() < ABI_VERSION:
             raise F3RError(f"{LIB_PATH} is version {l.f3r_version()}, this host code needs >= {ABI_VERSION}: rebuild it (fast3r_amd/csrc/build.sh)")
         for name in SYMBOLS:
-            if name in SYMBOL_IF_PRESENT and not hasattr(l, name):
+            if if_present(name) and not hasattr(l, name):
                 continue
             if symbol_since(name) <= l.f3r_version():
                 bind(name)
@@ -261,7 +270,7 @@ def entry(name: str):
     have, need = library_version(), symbol_since(name)
     if have < need:
         raise F3RError(f"{LIB_PATH} is version {have}, {name} needs >= {need}: rebuild it (fast3r_amd/csrc/build.sh)")
-    if name in SYMBOL_IF_PRESENT and not hasattr(l, name):
+    if if_present(name) and not hasattr(l, name):
         raise F3RError(f"{LIB_PATH} does not export {name}: rebuild it (fast3r_amd/csrc/build.sh)")
     return getattr(l, name)
 

@@ -113,6 +113,42 @@ __device__ __forceinline__ void block_sum(const double* v, double (*red)[LD], do
   __syncthreads();
 }
 
+// ---- minima and maxima of integers (for floats: of their order-preserving keys).  Order-free: every tree gives the same value.
+template <class T>
+__device__ __forceinline__ T wave_min(T x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = min(x, (T)__shfl_xor(x, off, 64));
+  return x;
+}
+template <class T>
+__device__ __forceinline__ T wave_max(T x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x = max(x, (T)__shfl_xor(x, off, 64));
+  return x;
+}
+
+// lo = the minimum of lo, hi = the maximum of hi over the NT threads of the workgroup, valid in thread 0 on return.  red: the caller's LDS,
+// NT / 64 rows.  Every thread calls it; red may be reused on return.
+template <int NT>
+__device__ __forceinline__ void block_min_max(uint32_t& lo, uint32_t& hi, uint32_t (*red)[2]) {
+  static_assert(NT % 64 == 0, "block_min_max: shape");
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  lo = wave_min(lo);
+  hi = wave_max(hi);
+  if (lane == 0) {
+    red[wv][0] = lo;
+    red[wv][1] = hi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < NT / 64; ++w) {
+      lo = min(lo, red[w][0]);
+      hi = max(hi, red[w][1]);
+    }
+  }
+  __syncthreads();
+}
+
 // ---- exclusive scan, in place, of row blockIdx.x: uint32 a[start(row) .. start(row) + len(row)); totals[row] = its sum (if totals).
 // With ts: row = segment, start = 256 ts[row], len = 256 (ts[row + 1] - ts[row]); without: dense rows of len0, start = row * len0.
 // One workgroup of SCAN_NT threads per row.  A template so that only the files that launch it carry a copy.

@@ -1,5 +1,5 @@
 """Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
-loss, scene assembly, sky detection, mesh export, point-cloud export and the point-splat renderer.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer and the map pictures.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
 out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
 """
 import ctypes
@@ -826,3 +826,77 @@ def raster_triangles(vertices, faces, camera, keys, *, f0=0, f1=None, index_base
     with torch.cuda.device(vertices.device):
         check(fn(ptr(vertices), nv, ptr(faces), mesh_index_id(faces.dtype), nf, int(f0), f1, int(index_base), (ctypes.c_double * 17)(*cam),
                  width, height, ptr(keys), ptr(ws), nbytes, int(faces_per_launch), stream_ptr()), "f3r_raster_triangles")
+
+
+# ------------------------------------------------------------------------------------------------------------------- map pictures
+def _map_source(t):
+    """a (H, W) fp32 view as (tensor to keep alive, element stride): read where it lies when its elements are evenly spaced in row-major
+    order -- a dense map, or one channel of an (H, W, C) tensor -- and from a dense copy otherwise"""
+    H, W = t.shape
+    step = t.stride(1) if W > 1 else (t.stride(0) if H > 1 else 1)
+    if step < 1 or (W > 1 and H > 1 and t.stride(0) != W * step):
+        return t.contiguous(), 1
+    return t, step
+
+
+def maps_table(srcs, dsts, mode=_lib.F3R_MAPS_LUT):
+    """The checked per-map table of f3r_maps_colorize for lists of sources and destinations (as `maps_colorize` takes them): -> dict(table:
+    the device words, host_rows: the rows for the argument checks, n, n_tiles, mode, device, keep: the tensors the table points into).
+    One small upload."""
+    n = len(srcs)
+    if n < 1 or len(dsts) != n:
+        raise ValueError(f"maps_colorize: need one destination per map and at least one map (got {n} maps, {len(dsts)} destinations)")
+    if mode not in (_lib.F3R_MAPS_LUT, _lib.F3R_MAPS_RGB):
+        raise ValueError(f"maps_colorize: unknown mode {mode}")
+    rgb = mode == _lib.F3R_MAPS_RGB
+    for i, t in enumerate(list(srcs) + list(dsts)):
+        require_gpu(t, f"map {i % n}")
+    dev = srcs[0].device
+    rows, pixels, keep = [], [], []
+    for i, (s, d) in enumerate(zip(srcs, dsts)):
+        if s.dtype != torch.float32 or s.dim() != (3 if rgb else 2) or (rgb and s.shape[0] != 3) or s.device != dev:
+            raise ValueError(f"maps_colorize: map {i} must be {'(3, H, W)' if rgb else '(H, W)'} fp32 on {dev}, got {tuple(s.shape)} {s.dtype} "
+                             f"on {s.device}")
+        H, W = (int(x) for x in s.shape[-2:])
+        if H < 1 or W < 1 or H * W > 2 ** 30:
+            raise ValueError(f"maps_colorize: map {i} is {H} x {W}; need H, W >= 1 and H * W <= 2^30")
+        if d.dtype != torch.uint8 or tuple(d.shape) != (H, W, 4) or d.device != dev or d.stride(2) != 1 or d.stride(1) != 4:
+            raise ValueError(f"maps_colorize: destination {i} must be ({H}, {W}, 4) uint8 on {dev} with dense pixels, got {tuple(d.shape)} "
+                             f"{d.dtype} on {d.device}, strides {d.stride()}")
+        pitch = d.stride(0) if H > 1 else 4 * W
+        s, step = (s.contiguous(), 1) if rgb else _map_source(s)
+        keep += [s, d]
+        rows.append([s.data_ptr(), step, H, W, d.data_ptr(), pitch])
+        pixels.append(H * W)
+    starts = tile_starts(pixels, _lib.MAPS_TILE)
+    host = table_words(rows, starts)
+    return {"table": host.to(dev), "host_rows": (ctypes.c_int64 * (6 * n))(*host[:6 * n].tolist()), "n": n, "n_tiles": starts[-1], "mode": int(mode),
+            "device": dev, "keep": keep}
+
+
+def maps_launch(plan, lut=None):
+    """f3r_maps_colorize on a table `maps_table` built: launches only.  -> the (n, 2) fp32 device ranges, or None for F3R_MAPS_RGB"""
+    fn = _lib.entry("f3r_maps_colorize")
+    n, dev, rgb = plan["n"], plan["device"], plan["mode"] == _lib.F3R_MAPS_RGB
+    if not rgb:
+        require_gpu(lut, "lut")
+        if lut.dtype != torch.uint8 or lut.numel() != 768 or lut.device != dev or not lut.is_contiguous():
+            raise ValueError(f"maps_colorize: lut must be a contiguous 256 x 3 uint8 tensor on {dev}")
+    small = None if rgb else torch.empty((2, n, 2), dtype=torch.int32, device=dev)   # the keys, then the ranges
+    with torch.cuda.device(dev):
+        check(fn(ptr(plan["table"]), plan["host_rows"], n, plan["n_tiles"], plan["mode"], None if rgb else ptr(lut),
+                 None if rgb else small[0].data_ptr(), None if rgb else small[1].data_ptr(), stream_ptr()), "f3r_maps_colorize")
+    return None if rgb else small[1].view(torch.float32)
+
+
+def maps_colorize(srcs, dsts, lut=None, *, mode=_lib.F3R_MAPS_LUT):
+    """f3r_maps_colorize (include/f3r.h) on a list of maps in one call.  srcs[i]: with F3R_MAPS_LUT an (H, W) fp32 GPU tensor, which may be
+    a view of one channel of an (H, W, C) tensor (read in place); with F3R_MAPS_RGB the (3, H, W) fp32 planes.  dsts[i]: the (H, W, 4)
+    uint8 picture it lands in, which may be a window of a larger picture (its row stride is the pitch); written in place, only inside the
+    window.  lut: (256, 3) uint8 on the device (F3R_MAPS_LUT).  -> the (n, 2) fp32 device tensor of (vmin, vmax) per map, or None for
+    F3R_MAPS_RGB."""
+    _lib.entry("f3r_maps_colorize")   # a library without it: say so before looking at a tensor
+    plan = maps_table(srcs, dsts, mode)
+    out = maps_launch(plan, lut)
+    del plan  # the launches are stream-ordered before the caching allocator can hand the table and the copies out again
+    return out

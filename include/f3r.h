@@ -829,6 +829,44 @@ int f3r_raster_triangles(const float* vertices, int64_t nv, const void* faces, i
                          int64_t faces_per_launch, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Map pictures: scalar fields and images as RGBA8 pictures -- what plot_confidence_maps, maybe_plot_local_depth_and_conf and
+ * plot_rgb_images of the reference's notebooks/demo_multiview.ipynb save through matplotlib.pylab.imsave(path, map, cmap='turbo' | 'Greys')
+ * and imsave(path, uint8 image), byte for byte (matplotlib 3.10: Normalize, then Colormap.__call__(bytes=True)).  Python:
+ * fast3r_amd/maps.py.  Kernels: fast3r_amd/csrc/f3r_maps.hip.  f3r_version() is unchanged: a caller learns whether a library has this
+ * entry point by looking for it.
+ * One call covers n_maps maps, which may differ in size.  table: device int64, n_maps rows of 6 words
+ *   { source pointer (fp32), element stride in floats, H, W, destination pointer (bytes), destination row pitch in bytes },
+ *   then the n_maps + 1 running tile counts of the maps, ceil(H W / F3R_MAPS_TILE) tiles each; host_rows: the same rows in HOST memory
+ *   (the argument checks read them; the kernels read the device copy).  Pixel (y, x) of a map is source[(y W + x) stride] -- stride 3 and
+ *   a pointer to element 2 read the z channel of an [H][W][3] pointmap in place -- and lands in the four bytes at destination + y pitch +
+ *   4 x as R, G, B, A, so a map can be written into its cell of a larger picture.  Bytes outside the H x W cells are not written.
+ * mode F3R_MAPS_LUT, per map, every operation rounded on its own, as numpy 2 runs matplotlib's lines on an fp32 array (vmin and vmax are
+ * Python floats there, so `resdat -= vmin` and `resdat /= (vmax - vmin)` compute in fp64 and round into the fp32 array):
+ *   1. vmin, vmax = the fp32 minimum and maximum with numpy's semantics: a NaN anywhere makes both NaN; +-inf take part as values (of
+ *      -0.0 and +0.0 the minimum is -0.0 and the maximum +0.0, where numpy's choice depends on their order; no byte depends on it).
+ *      They are reduced as order-preserving integer keys with integer atomics: two runs give the same bits.  keys: device uint32
+ *      [n_maps][2], scratch.  ranges: device fp32 [n_maps][2] = { vmin, vmax }, written for the caller.
+ *   2. x = 0 if vmin == vmax, otherwise t = a - vmin in fp32 (equal to the fp64 difference rounded to fp32: 53 >= 2 * 24 + 2 bits), then
+ *      x = (float)((double)t / ((double)vmax - (double)vmin)): a correctly rounded fp64 division by the fp64 range -- which is finite
+ *      where the fp32 range overflows, and is not rounded to fp32 -- rounded once more to fp32.  An all-fp32 division gives another
+ *      byte at about one pixel in 10^4 (tests/map_cases.py "fp64_divisor" holds one);
+ *   3. xa = x * 256; xa == 256 becomes 255;
+ *   4. a NaN xa gives the bytes (0, 0, 0, 0); otherwise i = trunc(xa) clamped to [0, 255] and the bytes are (lut[i][0], lut[i][1],
+ *      lut[i][2], 255).  lut: device bytes [256][3].
+ * mode F3R_MAPS_RGB: the source is three planes ([3][H][W]; plane c begins H W stride elements after plane c - 1), each channel
+ *   trunc((x + 1) * 127.5) -- an add and a multiply, each rounded -- clipped to [0, 255] (NaN reads as 0), alpha 255.  lut, keys and ranges
+ *   are not used and may be null.
+ * Launches only (one for RGB, three for LUT): nothing is allocated, copied or waited for.  Inputs are not written to.
+ * Limits, F3R_ERR_ARG before any launch: a null table or host_rows; n_maps < 1; an unknown mode; in mode F3R_MAPS_LUT a null lut, keys or
+ *   ranges; per map a null source or destination, H or W < 1 or H W > 2^30, a stride outside [1, 2^31), a pitch smaller than 4 W, a
+ *   source, destination or pitch that is not a multiple of 4 bytes; n_tiles that is not the maps' tile count.
+ */
+#define F3R_MAPS_TILE 1024
+typedef enum { F3R_MAPS_LUT = 0, F3R_MAPS_RGB = 1 } f3r_maps_mode;
+int f3r_maps_colorize(const int64_t* table, const int64_t* host_rows, int n_maps, int64_t n_tiles, int mode, const uint8_t* lut,
+                      uint32_t* keys, float* ranges, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
  * f3r_resample_u8 is ONE pass of PIL.Image.resize for 8-bit RGB (`_resize_pil_image`, :68-74; Pillow's Resample.c): axis 1 =
  * horizontal ([H][W][3] -> [H][out_size][3]), axis 0 = vertical ([H][W][3] -> [out_size][W][3]); bounds [out_size][2] = {first source

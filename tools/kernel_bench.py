@@ -1,6 +1,6 @@
 """Kernel micro-benchmarks on the GPU box (interleaved rounds, random data, HIP events on the launch stream): the attention kernels
 f3r_attn_fwd can take (--what attnproduct / attnsel / attnhd) and the model's GEMM / conv shapes per f3r_gemm_args.kernel_sel, with the vendor
-library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement; --what scene: scene assembly and PLY export likewise; --what cloud: point-cloud export (combine, voxel, farthest point) likewise; --what sky: sky detection alone, inside assemble_scene and next to the CPU (--what skydetect: its kernels alone, for a profiler run).  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
+library beside them (--what gemmref); --what loss: the validation criterion next to a torch-eager restatement; --what scene: scene assembly and PLY export likewise; --what cloud: point-cloud export (combine, voxel, farthest point) likewise; --what sky: sky detection alone, inside assemble_scene and next to the CPU (--what skydetect: its kernels alone, for a profiler run); --what maps: the map pictures next to PNG encoding and matplotlib's imsave.  Prints one JSON line per item.  (--what lab / labtime: ablations of the 8-wave GEMM, need
 F3R_LAB_LIB=tools/lab/libf3r_hip_lab.so.)"""
 import argparse
 import math
@@ -904,6 +904,104 @@ def bench_cloud(sizes=(100, 320), H=512, W=512, max_num_points=1_000_000, out_pa
         f.write(line + "\n")
 
 
+def bench_maps(n=320, H=512, W=512, host_views=8, out_path="profiles/maps_bench.jsonl"):
+    """The map pictures (fast3r_amd/maps.py, f3r_maps.hip) at n views of H x W generated on the device, warmed up, medians of 7 with
+    min / max.  Device time: stream events around 5 back-to-back `post_ops.maps_launch` calls on a table built before (the launches alone,
+    the queue never empty), per call:
+    * the n confidence maps (dense, 16-byte loads) into separate pictures, and into the cells of one contact sheet;
+    * the z channel of n (H, W, 3) pointmaps read in place (element stride 3);
+    * the n images (three planes each) in RGB mode;
+    with the algorithmic bytes of each -- a map is read twice and written once: 12 bytes per pixel; the images are read once: 16 -- and
+    the rate they imply.  Separately the host side: the whole `post_ops.maps_colorize` call on a wall clock (checks, table and upload for
+    n maps, then the launches, synchronised); the sheet's device-to-host copy, and PNG encoding of `host_views` pictures on one
+    thread (PIL, as `render._save_png`), and the path this replaces: `matplotlib.pylab.imsave(path, conf, cmap='turbo')` of the same
+    `host_views` host maps on this machine's CPU, per view.  One JSON line, appended to profiles/."""
+    import os
+    import statistics
+    import tempfile
+    import time
+    import numpy as np
+    from fast3r_amd import maps, render
+
+    def stats(ts):
+        return {"median_ms": round(statistics.median(ts), 3), "min_ms": round(min(ts), 3), "max_ms": round(max(ts), 3), "n": len(ts)}
+
+    def events(fn, rounds=7, inner=5):
+        fn()
+        ts = []
+        for _ in range(rounds):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) / inner)
+        return stats(ts)
+
+    def device_time(srcs, dsts, lut, mode, nbytes):
+        plan = post_ops.maps_table(srcs, dsts, mode)
+        return with_rate(events(lambda: post_ops.maps_launch(plan, lut)), nbytes)
+
+    def with_rate(st, nbytes):
+        return dict(st, algorithmic_bytes=nbytes, TB_per_s_at_median=round(nbytes / (st["median_ms"] * 1e-3) / 1e12, 3))
+
+    g = torch.Generator(device=DEV).manual_seed(0)
+    conf = 1.0 + 20.0 * torch.rand(n, H, W, generator=g, device=DEV) ** 2
+    pts = torch.randn(n, H, W, 3, generator=g, device=DEV)
+    img = torch.rand(n, 3, H, W, generator=g, device=DEV) * 2 - 1
+    turbo, greys = maps._lut_on(conf.device, "turbo"), maps._lut_on(conf.device, "Greys")
+    pictures = torch.empty((n, H, W, 4), dtype=torch.uint8, device=DEV)
+    height, width, _, origins = maps.sheet_layout([(H, W)] * n)
+    sheet = torch.zeros((height, width, 4), dtype=torch.uint8, device=DEV)
+    cells = [sheet[y:y + H, x:x + W] for ((y, x),) in origins]
+    px = n * H * W
+    rec = {"what": "maps", "device": torch.cuda.get_device_name(0), "views": n, "HW": [H, W], "tile": _lib.MAPS_TILE,
+           "conf_separate_pictures": device_time(list(conf), list(pictures), turbo, _lib.F3R_MAPS_LUT, 12 * px),
+           "conf_into_sheet_cells": device_time(list(conf), cells, turbo, _lib.F3R_MAPS_LUT, 12 * px),
+           "depth_channel_in_place": device_time(list(pts[..., 2]), list(pictures), greys, _lib.F3R_MAPS_LUT, 12 * px),
+           "rgb_planes": device_time(list(img), list(pictures), None, _lib.F3R_MAPS_RGB, 16 * px)}
+    walls = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        post_ops.maps_colorize(list(conf), cells, turbo)
+        torch.cuda.synchronize()
+        walls.append((time.perf_counter() - t0) * 1e3)
+    rec["conf_into_sheet_cells_wall_clock"] = stats(walls)
+    t0 = time.perf_counter()
+    host_sheet = sheet.cpu().numpy()
+    rec["sheet_to_host_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+    k = min(host_views, n)
+    with tempfile.TemporaryDirectory() as tmp:
+        enc = []
+        for i in range(k):
+            (y, x), = origins[i]
+            a = np.ascontiguousarray(host_sheet[y:y + H, x:x + W])
+            t0 = time.perf_counter()
+            render._save_png(a, os.path.join(tmp, f"view_{i}_conf.png"))
+            enc.append((time.perf_counter() - t0) * 1e3)
+        rec["png_encode_per_view_one_thread"] = stats(enc)
+        rec["png_workers"] = render.PNG_WORKERS
+        try:
+            from matplotlib import pylab
+            host_conf = conf[:k].cpu().numpy()
+            ims = []
+            for i in range(k):
+                t0 = time.perf_counter()
+                pylab.imsave(os.path.join(tmp, f"imsave_{i}.png"), host_conf[i], cmap="turbo")
+                ims.append((time.perf_counter() - t0) * 1e3)
+            rec["matplotlib_imsave_per_view_cpu"] = stats(ims)
+        except ImportError:
+            rec["matplotlib_imsave_per_view_cpu"] = "not measured: matplotlib does not import here"
+    line = json.dumps(rec)
+    print(line)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "a") as f:
+        f.write(line + "\n")
+
+
 def bench_posemetric(sizes=(320, 1500), H=512, W=512, out_path="profiles/r07_pose_metric_bench.jsonl"):
     """camera_pose_metrics (RRA / RTA / mAA from f3r_pose_pair_metrics) at B = 1 next to estimate_poses at the same view count in the same
     run: the metric stage is O(pairs) trigonometry on a few hundred kilobytes of poses and must stay below 5 % of the PnP stage.  Wall
@@ -1202,6 +1300,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if args.what == "scenesort":  # f3r_scene_sort alone at N = 100, for a profiler run of its own
         bench_scene(sizes=(100,), sort_only=True)
+        sys.exit(0)
+    if args.what == "maps":  # the map pictures: conf maps, the depth channel in place and the images, next to PNG encoding and matplotlib's imsave
+        bench_maps(*(tuple(int(v) for v in args.views.split(","))[:1] if args.views != "20,100" else ()))
         sys.exit(0)
     if args.what == "posemetric":  # RRA / RTA / mAA over all view pairs next to the PnP stage that feeds it
         bench_posemetric()
