@@ -19,3 +19,5 @@ from .viz import (CAM_COLORS, SceneViz, auto_cam_size, camera_meshes, plot_3d_po
                   render_mesh)
 from .maps import (colorize_maps, maybe_plot_local_depth_and_conf, plot_confidence_maps, plot_rgb_images,  # noqa: F401
                    save_pointmaps_and_camera_parameters_to_folder)
+from .gt_views import (build_gt_views, crop_resize_if_necessary, depthmap_to_absolute_camera_coordinates,  # noqa: F401
+                       depthmap_to_camera_coordinates)

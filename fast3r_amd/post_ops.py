@@ -1,5 +1,5 @@
 """Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
-loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer and the map pictures.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer, the map pictures and the ground-truth views.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
 out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
 """
 import ctypes
@@ -900,3 +900,112 @@ def maps_colorize(srcs, dsts, lut=None, *, mode=_lib.F3R_MAPS_LUT):
     out = maps_launch(plan, lut)
     del plan  # the launches are stream-ordered before the caching allocator can hand the table and the copies out again
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------- ground-truth views
+def _gtview_geometry(window, resized, crop, who):
+    """the checked ints of a launch group's geometry: window (x, y, w, h) in the frame, resized (w, h), crop (x, y, w, h) in the resized picture"""
+    wx, wy, ww, wh = (int(v) for v in window)
+    rw, rh = (int(v) for v in resized)
+    cx, cy, cw, ch = (int(v) for v in crop)
+    if min(wx, wy) < 0 or min(ww, wh) < 1 or max(wx + ww, wy + wh) > 2 ** 24:
+        raise ValueError(f"{who}: window {window} is not a box of a frame")
+    if min(rw, rh) < 1 or max(rw, rh) > 2 ** 24 or min(cx, cy) < 0 or min(cw, ch) < 1 or cx + cw > rw or cy + ch > rh:
+        raise ValueError(f"{who}: crop {crop} leaves the resized {rw} x {rh} picture")
+    return (wx, wy, ww, wh), (rw, rh), (cx, cy, cw, ch)
+
+
+def _gtview_sources(frames, window, dtype, channels, who):
+    """frames: per view a GPU tensor (H, W[, 3]) of `dtype` that contains the window, with dense pixels (rows may be pitched) -> (device
+    int64 table [n][2] = pointer, row pitch in elements, the tensors it points into)"""
+    wx, wy, ww, wh = window
+    n = len(frames)
+    if n < 1:
+        raise ValueError(f"{who}: need at least one view")
+    dev, keep, rows = frames[0].device, [], []
+    for i, t in enumerate(frames):
+        require_gpu(t, f"view {i}")
+        want = 3 if channels else 2
+        if t.dtype != dtype or t.dim() != want or (channels and t.shape[2] != channels) or t.device != dev:
+            raise ValueError(f"{who}: view {i} must be (H, W{', 3' if channels else ''}) {dtype} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+        H, W = int(t.shape[0]), int(t.shape[1])
+        if wx + ww > W or wy + wh > H:
+            raise ValueError(f"{who}: view {i} is {H} x {W}; the window (x {wx}, y {wy}, {ww} x {wh}) leaves it")
+        dense = t.stride(1) == (channels or 1) and (not channels or t.stride(2) == 1) and t.stride(0) >= W * (channels or 1)
+        if not dense:
+            t = t.contiguous()
+        keep.append(t)
+        rows.append([t.data_ptr(), t.stride(0)])
+    return torch.tensor(rows, dtype=torch.int64).to(dev), keep
+
+
+def gtview_resample(images, window, tables_h, tables_v, resized, crop, row_span, transpose=False):
+    """f3r_gtview_resample (include/f3r.h) on one launch group.  images: per view an (H, W, 3) uint8 GPU tensor.  window: crop box 1 (x, y, w,
+    h).  tables_h / tables_v: (ksize, bounds int32 (res, 2), kk int32 (res, ksize)) device tensors of the two passes, made for the window's
+    size (`image.resample_tables`).  resized: (w, h).  crop: box 2 (x, y, w, h).  row_span: (first, end) of the window rows the kept output rows
+    read (from the host copy of tables_v: the intermediate holds only those).  -> (img_u8 (n, h, w, 3) uint8, img (n, 3, h, w) fp32),
+    h and w swapped when transpose."""
+    fn, size_fn = _lib.entry("f3r_gtview_resample"), _lib.entry("f3r_gtview_workspace_bytes")
+    window, resized, crop = _gtview_geometry(window, resized, crop, "gtview_resample")
+    table, keep = _gtview_sources(images, window, torch.uint8, 3, "gtview_resample")
+    dev, n = table.device, len(images)
+    (kh, bh, wh_), (kv, bv, wv_) = tables_h, tables_v
+    for name, (k, b, w), res in (("tables_h", (kh, bh, wh_), resized[0]), ("tables_v", (kv, bv, wv_), resized[1])):
+        for t in (b, w):
+            require_gpu(t, name)
+        if b.dtype != torch.int32 or w.dtype != torch.int32 or tuple(b.shape) != (res, 2) or tuple(w.shape) != (res, int(k)) or not b.is_contiguous() \
+                or not w.is_contiguous() or b.device != dev or w.device != dev:
+            raise ValueError(f"gtview_resample: {name} must be (ksize, int32 ({res}, 2), int32 ({res}, ksize)) contiguous on {dev}")
+    cx, cy, cw, ch = crop
+    row0, row1 = (int(v) for v in row_span)
+    if row0 < 0 or row1 > window[3] or row1 <= row0:
+        raise ValueError(f"gtview_resample: row_span [{row0}, {row1}) is not a run of rows of a window of {window[3]} rows")
+    rows = row1 - row0
+    oh, ow = (cw, ch) if transpose else (ch, cw)
+    img_u8 = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+    img = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev)
+    nbytes = size_fn(n, rows, cw)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(ptr(table), n, *window, ptr(bh), ptr(wh_), int(kh), resized[0], ptr(bv), ptr(wv_), int(kv), resized[1], row0, rows, cx, cy, cw, ch,
+                 int(bool(transpose)), ptr(img_u8), ptr(img), ptr(ws), nbytes, stream_ptr()), "f3r_gtview_resample")
+    del keep, ws  # the launches are stream-ordered before the caching allocator can hand these out again
+    return img_u8, img
+
+
+def gtview_unproject(depthmaps, cams, window, nearest, resized, crop, transpose=False, *, pose=True, finite_mask=True, want_points=True, flag=None):
+    """f3r_gtview_unproject (include/f3r.h) on one launch group.  depthmaps: per view an (H, W) fp32 GPU tensor.  cams: (n, 25) fp32 device
+    tensor, per view the intrinsics as returned (rows [1, 0, 2] when transpose) and the pose.  nearest: None (no resize) or (nx int32
+    (res_w,), ny int32 (res_h,)) device tensors.  flag: None or a zeroed int32 device word, raised for a depth that is not finite.
+    -> (depthmap (n, h, w) fp32, pts3d (n, h, w, 3) fp32 or None, valid_mask (n, h, w) bool or None), h and w swapped when transpose."""
+    fn = _lib.entry("f3r_gtview_unproject")
+    window, resized, crop = _gtview_geometry(window, resized, crop, "gtview_unproject")
+    table, keep = _gtview_sources(depthmaps, window, torch.float32, 0, "gtview_unproject")
+    dev, n = table.device, len(depthmaps)
+    require_gpu(cams, "cams")
+    if cams.dtype != torch.float32 or tuple(cams.shape) != (n, _lib.GTVIEW_CAM_WORDS) or not cams.is_contiguous() or cams.device != dev:
+        raise ValueError(f"gtview_unproject: cams must be a contiguous ({n}, {_lib.GTVIEW_CAM_WORDS}) fp32 tensor on {dev}")
+    nx = ny = None
+    if nearest is not None:
+        nx, ny = nearest
+        for name, t, res in (("nx", nx, resized[0]), ("ny", ny, resized[1])):
+            require_gpu(t, name)
+            if t.dtype != torch.int32 or tuple(t.shape) != (res,) or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"gtview_unproject: {name} must be a contiguous int32 ({res},) tensor on {dev}")
+    elif resized != (window[2], window[3]):
+        raise ValueError(f"gtview_unproject: without nearest tables the resized size {resized} must be the window's")
+    if flag is not None:
+        require_gpu(flag, "flag")
+        if flag.dtype != torch.int32 or flag.numel() != 1 or flag.device != dev:
+            raise ValueError(f"gtview_unproject: flag must be one int32 word on {dev}")
+    cx, cy, cw, ch = crop
+    oh, ow = (cw, ch) if transpose else (ch, cw)
+    depth = torch.empty((n, oh, ow), dtype=torch.float32, device=dev)
+    pts = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev) if want_points else None
+    valid = torch.empty((n, oh, ow), dtype=torch.uint8, device=dev) if want_points else None
+    flags = (_lib.F3R_GTVIEW_POSE if pose else 0) | (_lib.F3R_GTVIEW_FINITE_MASK if finite_mask else 0)
+    with torch.cuda.device(dev):
+        check(fn(ptr(table), ptr(cams), n, *window, ptr(nx), ptr(ny), resized[0], resized[1], cx, cy, cw, ch, int(bool(transpose)), flags, ptr(depth),
+                 ptr(pts), ptr(valid), ptr(flag), stream_ptr()), "f3r_gtview_unproject")
+    del keep
+    return depth, pts, None if valid is None else valid.view(torch.bool)

@@ -867,6 +867,54 @@ int f3r_maps_colorize(const int64_t* table, const int64_t* host_rows, int n_maps
                       uint32_t* keys, float* ranges, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ground-truth views: posed RGB-D frames as the views the reference's datasets hand to the metrics and the loss -- what
+ * BaseStereoViewDataset.__getitem__ (fast3r/dust3r/datasets/base/base_stereo_view_dataset.py:78-142) makes of a frame through
+ * _crop_resize_if_necessary (:165-221), ImgNorm, depthmap_to_absolute_camera_coordinates (dust3r/utils/geometry.py:186-243) and
+ * transpose_to_landscape (:243-261).  Python: fast3r_amd/gt_views.py, whose plan_view does the reference's host arithmetic (crop boxes,
+ * sizes, intrinsics).  Kernels: fast3r_amd/csrc/f3r_views.hip.  f3r_version() is unchanged: a caller learns whether a library has these
+ * entry points by looking for them.
+ * One call covers a launch group: n_views views that share every number below and differ in their source pointers and cameras.
+ * Geometry: crop box 1 (win_x, win_y, win_w, win_h) in the frame, around the rounded principal point; the window resized to res_w x
+ * res_h; crop box 2 (crop_x, crop_y, out_w, out_h) in the resized picture: the out_h x out_w picture (v, u) of the view.  With
+ * transpose = 1 (a portrait view) every output is written transposed: output pixel (oy, ox) is picture pixel (v, u) = (ox, oy), and the
+ * output is out_w rows of out_h pixels.
+ * f3r_gtview_resample: PIL.Image.crop(box 1).resize((res_w, res_h), LANCZOS | BICUBIC).crop(box 2) and ImgNorm, bit for bit.
+ *   src_table: device int64 [n_views][2] = { pointer to the frame's [H][W][3] bytes, row pitch in bytes }; the frame must contain box 1.
+ *   bounds_h int32 [res_w][2] = { first source column inside the window, count } and kk_h int32 [res_w][ksize_h]: Pillow's 22-bit
+ *   fixed-point filter tables (precompute_coeffs / normalize_coeffs_8bpc) for in_size = win_w, so taps are clipped at the window's edges
+ *   as Pillow clips them at the cropped picture's; bounds_v, kk_v, ksize_v the same for rows (in_size = win_h).  The horizontal pass
+ *   writes an 8-bit intermediate (accumulator 1 << 21, shift >> 22, saturation) of the window rows [row0, row0 + rows) -- the caller
+ *   passes the rows the kept output rows read -- and the columns crop box 2 keeps, into workspace (f3r_gtview_workspace_bytes(n_views,
+ *   rows, out_w) bytes, 16-byte aligned); the vertical pass writes img_u8 [n_views][out_h][out_w][3] and img fp32 [n_views][3][out_h][out_w] =
+ *   ((u / 255) - 0.5) / 0.5, three rounded operations in torchvision's order (dimensions swapped when transposed).
+ * f3r_gtview_unproject: depth and points of the same picture.  src_table: device int64 [n_views][2] = { pointer to the frame's fp32
+ *   depth, row pitch in floats }.  nx int32 [res_w], ny int32 [res_h]: cv2.resize(..., INTER_NEAREST)'s source index per resized column
+ *   and row, inside the window (both null: no resize, res = win).  cams: device fp32 [n_views][F3R_GTVIEW_CAM_WORDS] = the 3 x 3
+ *   intrinsics of the picture as the view returns them (rows [1, 0, 2] of K when transposed), then the 4 x 4 cam-to-world pose.  Per pixel:
+ *   z = depth[win_y + ny[crop_y + v]][win_x + nx[crop_x + u]]; x = (u - cu) z / fu, y = (v - cv) z / fv in fp64, every operation rounded,
+ *   rounded once to fp32 (numpy promotes the reference's expression to float64); with F3R_GTVIEW_POSE the point is R (x, y, z) + t in
+ *   fp32, ((r0 x + r1 y) + r2 z) + t, each operation rounded; valid = z > 0, and with F3R_GTVIEW_FINITE_MASK also every coordinate
+ *   finite.  Outputs, each optional but one: depthmap fp32 [n_views][out_h][out_w], pts3d fp32 [...][3], valid_mask bytes 0 / 1
+ *   (dimensions swapped when transposed).  flag (optional): one device int32 the caller zeroed; set to 1 with a plain store when a
+ *   gathered depth is not finite.
+ * Launches only (two, and one): nothing is allocated, copied or waited for.  Inputs are not written to.  Table entries that point
+ * outside the window are clamped to it, so a wrong table gives wrong pixels, never a fault.
+ * Limits, F3R_ERR_ARG before any launch: a null pointer where one is needed; n_views outside [1, 2^20]; a box with a negative origin, an
+ * empty size or an end beyond 2^24; crop box 2 outside the resized picture; rows outside the window; transpose not 0 or 1; unknown flags;
+ * one of nx, ny without the other, or neither with res != win; a workspace that is too small or not 16-byte aligned.
+ */
+#define F3R_GTVIEW_CAM_WORDS 25
+typedef enum { F3R_GTVIEW_POSE = 1, F3R_GTVIEW_FINITE_MASK = 2 } f3r_gtview_flags;
+size_t f3r_gtview_workspace_bytes(int n_views, int rows, int out_w);
+int f3r_gtview_resample(const int64_t* src_table, int n_views, int win_x, int win_y, int win_w, int win_h, const int32_t* bounds_h,
+                        const int32_t* kk_h, int ksize_h, int res_w, const int32_t* bounds_v, const int32_t* kk_v, int ksize_v, int res_h,
+                        int row0, int rows, int crop_x, int crop_y, int out_w, int out_h, int transpose, uint8_t* img_u8, float* img,
+                        void* workspace, size_t workspace_bytes, f3r_stream_t stream);
+int f3r_gtview_unproject(const int64_t* src_table, const float* cams, int n_views, int win_x, int win_y, int win_w, int win_h,
+                         const int32_t* nx, const int32_t* ny, int res_w, int res_h, int crop_x, int crop_y, int out_w, int out_h,
+                         int transpose, int flags, float* depthmap, float* pts3d, uint8_t* valid_mask, int32_t* flag, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
  * f3r_resample_u8 is ONE pass of PIL.Image.resize for 8-bit RGB (`_resize_pil_image`, :68-74; Pillow's Resample.c): axis 1 =
  * horizontal ([H][W][3] -> [H][out_size][3]), axis 0 = vertical ([H][W][3] -> [out_size][W][3]); bounds [out_size][2] = {first source
