@@ -34,6 +34,10 @@ MAPS_TILE = 1024  # F3R_MAPS_TILE: pixels per workgroup of the map-picture kerne
 F3R_MAPS_LUT, F3R_MAPS_RGB = 0, 1
 GTVIEW_CAM_WORDS = 25  # F3R_GTVIEW_CAM_WORDS: floats of a row of the ground-truth views' camera table (the 3 x 3 intrinsics, then the 4 x 4 pose)
 F3R_GTVIEW_POSE, F3R_GTVIEW_FINITE_MASK = 1, 2
+# F3R_DEPTH_TILE: pixels per workgroup of the depth metrics' error and compaction kernels; F3R_DEPTH_ROW_WORDS: words of a row of their table;
+# F3R_DEPTH_OUT_WORDS: fixed words of a result row (the curves follow); F3R_DEPTH_MAX_THRESHOLDS: inlier thresholds of one call
+DEPTH_TILE, DEPTH_ROW_WORDS, DEPTH_OUT_WORDS, DEPTH_MAX_THRESHOLDS = 1024, 8, 16, 4
+F3R_DEPTH_ALIGN_NONE, F3R_DEPTH_ALIGN_MEDIAN = 0, 1
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
 
@@ -202,6 +206,12 @@ SYMBOLS = {
     "f3r_gtview_resample": (ctypes.c_int, [_c_vp] + [ctypes.c_int] * 5 + [_c_vp, _c_vp, ctypes.c_int, ctypes.c_int, _c_vp, _c_vp] + [ctypes.c_int] * 9
                             + [_c_vp, _c_vp, _c_vp, ctypes.c_size_t, _c_vp]),
     "f3r_gtview_unproject": (ctypes.c_int, [_c_vp, _c_vp] + [ctypes.c_int] * 5 + [_c_vp, _c_vp] + [ctypes.c_int] * 8 + [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "f3r_depth_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, _c_i64, _c_i64, ctypes.c_int, ctypes.c_int]),
+    "f3r_depth_medians": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, ctypes.c_int, ctypes.c_int, _c_f32, _c_vp, _c_i64, _c_vp]),
+    "f3r_depth_errors": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                        ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_i64, _c_vp]),
+    "f3r_depth_sparsify": (ctypes.c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_int, _c_vp, ctypes.c_size_t, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp]),
 }
 
 # entry points added after ABI_VERSION: {symbol: the f3r_version() that first exports it}.  lib() binds one only when the loaded library
@@ -213,6 +223,7 @@ SYMBOL_SINCE_430 = {name: 430 for name in SYMBOLS if name.startswith("f3r_render
 SYMBOL_IF_PRESENT = frozenset(name for name in SYMBOLS if name.startswith("f3r_raster_"))
 SYMBOL_IF_PRESENT_MAPS = frozenset(name for name in SYMBOLS if name.startswith("f3r_maps_"))  # the map pictures, gated the same way
 SYMBOL_IF_PRESENT_VIEWS = frozenset(name for name in SYMBOLS if name.startswith("f3r_gtview_"))  # the ground-truth views, gated the same way
+SYMBOL_IF_PRESENT_DEPTH = frozenset(name for name in SYMBOLS if name.startswith("f3r_depth_"))  # the multi-view depth metrics, gated the same way
 
 
 def symbol_since(name: str) -> int:
@@ -221,8 +232,8 @@ def symbol_since(name: str) -> int:
 
 
 def if_present(name: str) -> bool:
-    """is `name` gated by presence: the one lookup of lib() and entry() over the three sets above"""
-    return name in SYMBOL_IF_PRESENT or name in SYMBOL_IF_PRESENT_MAPS or name in SYMBOL_IF_PRESENT_VIEWS
+    """is `name` gated by presence: the one lookup of lib() and entry() over the four sets above"""
+    return name in SYMBOL_IF_PRESENT or name in SYMBOL_IF_PRESENT_MAPS or name in SYMBOL_IF_PRESENT_VIEWS or name in SYMBOL_IF_PRESENT_DEPTH
 
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")

@@ -12,6 +12,7 @@
 // Integer atomics only (LDS histogram counters, the bounds keys): two runs give the same bits.  Built with -ffp-contract=off.
 #include "f3r_common.h"
 #include "f3r_post_common.h"
+#include "f3r_sort.h"  // the LSD passes of the voxel sort (SORT_TILE, sort_ws, sort_pairs_lsd), shared with f3r_depth.hip
 
 #include <algorithm>
 
@@ -19,12 +20,7 @@ namespace {
 
 constexpr int CLOUD_TILE = 1024;               // pixels of one combine workgroup (one wave, 16 steps of 64)
 constexpr int CLOUD_STEPS = CLOUD_TILE / 64;
-constexpr int SORT_TILE = 2048;                // keys of one sort workgroup
-constexpr int SORT_NT = 256;
-constexpr int SORT_WAVES = SORT_NT / 64;
-constexpr int SORT_SUB = SORT_TILE / SORT_WAVES;  // consecutive keys owned by one wave
-constexpr int SORT_PER = SORT_SUB / 64;
-constexpr int FPS_TILE = 1024;                 // points of one tile of the tiled path
+constexpr int FPS_TILE = 1024;               // points of one tile of the tiled path
 constexpr int FPS_NT = 256;
 constexpr int FPS_PER = FPS_TILE / FPS_NT;
 constexpr int FPS_MAX_GRID = 1024;             // workgroups (= partials) of one tiled launch at most
@@ -35,7 +31,6 @@ constexpr int BOUNDS_NT = 256;
 static_assert(CLOUD_TILE == F3R_CLOUD_TILE && SORT_TILE == F3R_CLOUD_SORT_TILE && FPS_TILE == F3R_CLOUD_FPS_TILE &&
                   FPS_ONE_MAX == F3R_CLOUD_FPS_ONE_MAX,
               "include/f3r.h states the tile lengths");
-static_assert(SORT_NT == 256, "one thread per digit");
 
 struct CloudRow {  // one row of the device table, 12 x 8 bytes: the mesh rows (f3r_mesh_threshold reads the same table)
   const float* conf;    // (H W) fp32, or null: no threshold test
@@ -158,78 +153,6 @@ __global__ __launch_bounds__(256) void voxel_key_kernel(const float* __restrict_
   const uint64_t ix = (uint64_t)(int64_t)fmax(fx, 0.0), iy = (uint64_t)(int64_t)fmax(fy, 0.0), iz = (uint64_t)(int64_t)fmax(fz, 0.0);
   keys[i] = (ix << sh_x) | (iy << sh_y) | iz;
   idx[i] = (uint32_t)i;
-}
-
-// hist[digit * n_tiles + tile] = keys of the tile with that digit: digit-major, so one flat scan gives every (digit, tile) its first slot
-__global__ __launch_bounds__(SORT_NT) void sort_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
-                                                            int64_t n_tiles) {
-  __shared__ uint32_t cnt[256];
-  cnt[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * SORT_TILE, end = min(base + (int64_t)SORT_TILE, n);
-  for (int64_t i = base + threadIdx.x; i < end; i += SORT_NT) atomicAdd(&cnt[(uint32_t)(keys[i] >> shift) & 255u], 1u);
-  __syncthreads();
-  hist[(int64_t)threadIdx.x * n_tiles + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// one stable pass (after the two-level scan of the histogram: rows of row_len words, then the rows' totals): wave w owns keys [sub, sub + SORT_SUB) of the tile and ranks them 64 at a time in lane order; a key's slot is the
-// scanned first slot of its (digit, tile), plus the same digit's keys in the waves before, plus its rank within its wave
-__global__ __launch_bounds__(SORT_NT) void sort_scatter_kernel(const uint64_t* __restrict__ kin, const uint32_t* __restrict__ vin, int64_t n,
-                                                               int shift, const uint32_t* __restrict__ hist, int64_t n_tiles,
-                                                               const uint32_t* __restrict__ row_base, int64_t row_len,
-                                                               uint64_t* __restrict__ kout, uint32_t* __restrict__ vout) {
-  __shared__ uint32_t cnt[SORT_WAVES][256];
-  __shared__ uint32_t gbase[256];
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int64_t base = (int64_t)blockIdx.x * SORT_TILE, end = min(base + (int64_t)SORT_TILE, n);
-#pragma unroll
-  for (int j = 0; j < SORT_WAVES; ++j) cnt[j][tid] = 0;
-  {  // the histogram was scanned in rows of row_len words: a word's slot is its place in its row plus the rows before
-    const int64_t h = (int64_t)tid * n_tiles + blockIdx.x;
-    gbase[tid] = hist[h] + row_base[h / row_len];
-  }
-  __syncthreads();
-  const int64_t sub = base + (int64_t)w * SORT_SUB;
-  uint64_t k[SORT_PER];
-  uint32_t v[SORT_PER], rk[SORT_PER];
-#pragma unroll
-  for (int s = 0; s < SORT_PER; ++s) {
-    const int64_t i = sub + s * 64 + lane;
-    const bool ok = i < end;
-    k[s] = ok ? kin[i] : 0ull;
-    v[s] = ok ? vin[i] : 0u;
-  }
-#pragma unroll
-  for (int s = 0; s < SORT_PER; ++s) {
-    const bool ok = sub + s * 64 + lane < end;
-    const uint32_t d = (uint32_t)(k[s] >> shift) & 255u;
-    const uint64_t peers = digit_peers(d, ok);
-    const uint32_t below = (uint32_t)__popcll(peers & lanes_below());
-    // cnt[w] is this wave's alone, and a wave's LDS accesses execute in program order: every lane has read before the leader writes
-    const uint32_t c = cnt[w][d];
-    if (ok && below == 0) cnt[w][d] = c + (uint32_t)__popcll(peers);
-    rk[s] = c + below;
-  }
-  __syncthreads();
-  {  // thread = digit: the waves' counts become exclusive prefixes over the waves
-    uint32_t run = gbase[tid];
-#pragma unroll
-    for (int j = 0; j < SORT_WAVES; ++j) {
-      const uint32_t c = cnt[j][tid];
-      cnt[j][tid] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < SORT_PER; ++s) {
-    if (sub + s * 64 + lane < end) {
-      const uint32_t d = (uint32_t)(k[s] >> shift) & 255u;
-      const uint32_t o = cnt[w][d] + rk[s];
-      kout[o] = k[s];
-      vout[o] = v[s];
-    }
-  }
 }
 
 // segment heads: key differs from its predecessor's.  cnt[tile] = heads of the tile (n_tiles + 1 words, the last zeroed)
@@ -434,27 +357,18 @@ __global__ void cloud_gather_kernel(const float* __restrict__ p, const uint8_t* 
 bool cloud_n_ok(int64_t n) { return n >= 1 && n < (1ll << 31); }
 
 struct VoxelWs {
-  uint64_t *keys_a, *keys_b;
-  uint32_t *idx_a, *idx_b, *hist, *row_tot, *hscan, *starts;
-  int64_t sort_tiles, head_tiles, hist_rows, hist_row_len;
+  SortWs sort;  // first: the sort's buffers (f3r_sort.h), in the order this workspace has always had them
+  uint32_t *idx_a, *hscan, *starts;
+  int64_t head_tiles;
   size_t bytes;
 };
 
 VoxelWs voxel_ws(void* base, int64_t n) {
   Carve c(base, 256);
   VoxelWs w = {};
-  w.sort_tiles = (n + SORT_TILE - 1) / SORT_TILE;
   w.head_tiles = (n + CLOUD_TILE - 1) / CLOUD_TILE;
-  w.keys_a = c.take<uint64_t>(n);
-  w.keys_b = c.take<uint64_t>(n);
-  w.idx_a = c.take<uint32_t>(n);
-  w.idx_b = c.take<uint32_t>(n);
-  // the digit-major histogram is scanned as hist_rows rows of hist_row_len words by as many workgroups, then the rows' totals by one
-  const int64_t words = w.sort_tiles * 256;
-  w.hist_row_len = std::max<int64_t>(SCAN_NT, (words + SCAN_NT - 1) / SCAN_NT);
-  w.hist_rows = (words + w.hist_row_len - 1) / w.hist_row_len;
-  w.hist = c.take<uint32_t>((size_t)(w.hist_rows * w.hist_row_len));
-  w.row_tot = c.take<uint32_t>(w.hist_rows);
+  w.sort = sort_ws(c, n);
+  w.idx_a = w.sort.idx_a;
   w.hscan = c.take<uint32_t>(w.head_tiles + 1);
   w.starts = c.take<uint32_t>(n + 1);
   w.bytes = c.bytes();
@@ -538,28 +452,15 @@ extern "C" int f3r_cloud_voxel_sort(const float* points, int64_t n, const double
   hipStream_t s = (hipStream_t)stream;
   const double half = 0.5 * voxel_size;
   hipLaunchKernelGGL(voxel_key_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, points, n, min_bound[0] - half, min_bound[1] - half,
-                     min_bound[2] - half, voxel_size, bits[1] + bits[2], bits[2], w.keys_a, w.idx_a);
-  uint64_t *kin = w.keys_a, *kout = w.keys_b;
-  uint32_t *vin = w.idx_a, *vout = w.idx_b;
-  const int passes = voxel_passes(bits);
-  for (int pass = 0; pass < passes; ++pass) {
-    const dim3 g((unsigned)w.sort_tiles), b(SORT_NT);
-    hipLaunchKernelGGL(sort_hist_kernel, g, b, 0, s, (const uint64_t*)kin, n, pass * 8, w.hist, w.sort_tiles);
-    // the words past the histogram in the last row hold anything: they follow every word that is read, and the last row's total is not used
-    hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3((unsigned)w.hist_rows), dim3(SCAN_NT), 0, s, w.hist, (const int64_t*)nullptr,
-                       w.hist_row_len, w.row_tot);
-    hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(1), dim3(SCAN_NT), 0, s, w.row_tot, (const int64_t*)nullptr, w.hist_rows,
-                       (uint32_t*)nullptr);
-    hipLaunchKernelGGL(sort_scatter_kernel, g, b, 0, s, (const uint64_t*)kin, (const uint32_t*)vin, n, pass * 8, (const uint32_t*)w.hist,
-                       w.sort_tiles, (const uint32_t*)w.row_tot, w.hist_row_len, kout, vout);
-    std::swap(kin, kout);
-    std::swap(vin, vout);
-  }
+                     min_bound[2] - half, voxel_size, bits[1] + bits[2], bits[2], w.sort.keys_a, w.sort.idx_a);
+  const uint64_t* kin;
+  const uint32_t* vin;
+  sort_pairs_lsd(w.sort, n, voxel_passes(bits), s, &kin, &vin);
   const dim3 gh((unsigned)w.head_tiles), bh(64);
-  hipLaunchKernelGGL(head_count_kernel, gh, bh, 0, s, (const uint64_t*)kin, n, w.hscan, w.head_tiles);
+  hipLaunchKernelGGL(head_count_kernel, gh, bh, 0, s, kin, n, w.hscan, w.head_tiles);
   hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(1), dim3(SCAN_NT), 0, s, w.hscan, (const int64_t*)nullptr, w.head_tiles + 1,
                      (uint32_t*)nullptr);
-  hipLaunchKernelGGL(head_starts_kernel, gh, bh, 0, s, (const uint64_t*)kin, n, (const uint32_t*)w.hscan, w.head_tiles, w.starts, n_voxels);
+  hipLaunchKernelGGL(head_starts_kernel, gh, bh, 0, s, kin, n, (const uint32_t*)w.hscan, w.head_tiles, w.starts, n_voxels);
   if (vin != w.idx_a)  // an odd number of passes left the order in the second buffer: the sums read the first
     if (hipMemcpyAsync(w.idx_a, vin, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess) {
       (void)hipGetLastError();

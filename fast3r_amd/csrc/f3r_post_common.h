@@ -1,4 +1,5 @@
-// The quantile solver shared by the post-processing kernels (f3r_post.hip: align / focal; f3r_recon.hip: evaluate_reconstruction): the
+// The quantile solver shared by the post-processing kernels (f3r_post.hip: align / focal; f3r_recon.hip: evaluate_reconstruction;
+// f3r_depth.hip: the confidence threshold and the masked medians of the depth metrics): the
 // exact torch.quantile of a block's values by radix select over the order-preserving 32-bit keys of f3r_prims.h.  The other solver they
 // share, the Umeyama similarity solve from fp64 raw moments (similarity_from_moments), is in f3r_linalg.h, which also builds for the host.
 // The wave and block primitives (keys, ballots, sums, the scan kernel) live in f3r_prims.h, which this header brings along.  Header-only
@@ -8,9 +9,10 @@
 #include "f3r_linalg.h"
 #include "f3r_prims.h"
 
-// k-th smallest key (0-based) of conf[0..n) by radix select over 11 + 11 + 10 bits; all NT threads return the same value.
-template <int NT>
-__device__ uint32_t select_kth(const float* __restrict__ conf, int64_t n, int64_t k, uint32_t* hist /*2048*/, int64_t* sh_i64 /*2*/) {
+// k-th smallest (0-based) of the keys key_of(0), .., key_of(n - 1) by radix select over 11 + 11 + 10 bits; all NT threads return the same
+// value.  A masked select gives the entries it leaves out the largest key and takes its ranks from the count of the others.
+template <int NT, class KeyOf>
+__device__ uint32_t select_kth_key(KeyOf key_of, int64_t n, int64_t k, uint32_t* hist /*2048*/, int64_t* sh_i64 /*2*/) {
   uint32_t prefix = 0, prefix_mask = 0;
   const int shifts[3] = {21, 10, 0};
   const int bits[3] = {11, 11, 10};
@@ -19,7 +21,7 @@ __device__ uint32_t select_kth(const float* __restrict__ conf, int64_t n, int64_
     for (int i = threadIdx.x; i < nb; i += NT) hist[i] = 0;
     __syncthreads();
     for (int64_t i = threadIdx.x; i < n; i += NT) {
-      const uint32_t key = fkey(conf[i]);
+      const uint32_t key = key_of(i);
       if ((key & prefix_mask) == prefix) atomicAdd(&hist[(key >> shifts[pass]) & (nb - 1)], 1u);
     }
     __syncthreads();
@@ -41,6 +43,12 @@ __device__ uint32_t select_kth(const float* __restrict__ conf, int64_t n, int64_
     __syncthreads();
   }
   return prefix;
+}
+
+// the same over the keys of conf[0..n)
+template <int NT>
+__device__ uint32_t select_kth(const float* __restrict__ conf, int64_t n, int64_t k, uint32_t* hist /*2048*/, int64_t* sh_i64 /*2*/) {
+  return select_kth_key<NT>([conf](int64_t i) { return fkey(conf[i]); }, n, k, hist, sh_i64);
 }
 
 // torch.quantile(conf[0..n), q) (linear): rank = q*(n-1) in fp32, at::lerp between the two order statistics.  Every thread

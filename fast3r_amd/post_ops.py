@@ -1009,3 +1009,106 @@ def gtview_unproject(depthmaps, cams, window, nearest, resized, crop, transpose=
                  ptr(pts), ptr(valid), ptr(flag), stream_ptr()), "f3r_gtview_unproject")
     del keep
     return depth, pts, None if valid is None else valid.view(torch.bool)
+
+
+# ------------------------------------------------------------------------------------------------------------------- multi-view depth metrics
+def depth_plan(gt, pred, conf=None, mask=None, *, n_bins=0):
+    """The table of the depth-metric entry points (include/f3r.h) and the result rows they fill.  Lists over segments of GPU tensors: gt fp32
+    of n elements; pred fp32 of n elements (a depth map) or of shape (..., 3) with 3 n elements (a pointmap: channel 2 is read in place);
+    conf fp32 of n elements or None; mask bool or uint8 of n elements or None (conf and mask may be None as a whole).  Nothing is stacked:
+    a tensor that is not contiguous is made so first.  n_bins > 0 leaves room for the curves.  -> dict(table, host, n_seg, n_tiles, total,
+    lengths, out fp64 (n_seg, 16 + 2 n_bins), keep)."""
+    S = len(gt)
+    conf = [None] * S if conf is None else conf
+    mask = [None] * S if mask is None else mask
+    if S < 1 or len(pred) != S or len(conf) != S or len(mask) != S:
+        raise ValueError("depth_plan: need one gt, pred, conf and mask entry per segment, and at least one segment")
+    dev, keep, rows, lengths, base = gt[0].device, [], [], [], 0
+    for s in range(S):
+        g, p, c, m = gt[s], pred[s], conf[s], mask[s]
+        for t in (g, p, c, m):
+            if t is not None:
+                require_gpu(t, f"segment {s}")
+                if t.device != dev:
+                    raise ValueError(f"depth_plan: segment {s}: every tensor must be on {dev}, got {t.device}")
+        n = g.numel()
+        if g.dtype != torch.float32 or p.dtype != torch.float32 or not 1 <= n < 2 ** 31:
+            raise ValueError(f"depth_plan: segment {s}: gt and pred must be fp32 with 1 <= n < 2^31 pixels, got {g.dtype}, {p.dtype}, n = {n}")
+        if p.numel() == n:
+            stride, chan = 1, 0
+        elif p.dim() >= 1 and p.shape[-1] == 3 and p.numel() == 3 * n:
+            stride, chan = 3, 2
+        else:
+            raise ValueError(f"depth_plan: segment {s}: pred {tuple(p.shape)} is neither a depth map nor a pointmap of gt's {n} pixels")
+        if c is not None and (c.dtype != torch.float32 or c.numel() != n):
+            raise ValueError(f"depth_plan: segment {s}: conf must be fp32 with {n} elements, got {tuple(c.shape)} {c.dtype}")
+        if m is not None:
+            if m.dtype not in (torch.bool, torch.uint8) or m.numel() != n:
+                raise ValueError(f"depth_plan: segment {s}: mask must be bool or uint8 with {n} elements, got {tuple(m.shape)} {m.dtype}")
+        g, p = g.contiguous(), p.contiguous()
+        c = None if c is None else c.contiguous()
+        m = None if m is None else m.contiguous()
+        keep += [g, p, c, m]
+        rows.append([g.data_ptr(), p.data_ptr(), stride, chan, 0 if c is None else c.data_ptr(), 0 if m is None else m.data_ptr(), n, base])
+        lengths.append(n)
+        base += n
+    starts = tile_starts(lengths, _lib.DEPTH_TILE)
+    words = table_words(rows, starts)
+    host = (ctypes.c_int64 * words.numel())(*words.tolist())
+    out = torch.empty((S, _lib.DEPTH_OUT_WORDS + 2 * int(n_bins)), dtype=torch.float64, device=dev)
+    return {"table": words.to(dev), "host": host, "n_seg": S, "n_tiles": starts[-1], "total": base, "lengths": lengths, "out": out, "keep": keep,
+            "n_bins": int(n_bins)}
+
+
+def _depth_clip(clip):
+    if clip is None:
+        return 0, 0.0, 0.0
+    lo, hi = (float(v) for v in clip)
+    return 1, lo, hi
+
+
+def depth_medians(plan, alignment=_lib.F3R_DEPTH_ALIGN_MEDIAN, q=None):
+    """f3r_depth_medians on a plan: n_valid, thr, both medians and the scale into columns 0 .. 4 of plan["out"].  q: None (no threshold)
+    or the quantile in [0, 1] of each segment's confidence below which a pixel is not valid."""
+    fn = _lib.entry("f3r_depth_medians")
+    out = plan["out"]
+    with torch.cuda.device(out.device):
+        check(fn(ptr(plan["table"]), plan["host"], plan["n_seg"], plan["n_tiles"], int(alignment), int(q is not None), 0.0 if q is None else float(q),
+                 ptr(out), out.shape[1], stream_ptr()), "f3r_depth_medians")
+    return out
+
+
+def depth_errors(plan, thresholds=(1.03,), clip=None, use_thr=False):
+    """f3r_depth_errors on a plan whose medians are taken: absrel, rmse, inlier percentages and counts into columns 5 .. 14 of plan["out"]."""
+    fn, size_fn = _lib.entry("f3r_depth_errors"), _lib.entry("f3r_depth_workspace_bytes")
+    out = plan["out"]
+    tt, n_t = _thresholds(thresholds)
+    on, lo, hi = _depth_clip(clip)
+    nbytes = size_fn(plan["n_seg"], plan["n_tiles"], plan["total"], 0, 0)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=out.device)
+    with torch.cuda.device(out.device):
+        check(fn(ptr(plan["table"]), plan["host"], plan["n_seg"], plan["n_tiles"], int(bool(use_thr)), on, lo, hi, tt, n_t, ptr(ws), nbytes, ptr(out),
+                 out.shape[1], stream_ptr()), "f3r_depth_errors")
+    del ws  # the launches are stream-ordered before the caching allocator can hand the block out again
+    return out
+
+
+def depth_sparsify(plan, clip=None, use_thr=False, return_order=False):
+    """f3r_depth_sparsify on a plan made with n_bins > 0 whose medians are taken: ause into column 15 of plan["out"], the sparsification and
+    the oracle curve into the 2 n_bins columns after it.  With return_order also (order_conf, order_err, starts): int32 device tensors of the
+    two orders as pixel indices inside their segments, segment s at [starts[s], starts[s + 1])."""
+    fn, size_fn = _lib.entry("f3r_depth_sparsify"), _lib.entry("f3r_depth_workspace_bytes")
+    out, K = plan["out"], plan["n_bins"]
+    on, lo, hi = _depth_clip(clip)
+    nbytes = size_fn(plan["n_seg"], plan["n_tiles"], plan["total"], 1, K)
+    if nbytes == 0:
+        raise ValueError(f"depth_sparsify: n_bins = {K} with {plan['total']} pixels is not a supported shape (1 <= n_bins <= 65536, fewer than 2^31 pixels)")
+    dev = out.device
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    orders = torch.empty((2, plan["total"]), dtype=torch.int32, device=dev)
+    starts = torch.empty(plan["n_seg"] + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(ptr(plan["table"]), plan["host"], plan["n_seg"], plan["n_tiles"], int(bool(use_thr)), on, lo, hi, K, ptr(ws), nbytes, ptr(orders[0]),
+                 ptr(orders[1]), ptr(starts), ptr(out), out.shape[1], stream_ptr()), "f3r_depth_sparsify")
+    del ws
+    return (out, orders[0], orders[1], starts) if return_order else out

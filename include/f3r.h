@@ -915,6 +915,55 @@ int f3r_gtview_unproject(const int64_t* src_table, const float* cams, int n_view
                          int transpose, int flags, float* depthmap, float* pts3d, uint8_t* valid_mask, int32_t* flag, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multi-view depth metrics: what the reference's scripts/robustmvd_eval.py obtains, per sample on the host, from an external benchmark
+ * library with alignment="median" -- absolute relative error, inlier ratios, sparsification curves and their area -- for every (view,
+ * sample) segment of a forward pass in one call, on the device.  That library is installed nowhere this project runs, so the definitions
+ * are this project's own (docs/rows_f.md states them in full; docs/parity.md says so).  Python: fast3r_amd/depth_metric.py.  Kernels:
+ * fast3r_amd/csrc/f3r_depth.hip.  f3r_version() is unchanged: a caller learns whether a library has these entry points by looking for them.
+ * table: device int64, n_seg rows of F3R_DEPTH_ROW_WORDS words = { ground-truth depth fp32 [n], prediction fp32, its stride in floats (1: a
+ *   depth map; 3: a pointmap read in place), its channel (0 with stride 1; 0 .. 2 with stride 3), confidence fp32 [n] or 0, mask bytes [n]
+ *   (nonzero = valid) or 0, n = H W, the sum of the n before }, then the n_seg + 1 running tile counts, ceil(n / F3R_DEPTH_TILE) each.
+ *   host_table: the same words on the host; every entry point checks them before it launches.  n_tiles: the last running count.
+ * A pixel is valid when g > 0, g and p are finite, its mask byte (if any) is nonzero and, with use_thr, conf >= thr (a NaN confidence
+ * fails), thr = torch.quantile(conf of the whole segment, q) by the rule of f3r_align_local_to_global.  All arithmetic is fp64 on the
+ * exactly widened fp32 values, every operation rounded.
+ * out: device fp64 [n_seg][out_ld], out_ld >= F3R_DEPTH_OUT_WORDS: { 0 n_valid, 1 thr (NaN without use_thr or confidence), 2 median of g,
+ *   3 median of p (numpy's: the mean of the two middle order statistics, which are found exactly), 4 scale, 5 absrel, 6 rmse, 7 .. 10 inlier
+ *   percentages, 11 .. 14 inlier counts, 15 ause }, then with curves n_bins words s_k and n_bins words o_k.
+ * f3r_depth_medians writes columns 0 .. 4: scale = 1 (F3R_DEPTH_ALIGN_NONE) or median g / median p, 1 where that is not finite; a
+ *   negative scale is kept.  With n_valid = 0 the medians and the scale are NaN.  One workgroup per segment.
+ * f3r_depth_errors reads columns 0 .. 4 and writes 5 .. 15: sp = scale p, clipped to [clip_lo, clip_hi] with clip; e = |sp - g| / g;
+ *   absrel = 100 sum e / n; rmse = sqrt(sum (sp - g)^2 / n); inlier t = 100 count(max(g / sp, sp / g) < t) / n, strictly; NaN with n = 0
+ *   and for thresholds not given; ause = NaN until f3r_depth_sparsify.  workspace: f3r_depth_workspace_bytes(.., 0, 0) bytes at least.
+ * f3r_depth_sparsify reads columns 0 .. 4 and writes ause and the curves: the valid pixels by ascending confidence key (ties in pixel
+ *   order; without a confidence: pixel order) and by descending e rounded to fp32 (ties in pixel order); for k < n_bins, with n k / n_bins
+ *   pixels (integer division) removed from the front, s_k and o_k are the means of e over the rest, each from the sums of the bins kept,
+ *   never from total - prefix; ause = sum_{k < K - 1} (d_k + d_{k+1}) / (2 K), d_k = (s_k - o_k) / s_0; 0 with s_0 = 0, NaN with n = 0.
+ *   order_conf, order_err: device uint32 [total pixels], the two orders as pixel indices inside their segments, segment after segment,
+ *   segment s at [starts[s], starts[s + 1]); starts: device uint32 [n_seg + 1].  workspace: f3r_depth_workspace_bytes(.., 1, n_bins).
+ * Launches and device-to-device copies only.  Sums are fixed-order partials added in slot order, without floating-point atomics: two runs
+ * give the same bits.  Inputs are not written to.
+ * Limits, F3R_ERR_ARG before any launch: a null table, host_table, out, workspace or order; n_seg outside [1, 2^24]; a row with a null
+ *   depth or prediction, a stride other than 1 or 3, a pointer that is not a multiple of 4 bytes, n < 1 or n >= 2^31, a base or tile
+ *   starts that do not follow from the sizes; more than F3R_DEPTH_MAX_THRESHOLDS thresholds; clip bounds that are no interval; n_bins
+ *   outside [1, 65536]; 2^31 pixels or more in all (sparsify); out_ld or workspace too small.  f3r_depth_workspace_bytes returns 0 for them.
+ */
+#define F3R_DEPTH_TILE 1024
+#define F3R_DEPTH_ROW_WORDS 8
+#define F3R_DEPTH_OUT_WORDS 16
+#define F3R_DEPTH_MAX_THRESHOLDS 4
+typedef enum { F3R_DEPTH_ALIGN_NONE = 0, F3R_DEPTH_ALIGN_MEDIAN = 1 } f3r_depth_alignment;
+size_t f3r_depth_workspace_bytes(int n_seg, int64_t n_tiles, int64_t total_pixels, int eval_uncertainty, int n_bins);
+int f3r_depth_medians(const int64_t* table, const int64_t* host_table, int n_seg, int64_t n_tiles, int alignment, int use_thr, float q,
+                      double* out, int64_t out_ld, f3r_stream_t stream);
+int f3r_depth_errors(const int64_t* table, const int64_t* host_table, int n_seg, int64_t n_tiles, int use_thr, int clip, double clip_lo,
+                     double clip_hi, const double* thresholds, int n_thresholds, void* workspace, size_t workspace_bytes, double* out,
+                     int64_t out_ld, f3r_stream_t stream);
+int f3r_depth_sparsify(const int64_t* table, const int64_t* host_table, int n_seg, int64_t n_tiles, int use_thr, int clip, double clip_lo,
+                       double clip_hi, int n_bins, void* workspace, size_t workspace_bytes, uint32_t* order_conf, uint32_t* order_err,
+                       uint32_t* starts, double* out, int64_t out_ld, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
  * f3r_resample_u8 is ONE pass of PIL.Image.resize for 8-bit RGB (`_resize_pil_image`, :68-74; Pillow's Resample.c): axis 1 =
  * horizontal ([H][W][3] -> [H][out_size][3]), axis 0 = vertical ([H][W][3] -> [out_size][W][3]); bounds [out_size][2] = {first source
