@@ -24,6 +24,7 @@ from .align import align_local_pts3d_to_global as _align
 from .focal import estimate_focal, estimate_focals  # noqa: F401  (module-level in the reference too, :1081)
 from .cam_pose_metric import camera_pose_metrics as _camera_pose_metrics
 from .depth_metric import evaluate_multiview_depth as _evaluate_multiview_depth
+from .matching import match_views as _match_views
 from .pose import estimate_camera_poses as _estimate_camera_poses
 from .pose import estimate_camera_poses_device as _estimate_camera_poses_device
 from .recon_metric import reconstruction_metrics as _reconstruction_metrics
@@ -188,3 +189,8 @@ class MultiViewDUSt3RLitModule(torch.nn.Module):
         for sample in _evaluate_multiview_depth(views, preds, **kw):
             self.depth_metrics_per_epoch.setdefault(dataset_name, {})[sample["scene"]] = sample
         return self.depth_metrics_per_epoch.get(dataset_name)
+
+    def match_views(self, views, preds, **kw):
+        """Reciprocal pointmap matches between view pairs of a forward pass (fast3r_amd/matching.py: the reference's find_reciprocal_matches
+        over the pairs of make_pairs, batched on the device) -> ViewMatches.  The keywords of `fast3r_amd.match_views` pass through."""
+        return _match_views(preds, views, **kw)

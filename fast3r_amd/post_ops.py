@@ -1,5 +1,5 @@
 """Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
-loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer, the map pictures and the ground-truth views.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer, the map pictures, the ground-truth views, the depth metrics and view matching.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
 out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
 """
 import ctypes
@@ -1112,3 +1112,112 @@ def depth_sparsify(plan, clip=None, use_thr=False, return_order=False):
                  ptr(orders[1]), ptr(starts), ptr(out), out.shape[1], stream_ptr()), "f3r_depth_sparsify")
     del ws
     return (out, orders[0], orders[1], starts) if return_order else out
+
+
+# ------------------------------------------------------------------------------------------------------------------- view matching
+def _host_i64(values):
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.int64).reshape(-1))
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _host_i32(values):
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.int32).reshape(-1))
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def _table(host, dev):
+    """the device copy of a host table (one word at least, so that an empty table still has an address)"""
+    return torch.from_numpy(host if host.size else np.zeros(1, host.dtype)).to(dev)
+
+
+def match_index_bytes(counts):
+    """bytes of the index f3r_match_index builds over views of `counts` candidates (0: not a supported shape).  Needs no GPU."""
+    seg, seg_p = _host_i64(np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]))
+    return int(_lib.entry("f3r_match_index_bytes")(seg_p, len(counts)))
+
+
+def match_index(points, counts):
+    """f3r_match_index: one exact nearest-neighbour index per view.  points: fp32 (total, 3) on the GPU, the candidates of the views one
+    after another; counts: candidates per view.  -> dict(index, seg, seg_host, n_views, counts, total).  Launches only."""
+    fn, size_fn, ws_fn = _lib.entry("f3r_match_index"), _lib.entry("f3r_match_index_bytes"), _lib.entry("f3r_match_workspace_bytes")
+    require_gpu(points, "points")
+    counts = [int(c) for c in counts]
+    V, total = len(counts), int(sum(counts))
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] != total or not points.is_contiguous():
+        raise ValueError(f"match_index: points must be contiguous fp32 ({total}, 3), got {tuple(points.shape)} {points.dtype}")
+    seg, seg_p = _host_i64(np.concatenate([[0], np.cumsum(np.asarray(counts, dtype=np.int64))]))
+    nbytes, wbytes = size_fn(seg_p, V), ws_fn(total, V)
+    if nbytes == 0 or wbytes == 0:
+        raise ValueError(f"match_index: {V} views with {total} candidates is not a supported shape (1 .. 65536 views, fewer than 2^31 candidates "
+                         "per view and 2^32 in all)")
+    dev = points.device
+    index = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    seg_dev = _table(seg, dev)
+    with torch.cuda.device(dev):
+        check(fn(ptr(points) if total else None, ptr(seg_dev), seg_p, V, ptr(index), nbytes, ptr(ws), wbytes, stream_ptr()), "f3r_match_index")
+    del ws  # the launches are stream-ordered before the caching allocator can hand the block out again
+    return {"index": index, "seg": seg_dev, "seg_host": (seg, seg_p), "n_views": V, "counts": counts, "total": total, "points": points}
+
+
+def match_search(ix, directed):
+    """f3r_match_search on an index: directed = rows (a, b).  -> dict(directed, qoff (device and host), nn_idx int32 [Q], nn_dist fp64 [Q]):
+    for candidate q of a, entry qoff[d] + q holds its nearest candidate of b (local to b) and the distance.  One launch."""
+    fn = _lib.entry("f3r_match_search")
+    dev, V = ix["index"].device, ix["n_views"]
+    dh, dh_p = _host_i32(directed)
+    D = dh.size // 2
+    if dh.size != 2 * D or (D and (dh.min() < 0 or dh.max() >= V)):
+        raise ValueError(f"match_search: directed pairs must be rows (a, b) of views 0 .. {V - 1}")
+    qoff, qoff_p = _host_i64(np.concatenate([[0], np.cumsum(np.asarray([ix["counts"][a] for a in dh[0::2]], dtype=np.int64))]))
+    Q = int(qoff[-1])
+    d_dev, q_dev = _table(dh, dev), _table(qoff, dev)
+    nn_idx = torch.empty(max(Q, 1), dtype=torch.int32, device=dev)
+    nn_dist = torch.empty(max(Q, 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(ptr(ix["index"]), ix["seg_host"][1], V, ptr(d_dev), dh_p, ptr(q_dev), qoff_p, D, ptr(nn_idx), ptr(nn_dist), stream_ptr()),
+              "f3r_match_search")
+    return {"directed": d_dev, "directed_host": (dh, dh_p), "qoff": q_dev, "qoff_host": (qoff, qoff_p), "n_directed": D, "n_queries": Q,
+            "nn_idx": nn_idx[:Q], "nn_dist": nn_dist[:Q]}
+
+
+def match_count(ix, found, pairs):
+    """f3r_match_count: pairs = rows (i, j, directed row of i -> j, directed row of j -> i) over the rows of `found` (match_search).
+    -> dict with offsets: device int64 [P + 2] = matches before each pair, the total, the index's flag word (views with a NaN / inf
+    coordinate).  Launches only: the caller reads offsets back once."""
+    fn = _lib.entry("f3r_match_count")
+    dev, V, D = ix["index"].device, ix["n_views"], found["n_directed"]
+    ph, ph_p = _host_i32(pairs)
+    P = ph.size // 4
+    if ph.size != 4 * P:
+        raise ValueError("match_count: pairs must be rows (i, j, forward, backward)")
+    tiles = [-(-ix["counts"][j] // _lib.MATCH_TILE) for j in ph[1::4]]
+    toff, toff_p = _host_i64(np.concatenate([[0], np.cumsum(np.asarray(tiles, dtype=np.int64))]))
+    p_dev, t_dev = _table(ph, dev), _table(toff, dev)
+    tile_counts = torch.empty(int(toff[-1]) + 1, dtype=torch.int32, device=dev)
+    offsets = torch.empty(P + 2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(ptr(ix["index"]), ptr(ix["seg"]), ix["seg_host"][1], V, ptr(p_dev), ph_p, ptr(t_dev), toff_p, P, ptr(found["qoff"]),
+                 found["qoff_host"][1], D, ptr(found["nn_idx"]) if found["n_queries"] else None, ptr(tile_counts), ptr(offsets), stream_ptr()),
+              "f3r_match_count")
+    return {"pairs": p_dev, "pairs_host": (ph, ph_p), "tile_off": t_dev, "tile_off_host": (toff, toff_p), "n_pairs": P, "tile_counts": tile_counts,
+            "offsets": offsets}
+
+
+def match_write(ix, found, counted, n_matches, pix, widths):
+    """f3r_match_write after match_count: pix int32 [total] = every candidate's row-major pixel index in its view, widths int32 [V].
+    -> (xy_i int32 [M, 2], xy_j int32 [M, 2], dist fp64 [M]) in pair order, ascending candidates of j inside a pair."""
+    fn = _lib.entry("f3r_match_write")
+    dev, V, M = ix["index"].device, ix["n_views"], int(n_matches)
+    if pix.dtype != torch.int32 or pix.numel() != ix["total"] or widths.dtype != torch.int32 or widths.numel() != V:
+        raise ValueError(f"match_write: pix must be int32 [{ix['total']}] and widths int32 [{V}]")
+    xy_i = torch.empty((M, 2), dtype=torch.int32, device=dev)
+    xy_j = torch.empty((M, 2), dtype=torch.int32, device=dev)
+    dist = torch.empty(M, dtype=torch.float64, device=dev)
+    if M:
+        with torch.cuda.device(dev):
+            check(fn(ptr(ix["seg"]), ix["seg_host"][1], V, ptr(counted["pairs"]), counted["pairs_host"][1], ptr(counted["tile_off"]),
+                     counted["tile_off_host"][1], counted["n_pairs"], ptr(found["qoff"]), found["qoff_host"][1], found["n_directed"],
+                     ptr(found["nn_idx"]), ptr(found["nn_dist"]), ptr(counted["tile_counts"]), ptr(pix.contiguous()), ptr(widths.contiguous()),
+                     ptr(xy_i), ptr(xy_j), ptr(dist), M, stream_ptr()), "f3r_match_write")
+    return xy_i, xy_j, dist

@@ -964,6 +964,48 @@ int f3r_depth_sparsify(const int64_t* table, const int64_t* host_table, int n_se
                        uint32_t* starts, double* out, int64_t out_ld, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * View matching: the reference's find_reciprocal_matches (fast3r/dust3r/utils/geometry.py:381-397: two cKDTrees, mutual nearest
+ * neighbours) over the view pairs of make_pairs (fast3r/dust3r/image_pairs.py:17-47), for all views and pairs of a scene at once.
+ * Python: fast3r_amd/matching.py.  Kernels: fast3r_amd/csrc/f3r_match.hip, on the search of f3r_nn_query (f3r_nn.h).  f3r_version() is
+ * unchanged: a caller learns whether a library has these entry points by looking for them.
+ * Candidates: pts fp32 [total][3], the candidates of view 0, 1, .. one after another; seg: device int64 [n_views + 1], view v at
+ *   [seg[v], seg[v + 1]).  Every table has a host copy (*_host) with the same words: the entry points check the host copies before they
+ *   launch, and the kernels guard every index they take from the device copies.
+ * f3r_match_index builds, in one call without a host round trip, one exact nearest-neighbour index per view in `index`
+ *   (f3r_match_index_bytes): a grid over the view's own bounding box, its cell from the view's extent and occupied-cell count (the rule of
+ *   f3r_nn_build, at most 4 m + 63 cells for m candidates), all points sorted once per round by (view, cell).  A view with a NaN or inf
+ *   coordinate is counted in the index's flag word; f3r_match_search then searches nothing and f3r_match_count reports the word.
+ * f3r_match_search: one launch over all directed pairs.  directed: int32 [n_directed][2] = (a, b); qoff: int64 [n_directed + 1], the running
+ *   sum of the candidates of a.  For candidate q of a (local index) nn_idx[qoff[d] + q] = its nearest candidate of b (local to b; exact by
+ *   the fp64 distance ((dx^2 + dy^2) + dz^2) of the fp32 coordinates, ties to the smaller index; 0 for an empty b) and nn_dist = the fp64
+ *   distance (inf for an empty b).
+ * f3r_match_count / f3r_match_write: pairs: int32 [n_pairs][4] = (i, j, the directed row of i -> j, the directed row of j -> i); tile_off:
+ *   int64 [n_pairs + 1], the running sum of ceil(candidates of j / F3R_MATCH_TILE).  Candidate q of j matches iff nn_ij[nn_ji[q]] == q.
+ *   _count writes tile_counts (uint32 [tiles + 1], scanned) and offsets: int64 [n_pairs + 2] = matches before each pair, the total, then the
+ *   flag word: the one read-back of a call.  _write fills xy_i, xy_j (int32 [n_matches][2] = (x, y) from pix, the candidate's row-major
+ *   pixel index, and widths[view]) and dist (fp64 [n_matches]) in pair order, inside a pair in ascending candidate order of j.
+ * Launches only; integer atomics for boxes and occupied cells only: two runs give the same bits.  Inputs are not written to.
+ * Limits, F3R_ERR_ARG before any launch: null or misaligned buffers (index and workspace: 256 bytes); n_views outside [1, 65536]; a
+ *   segment table that does not ascend from 0, 2^31 candidates in a view or 2^32 in all; pairs outside the views or the directed rows;
+ *   offsets that do not follow from the segments; 2^31 directed queries or 2^21 tiles or more in one call; index or workspace too small.  The *_bytes functions return 0 for them.
+ */
+#define F3R_MATCH_TILE 2048
+size_t f3r_match_index_bytes(const int64_t* seg_host, int n_views);
+size_t f3r_match_workspace_bytes(int64_t total, int n_views);
+int f3r_match_index(const float* pts, const int64_t* seg, const int64_t* seg_host, int n_views, void* index, size_t index_bytes,
+                    void* workspace, size_t workspace_bytes, f3r_stream_t stream);
+int f3r_match_search(const void* index, const int64_t* seg_host, int n_views, const int32_t* directed, const int32_t* directed_host,
+                     const int64_t* qoff, const int64_t* qoff_host, int n_directed, int32_t* nn_idx, double* nn_dist, f3r_stream_t stream);
+int f3r_match_count(const void* index, const int64_t* seg, const int64_t* seg_host, int n_views, const int32_t* pairs,
+                    const int32_t* pairs_host, const int64_t* tile_off, const int64_t* tile_off_host, int n_pairs, const int64_t* qoff,
+                    const int64_t* qoff_host, int n_directed, const int32_t* nn_idx, uint32_t* tile_counts, int64_t* offsets,
+                    f3r_stream_t stream);
+int f3r_match_write(const int64_t* seg, const int64_t* seg_host, int n_views, const int32_t* pairs, const int32_t* pairs_host,
+                    const int64_t* tile_off, const int64_t* tile_off_host, int n_pairs, const int64_t* qoff, const int64_t* qoff_host,
+                    int n_directed, const int32_t* nn_idx, const double* nn_dist, const uint32_t* tile_counts, const int32_t* pix,
+                    const int32_t* widths, int32_t* xy_i, int32_t* xy_j, double* dist, int64_t n_matches, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
  * f3r_resample_u8 is ONE pass of PIL.Image.resize for 8-bit RGB (`_resize_pil_image`, :68-74; Pillow's Resample.c): axis 1 =
  * horizontal ([H][W][3] -> [H][out_size][3]), axis 0 = vertical ([H][W][3] -> [out_size][W][3]); bounds [out_size][2] = {first source
