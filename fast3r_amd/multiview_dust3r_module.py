@@ -25,6 +25,7 @@ from .focal import estimate_focal, estimate_focals  # noqa: F401  (module-level 
 from .cam_pose_metric import camera_pose_metrics as _camera_pose_metrics
 from .depth_metric import evaluate_multiview_depth as _evaluate_multiview_depth
 from .matching import match_views as _match_views
+from .clean import clean_pointcloud as _clean_pointcloud
 from .pose import estimate_camera_poses as _estimate_camera_poses
 from .pose import estimate_camera_poses_device as _estimate_camera_poses_device
 from .recon_metric import reconstruction_metrics as _reconstruction_metrics
@@ -194,3 +195,9 @@ class MultiViewDUSt3RLitModule(torch.nn.Module):
         """Reciprocal pointmap matches between view pairs of a forward pass (fast3r_amd/matching.py: the reference's find_reciprocal_matches
         over the pairs of make_pairs, batched on the device) -> ViewMatches.  The keywords of `fast3r_amd.match_views` pass through."""
         return _match_views(preds, views, **kw)
+
+    @staticmethod
+    def clean_pointcloud(preds, views=None, **kw):
+        """The cross-view occlusion filter of the reference's BasePCOptimizer.clean_pointcloud (cloud_opt/base_opt.py:279-317) on a forward
+        pass (fast3r_amd/clean.py) -> CleanedCloud.  The keywords of `fast3r_amd.clean_pointcloud` pass through."""
+        return _clean_pointcloud(preds, views, **kw)

@@ -1,5 +1,5 @@
 """Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
-loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer, the map pictures, the ground-truth views, the depth metrics and view matching.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer, the map pictures, the ground-truth views, the depth metrics, view matching and confidence cleaning.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
 out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
 """
 import ctypes
@@ -1221,3 +1221,59 @@ def match_write(ix, found, counted, n_matches, pix, widths):
                      ptr(found["nn_idx"]), ptr(found["nn_dist"]), ptr(counted["tile_counts"]), ptr(pix.contiguous()), ptr(widths.contiguous()),
                      ptr(xy_i), ptr(xy_j), ptr(dist), M, stream_ptr()), "f3r_match_write")
     return xy_i, xy_j, dist
+
+
+# ------------------------------------------------------------------------------------------------------------------- confidence cleaning
+def clean_frame_id(frame):
+    if frame == "world":
+        return _lib.F3R_CLEAN_WORLD
+    if frame == "camera":
+        return _lib.F3R_CLEAN_CAMERA
+    raise ValueError(f"clean_confidence: frame must be 'world' or 'camera', got {frame!r}")
+
+
+def clean_table(shapes, starts):
+    """the host table of f3r_clean_confidence: rows (H, W, first element) of the views, then the starts of the neighbour lists"""
+    rows, off = [], 0
+    for H, W in shapes:
+        rows.append([int(H), int(W), off])
+        off += int(H) * int(W)
+    return table_words(rows, [int(s) for s in starts]), off
+
+
+def clean_confidence(pts, conf, depth, poses, intrinsics, shapes, starts, nbr, *, tol=0.001, max_bad_conf=0.0, frame="world"):
+    """f3r_clean_confidence (include/f3r.h): the views one after another in pts (total, 3), conf and depth (total,), all fp32 on the GPU; poses
+    (N, 4, 4) fp32 camera-to-world, intrinsics (N, 4) fp32 = fx, fy, cx, cy; shapes[i] = (H, W); starts (N + 1) and nbr: the neighbour lists
+    (ascending, without the view itself).  -> (out_conf fp32 (total,), n_lowered int64 numpy (N,)).  Inputs are not written to.  One
+    read-back: the counts and the flag word (ValueError on a pose without an inverse)."""
+    fn, size_fn = _lib.entry("f3r_clean_confidence"), _lib.entry("f3r_clean_workspace_bytes")
+    N = len(shapes)
+    table_t, total = clean_table(shapes, starts)
+    frame_id = clean_frame_id(frame)
+    f32 = torch.float32
+    for t, name, shape in ((pts, "pts", (total, 3)), (conf, "conf", (total,)), (depth, "depth", (total,)), (poses, "poses", (N, 4, 4)),
+                           (intrinsics, "intrinsics", (N, 4))):
+        require_gpu(t, name)
+        if t.dtype != f32 or tuple(t.shape) != shape or t.device != pts.device or not t.is_contiguous():
+            raise ValueError(f"clean_confidence: {name} must be contiguous fp32 {shape} on {pts.device}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    if len(starts) != N + 1:
+        raise ValueError(f"clean_confidence: {len(starts)} neighbour-list starts for {N} views")
+    dev = pts.device
+    table = table_t.numpy()
+    table_p = table.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+    nh, nh_p = _host_i32(nbr)
+    nbytes = size_fn(N)
+    if nbytes == 0:
+        raise ValueError(f"clean_confidence: {N} views is not a supported shape (at least one view)")
+    t_dev, n_dev = _table(table, dev), _table(nh, dev)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(total, dtype=f32, device=dev)
+    small = torch.empty(N + 1, dtype=torch.int32, device=dev)  # the counts, then the flag word: one read-back
+    with torch.cuda.device(dev):
+        check(fn(ptr(pts), ptr(conf), ptr(depth), ptr(poses), ptr(intrinsics), ptr(t_dev), table_p, N, ptr(n_dev), nh_p, nh.size, float(tol),
+                 float(max_bad_conf), frame_id, ptr(out), ptr(small), small.data_ptr() + 4 * N, ptr(ws), nbytes, stream_ptr()), "f3r_clean_confidence")
+        host = small.cpu().numpy()
+    del ws, t_dev, n_dev  # the launches are stream-ordered before the caching allocator can hand these blocks out again
+    if host[N] != 0:
+        raise ValueError("clean_confidence: a camera pose has no inverse (its 3 x 3 block is singular, NaN or inf)")
+    return out, host[:N].view(np.uint32).astype(np.int64)

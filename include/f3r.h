@@ -1006,6 +1006,37 @@ int f3r_match_write(const int64_t* seg, const int64_t* seg_host, int n_views, co
                     const int32_t* widths, int32_t* xy_i, int32_t* xy_j, double* dist, int64_t n_matches, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Cross-view occlusion filter: the reference's BasePCOptimizer.clean_pointcloud (fast3r/dust3r/cloud_opt/base_opt.py:279-317).  Every point
+ * of view i is projected into the camera of each neighbour j; one that lies in front of camera j's depth map and is less confident than
+ * the pixel it lands on has its confidence clipped to max_bad_conf.  Python: fast3r_amd/clean.py.  Kernels: fast3r_amd/csrc/f3r_clean.hip.
+ * The library version is unchanged: a caller learns whether a library has these entry points by looking for them.
+ * Views lie one after another: pts fp32 [total][3], conf, depth, out_conf fp32 [total]; poses fp32 [n_views][4][4] camera-to-world (the
+ *   affine part is used); intrinsics fp32 [n_views][4] = fx, fy, cx, cy.  table: int64 [n_views][3] = H, W, first element of the view, then
+ *   int64 [n_views + 1] = the starts of the neighbour lists in nbr (int32 [n_nbr], ascending inside a list, never the view itself).  table
+ *   and nbr have host copies with the same words: they are checked before anything is launched, and the kernel guards what it takes from
+ *   the device copies.
+ * One small launch copies conf to out_conf, zeroes n_lowered and writes the view table into the workspace: the fp64 cofactor inverse of the
+ *   pose's 3 x 3 block and -A^-1 t, rounded to fp32; a determinant that is 0 or not finite sets bit 0 of *flag (then nothing is tested:
+ *   the caller reads the word and raises).  Then one launch per view i with a neighbour, in ascending order: one thread per pixel,
+ *     frame F3R_CLEAN_CAMERA only: p = ((r00 x + r01 y) + r02 z) + t0, .. with the pose of view i, in fp32
+ *     X = ((m00 x + m01 y) + m02 z) + m03, Y, Z likewise;  u = (fx X + cx Z) / Z;  v = (fy Y + cy Z) / Z;  ur = rint(u), vr = rint(v)
+ *     in cone: Z > 0, 0 <= ur < W_j, 0 <= vr < H_j, on the rounded floats (NaN fails)
+ *     bad: in cone and Z < (float)(1 - tol) * depth_j[vr][ur] and conf_i[p] < out_conf_j[vr][ur]
+ *   every operation rounded on its own.  A pixel with a bad neighbour gets out_conf = fminf(conf, max_bad_conf); n_lowered[i] counts those
+ *   whose value changed.  View i reads the working copy: cleaned already for j < i, the input for j > i, as the reference's loop does.
+ * Inputs are not written to.  F3R_ERR_ARG before any launch: null or misaligned buffers (workspace: 256 bytes); n_views < 1; a view
+ *   with a side outside [1, 2^24] or more than 2^31 - 1 pixels; offsets that are not the running sum of the shapes; neighbour lists that do not
+ *   start at 0, end at n_nbr and ascend, or name a view outside the views or the view itself; tol outside [0, 1) or NaN; NaN max_bad_conf; an
+ *   unknown frame; a workspace that is too small.  The sizing function returns 0 for n_views < 1.
+ */
+typedef enum { F3R_CLEAN_WORLD = 0, F3R_CLEAN_CAMERA = 1 } f3r_clean_frame;
+size_t f3r_clean_workspace_bytes(int n_views);
+int f3r_clean_confidence(const float* pts, const float* conf, const float* depth, const float* poses, const float* intrinsics,
+                         const int64_t* table, const int64_t* table_host, int n_views, const int32_t* nbr, const int32_t* nbr_host,
+                         int64_t n_nbr, double tol, float max_bad_conf, int frame, float* out_conf, uint32_t* n_lowered, uint32_t* flag,
+                         void* workspace, size_t workspace_bytes, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
  * f3r_resample_u8 is ONE pass of PIL.Image.resize for 8-bit RGB (`_resize_pil_image`, :68-74; Pillow's Resample.c): axis 1 =
  * horizontal ([H][W][3] -> [H][out_size][3]), axis 0 = vertical ([H][W][3] -> [out_size][W][3]); bounds [out_size][2] = {first source
