@@ -12,6 +12,8 @@ from .cam_pose_metric import calculate_auc, camera_pose_metrics, camera_to_rel_d
 from .depth_metric import depth_metrics, evaluate_multiview_depth  # noqa: F401
 from .matching import ViewMatches, find_reciprocal_matches, match_views, scene_graph_pairs  # noqa: F401
 from .clean import CleanedCloud, clean_confidences, clean_pointcloud  # noqa: F401
+from .global_align import (GlobalAlignerMode, Observations, PointCloudOptimizer, alignment_loss, global_aligner,  # noqa: F401
+                           pairs_from_passes)
 from .losses import ConfLossMultiviewV2, L21, L21Loss, Regr3DMultiviewV3, Regr3DMultiviewV4  # noqa: F401
 from .scene import Scene, assemble_scene, generate_ply_bytes, save_ply  # noqa: F401
 from .mesh import Mesh, build_mesh, cat_meshes, generate_mesh_ply_bytes, pts3d_to_trimesh, save_mesh_ply  # noqa: F401

@@ -40,6 +40,7 @@ DEPTH_TILE, DEPTH_ROW_WORDS, DEPTH_OUT_WORDS, DEPTH_MAX_THRESHOLDS = 1024, 8, 16
 F3R_DEPTH_ALIGN_NONE, F3R_DEPTH_ALIGN_MEDIAN = 0, 1
 MATCH_TILE = 2048  # F3R_MATCH_TILE: candidates of a pair's second view per workgroup of the reciprocity kernels
 F3R_CLEAN_WORLD, F3R_CLEAN_CAMERA = 0, 1  # f3r_clean_frame: the frame of the points handed to f3r_clean_confidence
+F3R_GALIGN_L1, F3R_GALIGN_L2 = 0, 1  # f3r_galign_dist: the distance of f3r_galign_loss_grad
 
 _c_i64, _c_i32, _c_f32, _c_vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
 
@@ -228,6 +229,10 @@ SYMBOLS = {
     "f3r_clean_confidence": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.POINTER(_c_i64), ctypes.c_int, _c_vp,
                                             ctypes.POINTER(_c_i32), _c_i64, ctypes.c_double, _c_f32, ctypes.c_int, _c_vp, _c_vp, _c_vp, _c_vp,
                                             ctypes.c_size_t, _c_vp]),
+    "f3r_galign_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "f3r_galign_loss_grad": (ctypes.c_int, [_c_vp] * 7 + [ctypes.POINTER(_c_i64), ctypes.c_int, _c_vp, ctypes.POINTER(_c_i32), ctypes.c_int, _c_vp,
+                                            ctypes.POINTER(_c_i64), _c_vp, ctypes.POINTER(_c_i32), ctypes.c_int] + [_c_vp] * 8
+                             + [ctypes.c_size_t, _c_vp]),
 }
 
 # entry points added after ABI_VERSION: {symbol: the f3r_version() that first exports it}.  lib() binds one only when the loaded library
@@ -242,6 +247,7 @@ SYMBOL_IF_PRESENT_VIEWS = frozenset(name for name in SYMBOLS if name.startswith(
 SYMBOL_IF_PRESENT_DEPTH = frozenset(name for name in SYMBOLS if name.startswith("f3r_depth_"))  # the multi-view depth metrics, gated the same way
 SYMBOL_IF_PRESENT_MATCH = frozenset(name for name in SYMBOLS if name.startswith("f3r_match_"))  # view matching, gated the same way
 SYMBOL_IF_PRESENT_CLEAN = frozenset(name for name in SYMBOLS if name.startswith("f3r_clean_"))  # confidence cleaning, gated the same way
+SYMBOL_IF_PRESENT_GALIGN = frozenset(name for name in SYMBOLS if name.startswith("f3r_galign_"))  # global alignment, gated the same way
 
 
 def symbol_since(name: str) -> int:
@@ -250,9 +256,9 @@ def symbol_since(name: str) -> int:
 
 
 def if_present(name: str) -> bool:
-    """is `name` gated by presence: the one lookup of lib() and entry() over the six sets above"""
+    """is `name` gated by presence: the one lookup of lib() and entry() over the seven sets above"""
     return (name in SYMBOL_IF_PRESENT or name in SYMBOL_IF_PRESENT_MAPS or name in SYMBOL_IF_PRESENT_VIEWS or name in SYMBOL_IF_PRESENT_DEPTH
-            or name in SYMBOL_IF_PRESENT_MATCH or name in SYMBOL_IF_PRESENT_CLEAN)
+            or name in SYMBOL_IF_PRESENT_MATCH or name in SYMBOL_IF_PRESENT_CLEAN or name in SYMBOL_IF_PRESENT_GALIGN)
 
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libf3r_hip.so")

@@ -26,6 +26,7 @@ from .cam_pose_metric import camera_pose_metrics as _camera_pose_metrics
 from .depth_metric import evaluate_multiview_depth as _evaluate_multiview_depth
 from .matching import match_views as _match_views
 from .clean import clean_pointcloud as _clean_pointcloud
+from .global_align import global_aligner as _global_aligner
 from .pose import estimate_camera_poses as _estimate_camera_poses
 from .pose import estimate_camera_poses_device as _estimate_camera_poses_device
 from .recon_metric import reconstruction_metrics as _reconstruction_metrics
@@ -201,3 +202,9 @@ class MultiViewDUSt3RLitModule(torch.nn.Module):
         """The cross-view occlusion filter of the reference's BasePCOptimizer.clean_pointcloud (cloud_opt/base_opt.py:279-317) on a forward
         pass (fast3r_amd/clean.py) -> CleanedCloud.  The keywords of `fast3r_amd.clean_pointcloud` pass through."""
         return _clean_pointcloud(preds, views, **kw)
+
+    @staticmethod
+    def global_aligner(dust3r_output, device, **kw):
+        """The reference's cloud_opt.global_aligner (fast3r_amd/global_align.py): pairwise observations -> a PointCloudOptimizer on `device`
+        whose compute_global_alignment fuses them into one set of poses, focals and depth maps.  The keywords pass through."""
+        return _global_aligner(dust3r_output, device, **kw)

@@ -1,5 +1,5 @@
 """Tensor-level wrappers over the C ABI (include/f3r.h) for what runs after the forward pass: the camera-pose metrics, the multi-view
-loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer, the map pictures, the ground-truth views, the depth metrics, view matching and confidence cleaning.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
+loss, scene assembly, sky detection, mesh export, point-cloud export, the point-splat renderer, the map pictures, the ground-truth views, the depth metrics, view matching, confidence cleaning and global alignment.  Like fast3r_amd/ops.py (the model's operators), these only check arguments, lay
 out the per-view device tables and launch: every arithmetic op is a HIP kernel in fast3r_amd/csrc/, and CPU tensors raise F3RError.
 """
 import ctypes
@@ -1277,3 +1277,69 @@ def clean_confidence(pts, conf, depth, poses, intrinsics, shapes, starts, nbr, *
     if host[N] != 0:
         raise ValueError("clean_confidence: a camera pose has no inverse (its 3 x 3 block is singular, NaN or inf)")
     return out, host[:N].view(np.uint32).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------------------------- global alignment
+def galign_dist_id(dist):
+    if dist == "l1":
+        return _lib.F3R_GALIGN_L1
+    if dist == "l2":
+        return _lib.F3R_GALIGN_L2
+    raise ValueError(f"alignment_loss: dist must be 'l1' or 'l2', got {dist!r}")
+
+
+def galign_tables(shapes, edges, maps, device=None):
+    """The tables of f3r_galign_loss_grad, built once per problem.  shapes[v] = (H, W); edges: rows (i, j); maps[2 e + side] = (pointmap,
+    weight map, H, W): contiguous fp32 device tensors (H, W, 3) and (H, W), or (address, address, H, W) when device is None (host checks
+    only).  Edges may share a map: only its address is stored.  -> dict with the host arrays (kept alive for the calls), their device copies
+    and the maps themselves."""
+    N, E = len(shapes), len(edges)
+    rows, off = [], 0
+    for H, W in shapes:
+        rows.append([int(H), int(W), off])
+        off += int(H) * int(W)
+    eh, eh_p = _host_i32([x for e in edges for x in e])
+    lists = [[] for _ in range(N)]
+    for o, v in enumerate(eh.tolist()):
+        if 0 <= v < N:  # an edge outside the views is refused by the entry point, which reads these host copies
+            lists[v].append(o)
+    starts = [0]
+    for ls in lists:
+        starts.append(starts[-1] + len(ls))
+    vt, vt_p = _host_i64([x for r in rows for x in r] + starts)
+    ol, ol_p = _host_i32([o for ls in lists for o in ls])
+    addr = lambda t: t.data_ptr() if torch.is_tensor(t) else int(t)  # noqa: E731
+    ot, ot_p = _host_i64([x for (p, w, H, W) in maps for x in (addr(p), addr(w), int(H), int(W))])
+    tb = {"n_views": N, "n_edges": E, "total": off, "shapes": [(int(H), int(W)) for H, W in shapes], "maps": maps,
+          "view_table_host": (vt, vt_p), "edges_host": (eh, eh_p), "obs_table_host": (ot, ot_p), "obs_list_host": (ol, ol_p), "device": device}
+    if device is not None:
+        tb.update(view_table=_table(vt, device), edges=_table(eh, device), obs_table=_table(ot, device), obs_list=_table(ol, device))
+    return tb
+
+
+def galign_loss_grad(poses, focals, pp, log_depth, pw_poses, adaptors, tables, dist="l1"):
+    """f3r_galign_loss_grad (include/f3r.h): poses (N, 3, 4), focals (N,), pp (N, 2), log_depth (total,), pw_poses (E, 3, 4), adaptors (E, 3),
+    contiguous fp32 on the device of the tables (galign_tables).  -> (loss: 0-dim fp64, d_log_depth, d_poses, d_focals, d_pp, d_pw_poses,
+    d_adaptors: fp32 shaped like the inputs), all on the device.  Launches only: nothing is read back.  Inputs are not written to."""
+    fn, size_fn = _lib.entry("f3r_galign_loss_grad"), _lib.entry("f3r_galign_workspace_bytes")
+    N, E, total, dev = tables["n_views"], tables["n_edges"], tables["total"], tables["device"]
+    dist_id = galign_dist_id(dist)
+    f32 = torch.float32
+    for t, name, shape in ((poses, "poses", (N, 3, 4)), (focals, "focals", (N,)), (pp, "pp", (N, 2)), (log_depth, "log_depth", (total,)),
+                           (pw_poses, "pw_poses", (E, 3, 4)), (adaptors, "adaptors", (E, 3))):
+        require_gpu(t, name)
+        if t.dtype != f32 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"galign_loss_grad: {name} must be contiguous fp32 {shape} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    nbytes = size_fn(N, E)
+    if nbytes == 0:
+        raise ValueError(f"galign_loss_grad: {N} views with {E} edges is not a supported shape (2 .. 65535 views, at least one edge)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float64, device=dev)
+    outs = [torch.empty_like(t) for t in (log_depth, poses, focals, pp, pw_poses, adaptors)]
+    with torch.cuda.device(dev):
+        check(fn(ptr(poses), ptr(focals), ptr(pp), ptr(log_depth), ptr(pw_poses), ptr(adaptors), ptr(tables["view_table"]),
+                 tables["view_table_host"][1], N, ptr(tables["edges"]), tables["edges_host"][1], E, ptr(tables["obs_table"]),
+                 tables["obs_table_host"][1], ptr(tables["obs_list"]), tables["obs_list_host"][1], dist_id, ptr(loss), *[ptr(t) for t in outs],
+                 ptr(ws), nbytes, stream_ptr()), "f3r_galign_loss_grad")
+    del ws  # the launches are stream-ordered before the caching allocator can hand the block out again
+    return (loss, *outs)

@@ -1037,6 +1037,40 @@ int f3r_clean_confidence(const float* pts, const float* conf, const float* depth
                          void* workspace, size_t workspace_bytes, f3r_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Global alignment: the loss of the reference's PointCloudOptimizer.forward (fast3r/dust3r/cloud_opt/optimizer.py:219-266, l1_dist /
+ * l2_dist of commons.py) and every gradient it has, at the level of matrices, in one evaluation.  Python: fast3r_amd/global_align.py.
+ * Kernels: fast3r_amd/csrc/f3r_galign.hip.  The library version is unchanged: a caller learns whether a library has these entry points by
+ * looking for them.  All inputs fp32 on the device:
+ *   poses [n_views][3][4] = [R | t] camera-to-world; focals [n_views]; pp [n_views][2] = cx, cy; log_depth [total], the views one after
+ *   another; pw_poses [n_edges][3][4] = [S | m], the top of the scaled pairwise pose; adaptors [n_edges][3].
+ *   view_table: int64 [n_views][3] = H, W, first element of the view in log_depth, then the n_views + 1 starts of the observation lists.
+ *   edges: int32 [n_edges][2] = (i, j).  Observation o = 2 e + side belongs to view i_e (side 0) or j_e (side 1).
+ *   obs_table: int64 [2 n_edges][4] = { pointmap fp32 [H][W][3], weight map fp32 [H][W], H, W }: pointers, so that edges may share a map.
+ *   obs_list: int32 [2 n_edges], the observations by view, ascending inside a view (the CSR the starts index).
+ *   *_host: the same words on the host, checked before the first launch.
+ * With (x, y) = (column, row) of pixel p of view v, for every observation o of v:
+ *   d = exp(l_v[p]);  q = (d (x - cx) / f, d (y - cy) / f, d);  X = R q + t;  A = S (a * P_o[p]) + m;  r = X - A
+ *   cost = w_o[p] |r| (F3R_GALIGN_L1) or w_o[p] |r|^2 (F3R_GALIGN_L2);  loss = sum_o k_o sum_p cost,  k_o = 1 / sum_e H W of that side
+ *   g = k_o w_o[p] r / |r| (exactly 0 where r = 0) or 2 k_o w_o[p] r; a weight of exactly 0 contributes exactly nothing
+ * Outputs: loss (one double); d_log_depth fp32 [total]; d_poses fp32 [n_views][3][4]; d_focals [n_views]; d_pp [n_views][2]; d_pw_poses
+ *   [n_edges][3][4]; d_adaptors [n_edges][3].  fp64 arithmetic on the widened inputs, fp64 sums in a fixed order, no atomics: two runs give
+ *   the same bits.  Inputs are not written to.  Launches only.
+ * F3R_ERR_ARG before any launch: null or misaligned buffers (workspace: 256 bytes); fewer than 2 views or more than 65535; no edge; a
+ *   view with more than 2^31 - 1 pixels; offsets that are not the running sum of the shapes; an edge outside the views or with i == j; a null
+ *   or misaligned map pointer; an observation whose shape is not its view's; lists that do not hold every observation once under its own
+ *   view, ascending; an unknown dist; a workspace that is too small.  The workspace bound does not depend on the image sizes; the sizing
+ *   function returns 0 for an unsupported shape.
+ */
+typedef enum { F3R_GALIGN_L1 = 0, F3R_GALIGN_L2 = 1 } f3r_galign_dist;
+size_t f3r_galign_workspace_bytes(int n_views, int n_edges);
+int f3r_galign_loss_grad(const float* poses, const float* focals, const float* pp, const float* log_depth, const float* pw_poses,
+                         const float* adaptors, const int64_t* view_table, const int64_t* view_table_host, int n_views,
+                         const int32_t* edges, const int32_t* edges_host, int n_edges, const int64_t* obs_table,
+                         const int64_t* obs_table_host, const int32_t* obs_list, const int32_t* obs_list_host, int dist, double* loss,
+                         float* d_log_depth, float* d_poses, float* d_focals, float* d_pp, float* d_pw_poses, float* d_adaptors,
+                         void* workspace, size_t workspace_bytes, f3r_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * f3r_resample_u8 / f3r_imgnorm_u8: the device side of the input pipeline `load_images` (fast3r/dust3r/utils/image.py:76-159).
  * f3r_resample_u8 is ONE pass of PIL.Image.resize for 8-bit RGB (`_resize_pil_image`, :68-74; Pillow's Resample.c): axis 1 =
  * horizontal ([H][W][3] -> [H][out_size][3]), axis 0 = vertical ([H][W][3] -> [out_size][W][3]); bounds [out_size][2] = {first source
