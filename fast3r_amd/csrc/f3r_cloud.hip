@@ -357,7 +357,7 @@ __global__ void cloud_gather_kernel(const float* __restrict__ p, const uint8_t* 
 bool cloud_n_ok(int64_t n) { return n >= 1 && n < (1ll << 31); }
 
 struct VoxelWs {
-  SortWs sort;  // first: the sort's buffers (f3r_sort.h), in the order this workspace has always had them
+  SortWs<> sort;  // first: the sort's buffers (f3r_sort.h), in the order this workspace has always had them
   uint32_t *idx_a, *hscan, *starts;
   int64_t head_tiles;
   size_t bytes;

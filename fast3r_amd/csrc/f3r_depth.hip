@@ -354,7 +354,7 @@ __global__ __launch_bounds__(64) void depth_curve_kernel(Params P, const uint32_
 struct DepthWs {
   double *part, *err, *bins;
   uint32_t* scan;
-  SortWs sort;
+  SortWs<> sort;
   size_t bytes;
 };
 

@@ -5,8 +5,9 @@
 //     records {x, y, z, candidate index local to v} in cell order, a dense cell-start table) in its own slice of one buffer, so grid_search
 //     and its lower bound serve unchanged.  The grid of a view spans the box of its own points (no point is clamped into a cell it does not
 //     lie in, so the bound holds for far outliers too: they only stretch the cells); its cell comes from the view's own extent and
-//     occupancy, 16 points per cell and one refinement from the occupied-cell count, one thread per view.  A view's grid holds at most
-//     4 m + 63 cells (a larger cell where that binds: slower, never inexact), so the key width and every slice are known to the host;
+//     occupancy by the sizing rules of f3r_nn.h (16 points per cell and one refinement from the occupied-cell count), one thread per
+//     view.  A view's grid holds at most 4 m + 63 cells (a larger cell where that binds: slower, never inexact), so the key width and
+//     every slice are known to the host;
 //   * all points are sorted once per round by (view, cell) keys with sort_pairs_lsd (f3r_sort.h);
 //   * the search: thread t of directed pair (a -> b) takes record t of a (a's own cell order: neighbouring lanes walk neighbouring cells)
 //     and writes the nearest candidate of b (int32, local to b) and the fp64 distance at the query's own candidate index;
@@ -21,7 +22,7 @@
 
 #include "f3r_prims.h"
 #include "f3r_sort.h"
-#include "f3r_nn.h"
+#include "f3r_nn.h"  // the index layout, the sizing rules (set_grid, key_bits_of, ...), grid_search, Best1 (shared with f3r_recon.hip)
 
 // build.sh compiles this file with -ffp-contract=off, like f3r_recon.hip: dist2 rounds every product and sum on its own, as cKDTree does.
 
@@ -36,11 +37,6 @@ struct ViewWs {  // per view: order-preserving keys of the box ends, then the oc
   uint32_t mn[3], mx[3], occ, pad;
 };
 
-inline int key_bits_of(int64_t n) {  // bits that hold 0 .. n - 1
-  int b = 0;
-  while (b < 62 && ((int64_t)1 << b) < n) ++b;
-  return b;
-}
 inline int64_t blob_units(int64_t m) { return (2 * HDR_BYTES + 36 * m + 255) / 256; }  // header, 16 m records, 4 m unused, 16 m + 256 table
 inline size_t units_bytes(int V) { return align256(4 * ((size_t)V + 1)); }
 
@@ -100,38 +96,9 @@ __global__ __launch_bounds__(256) void mv_bbox_kernel(const float* __restrict__ 
   }
 }
 
-// grid of cell h over the (finite) box [lo, hi]: at most MAX_DIM cells per axis and cap cells in all (set_grid of f3r_recon.hip, on the device)
-__device__ void set_grid_dev(Grid& g, const double lo[3], const double hi[3], double h, int64_t cap) {
-  double ext = 0.0;
-  for (int a = 0; a < 3; ++a) ext = fmax(ext, hi[a] - lo[a]);
-  if (!(ext > 0.0)) h = 1.0;
-  else if (!(h >= ext / (MAX_DIM - 0.5))) h = ext / (MAX_DIM - 0.5);  // also a NaN / zero h
-  for (int it = 0;; ++it) {
-    g.h = h;
-    g.inv_h = 1.0 / h;
-    g.ncells = 1;
-    for (int a = 0; a < 3; ++a) {
-      g.lo[a] = lo[a];
-      g.hi[a] = hi[a];
-      g.dims[a] = (int)fmin(fmax(floor((hi[a] - lo[a]) * g.inv_h) + 1.0, 1.0), (double)MAX_DIM);
-      g.ncells *= g.dims[a];
-    }
-    if (g.ncells <= cap) break;
-    // too many cells for the view's table: a larger cell (h > ext gives one cell, so this ends; the bound of grid_search holds for any h)
-    h = it < 200 ? h * fmax(cbrt((double)g.ncells / (double)cap), 1.0) * 1.1 : 2.0 * ext;
-  }
-  g.base = 0;
-}
-
-__device__ double box_volume_dev(const double lo[3], const double hi[3]) {
-  double ext = 0.0, vol = 1.0;
-  for (int a = 0; a < 3; ++a) ext = fmax(ext, hi[a] - lo[a]);
-  for (int a = 0; a < 3; ++a) vol *= fmax(hi[a] - lo[a], 1e-3 * ext);
-  return vol;
-}
-
 // ---- one thread per view.  round 0: the box, 16 points per cell if the cloud filled it.  round 1: one refinement from the occupied-cell
-//      count of the first sort unless that lands within 8 .. 32 points per cell already (the rule of f3r_nn_build).
+//      count of the first sort unless that lands within 8 .. 32 points per cell already: the sizing rules of f3r_nn.h, which f3r_nn_build
+//      evaluates on the host.
 __global__ void mv_grid_kernel(const int64_t* __restrict__ seg, int V, ViewWs* __restrict__ vw, uint8_t* __restrict__ index, int round,
                                uint32_t* __restrict__ flag) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -156,7 +123,7 @@ __global__ void mv_grid_kernel(const int64_t* __restrict__ seg, int V, ViewWs* _
       atomicAdd(flag, 1u);  // a count of views: the search does not run, the caller raises
       for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.0;
     }
-    set_grid_dev(H.g[0], lo, hi, (m > 0 && finite) ? cbrt(box_volume_dev(lo, hi) * 16.0 / (double)m) : 1.0, cap);
+    set_grid(H.g[0], lo, hi, (m > 0 && finite) ? first_cell_size(box_volume(lo, hi), m) : 1.0, cap);
     H.g[1] = H.g[0];
     H.ncells = H.g[0].ncells;
     H.key_bits = 0;
@@ -168,14 +135,13 @@ __global__ void mv_grid_kernel(const int64_t* __restrict__ seg, int V, ViewWs* _
   H.occupied = occ;  // of the first sort: 0 below if the grid is refined (nothing counts the cells of the second)
   if (m > 0 && H.g[0].ncells > 1) {
     const double ppc = (double)m / (double)max(occ, 1u);
-    if (!(ppc >= 8.0 && ppc <= 32.0)) {
-      // too few points per cell: a surface (~h^2 per cell); too many: the points fill a smaller volume than the box (~h^3 per cell)
+    if (!occupancy_ok(ppc)) {
       double lo[3], hi[3];
       for (int a = 0; a < 3; ++a) {
         lo[a] = H.g[0].lo[a];
         hi[a] = H.g[0].hi[a];
       }
-      set_grid_dev(H.g[0], lo, hi, H.g[0].h * (ppc < 8.0 ? sqrt(16.0 / ppc) : cbrt(16.0 / ppc)), cap);
+      set_grid(H.g[0], lo, hi, refined_cell_size(H.g[0].h, ppc), cap);
       H.g[1] = H.g[0];
       H.ncells = H.g[0].ncells;
       H.occupied = 0;
@@ -233,13 +199,7 @@ __global__ __launch_bounds__(256) void mv_table_kernel(const uint64_t* __restric
   const NNHeader& H = *(const NNHeader*)blob;
   if (c > H.ncells) return;
   const uint64_t want = ((uint64_t)v << cell_bits) | (uint64_t)c;  // c == ncells: beyond every key of the view
-  const int64_t s0 = seg[v];
-  int64_t lo = s0, up = seg[v + 1];
-  while (lo < up) {
-    const int64_t mid = (lo + up) >> 1;
-    if (keys[mid] < want) lo = mid + 1; else up = mid;
-  }
-  ((uint32_t*)(blob + HDR_BYTES + 20 * H.m))[c] = (uint32_t)(lo - s0);
+  ((uint32_t*)(blob + HDR_BYTES + 20 * H.m))[c] = (uint32_t)(first_ge(keys, seg[v], seg[v + 1], want) - seg[v]);
 }
 
 // ---- the search: every query of every directed pair in one launch
@@ -350,7 +310,7 @@ __global__ __launch_bounds__(64) void mv_write_kernel(const int32_t* __restrict_
 
 // ---- host
 struct IndexWs {
-  SortWs sort;
+  SortWs<> sort;
   ViewWs* vw;
   size_t bytes;
 };

@@ -1,13 +1,15 @@
-// The exact nearest-neighbour search shared by the reconstruction metrics (f3r_recon.hip) and the view matcher (f3r_match.hip): the layout of
-// one index (a header, float4 records {x, y, z, index} in cell order, the sorted keys, the cell-start table), the cell arithmetic, the fp64
-// distance, and the ring walk with the lower bound that makes it exact.  Header-only: device functions in an unnamed namespace, so each
-// file that includes it carries its own copy.  Files that include it are compiled with -ffp-contract=off (see dist2).
+// The exact nearest-neighbour index shared by the reconstruction metrics (f3r_recon.hip) and the view matcher (f3r_match.hip): the layout of
+// one index (a header, float4 records {x, y, z, index} in cell order, the sorted keys, the cell-start table), the rules that size a grid
+// (set_grid, the first cell size, the occupancy test, the refinement: host and device functions, so that the host-driven builder of
+// f3r_recon.hip and the device-driven one of f3r_match.hip evaluate one text), the cell arithmetic, the fp64 distance, and the ring walk
+// with the lower bound that makes it exact.  Header-only: functions in an unnamed namespace, so each file that includes it carries its
+// own copy.  Files that include it are compiled with -ffp-contract=off (see dist2).
 #pragma once
 
 #include <cmath>
 #include <cstddef>
 
-#include "f3r_common.h"
+#include "f3r_prims.h"
 
 namespace {
 
@@ -35,6 +37,57 @@ struct NNHeader {
 };
 static_assert(sizeof(NNHeader) <= HDR_BYTES, "header");
 static_assert(sizeof(Grid) == 88 && offsetof(NNHeader, ngrid) == 176, "tests/test_recon_metric_gpu.py reads ngrid at byte 176");
+
+// ---- sizing a grid.  Each builder evaluates these where it always has (f3r_nn_build on the host, mv_grid_kernel on the device: cbrt and sqrt
+//      of the two sides need not agree to the last bit, and h decides the bytes of the index).  fmax / fmin / floor mean the same on both sides
+//      for the finite boxes these see.  The bound of grid_search holds for any h: these rules decide the speed, never the result.
+__host__ __device__ inline int key_bits_of(int64_t n) {  // bits that hold 0 .. n - 1
+  int b = 0;
+  while (b < 62 && ((int64_t)1 << b) < n) ++b;
+  return b;
+}
+
+// grid of cell h over the (finite) box [lo, hi]: at most MAX_DIM cells per axis and cap cells in all
+__host__ __device__ inline void set_grid(Grid& g, const double lo[3], const double hi[3], double h, int64_t cap) {
+  double ext = 0.0;
+  for (int a = 0; a < 3; ++a) ext = fmax(ext, hi[a] - lo[a]);
+  if (!(ext > 0.0)) h = 1.0;
+  else if (!(h >= ext / (MAX_DIM - 0.5))) h = ext / (MAX_DIM - 0.5);  // also a NaN / zero h
+  for (int it = 0;; ++it) {
+    g.h = h;
+    g.inv_h = 1.0 / h;
+    g.ncells = 1;
+    for (int a = 0; a < 3; ++a) {
+      g.lo[a] = lo[a];
+      g.hi[a] = hi[a];
+      g.dims[a] = (int)fmin(fmax(floor((hi[a] - lo[a]) * g.inv_h) + 1.0, 1.0), (double)MAX_DIM);
+      g.ncells *= g.dims[a];
+    }
+    if (g.ncells <= cap) break;
+    // too many cells for the caller's table: a larger cell (h > ext gives one cell, so this ends)
+    h = it < 200 ? h * fmax(cbrt((double)g.ncells / (double)cap), 1.0) * 1.1 : 2.0 * ext;
+  }
+  g.base = 0;
+}
+
+__host__ __device__ inline double box_volume(const double lo[3], const double hi[3]) {
+  double ext = 0.0, vol = 1.0;
+  for (int a = 0; a < 3; ++a) ext = fmax(ext, hi[a] - lo[a]);
+  for (int a = 0; a < 3; ++a) vol *= fmax(hi[a] - lo[a], 1e-3 * ext);
+  return vol;
+}
+
+// the first cell: PPC_TARGET points per cell if the count points filled the volume
+constexpr double PPC_TARGET = 16.0;
+__host__ __device__ inline double first_cell_size(double volume, int64_t count) { return cbrt(volume * PPC_TARGET / (double)count); }
+
+// points per occupied cell after a sort: within a factor of two of the target, the grid stays as it is
+__host__ __device__ inline bool occupancy_ok(double ppc) { return ppc >= 0.5 * PPC_TARGET && ppc <= 2.0 * PPC_TARGET; }
+
+// one refinement.  Too few points per cell: a surface (~h^2 per cell); too many: the points fill a smaller volume than the box (~h^3 per cell)
+__host__ __device__ inline double refined_cell_size(double h, double ppc) {
+  return h * (ppc < 0.5 * PPC_TARGET ? sqrt(PPC_TARGET / ppc) : cbrt(PPC_TARGET / ppc));
+}
 
 __device__ __forceinline__ const float4v* hdr_recs(const uint8_t* ix) { return (const float4v*)(ix + HDR_BYTES); }
 __device__ __forceinline__ const uint32_t* hdr_keys(const uint8_t* ix, int64_t m) { return (const uint32_t*)(ix + HDR_BYTES + 16 * m); }
@@ -136,12 +189,7 @@ __device__ void grid_search(const uint8_t* __restrict__ ix, int gi, double qx, d
             j = table[key];
             e = table[key + 1];
           } else {
-            int64_t lo = 0, hi = H.m;
-            while (lo < hi) {
-              const int64_t mid = (lo + hi) >> 1;
-              if (keys[mid] < key) lo = mid + 1; else hi = mid;
-            }
-            j = lo;
+            j = first_ge(keys, 0, H.m, key);
             e = H.m;
           }
           for (; j < e; ++j) {

@@ -85,6 +85,17 @@ __device__ __forceinline__ int last_le(const I* __restrict__ start, int lo, int 
   return lo;
 }
 
+// ---- its mirror image: the first position in [lo, hi) with keys[position] >= want, or hi if there is none, for keys ascending: where the
+//      run of a key starts in a sorted array
+template <class K>
+__device__ __forceinline__ int64_t first_ge(const K* __restrict__ keys, int64_t lo, int64_t hi, std::common_type_t<K> want) {
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < want) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // ---- sums (see the order contract above)
 template <class T>
 __device__ __forceinline__ T wave_sum(T x) {

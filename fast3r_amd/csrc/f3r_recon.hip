@@ -1,9 +1,9 @@
 // Reconstruction metrics (MultiViewDUSt3RLitModule.evaluate_reconstruction, fast3r/models/multiview_dust3r_module.py:551-735, and
 // accuracy / completion / completion_ratio, fast3r/eval/recon_metric.py:14-49) on the GPU:
 //   * an exact nearest-neighbour index over a point cloud: a uniform grid whose cell is sized from the occupied-cell count (surfaces),
-//     points sorted by cell key with a stable LSD counting sort (per-tile histograms, exclusive scan, ordered per-tile scatter: slot
-//     order never depends on arrival order), float4 records {x, y, z, original index}, a dense cell-start table for small grids and
-//     a binary search in the sorted keys otherwise;
+//     points sorted by their 32-bit cell keys with the stable LSD radix sort of f3r_sort.h (slot order never depends on arrival order),
+//     float4 records {x, y, z, original index}, a dense cell-start table for small grids and a binary search in the sorted keys
+//     otherwise; the grids are sized on the host by the rules of f3r_nn.h;
 //   * exact 1-NN (what scipy's cKDTree.query returns: fp64 distances of the fp32 coordinates, ties to the smaller index) by
 //     Chebyshev rings of cells around the query's cell, stopped by a lower bound on every unvisited cell (grid_search);
 //   * k-NN (k <= 64) and the normal of Open3D's PointCloud.estimate_normals() (KNN 30, fast_normal_computation): one-pass cumulant
@@ -21,14 +21,15 @@
 
 #include "f3r_linalg.h"
 #include "f3r_post_common.h"
-#include "f3r_nn.h"  // the index layout, the cell arithmetic, dist2, grid_search with its lower bound, Best1 (shared with f3r_match.hip)
+#include "f3r_sort.h"  // sort_ws / sort_pairs_lsd, here over 32-bit keys (shared with f3r_cloud.hip, f3r_depth.hip, f3r_match.hip)
+#include "f3r_nn.h"    // the index layout, the sizing rules, the cell arithmetic, dist2, grid_search with its bound, Best1 (shared with f3r_match.hip)
 
 // build.sh compiles this file with -ffp-contract=off: every product and sum is rounded on its own, as the reference's numpy / torch CPU
 // operations and cKDTree's distance are (the __d*_rn intrinsics alone do not stop the compiler from fusing them into FMAs).
 
 namespace {
 
-constexpr int TILE = 2048;         // elements per sort / compaction workgroup (one wave walks its tile in 64-element steps)
+constexpr int TILE = 2048;         // pixels per compaction workgroup of f3r_recon_prepare (one wave walks its tile in 64-pixel steps)
 constexpr int64_t DENSE_EXTRA = 65536;
 constexpr int MISC_BYTES = 512;    // workspace tail: bbox / count words [0, 8), quantiles [8, 14), a header copy from word 16
 constexpr int PNT = 1024;
@@ -68,59 +69,6 @@ __global__ void key_kernel(const float* __restrict__ p, int64_t n, const NNHeade
   vals[i] = (uint32_t)i;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// stable LSD counting sort of (key, val) pairs, 8 bits per pass.  Tile t of TILE elements is one 64-lane workgroup.
-__global__ __launch_bounds__(64) void radix_hist_kernel(const uint32_t* __restrict__ keys, int64_t n, int shift, uint32_t* __restrict__ hist,
-                                                        int64_t ntiles) {
-  __shared__ uint32_t cnt[256];
-  for (int d = threadIdx.x; d < 256; d += 64) cnt[d] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * TILE;
-  const int64_t end = min(base + TILE, n);
-  for (int64_t i = base + threadIdx.x; i < end; i += 64) atomicAdd(&cnt[(keys[i] >> shift) & 255u], 1u);
-  __syncthreads();
-  for (int d = threadIdx.x; d < 256; d += 64) hist[(int64_t)d * ntiles + blockIdx.x] = cnt[d];  // digit-major: the scan gives slot bases
-}
-
-__global__ __launch_bounds__(64) void radix_scatter_kernel(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, int64_t n, int shift,
-                                                           const uint32_t* __restrict__ hist, int64_t ntiles, uint32_t* __restrict__ kout,
-                                                           uint32_t* __restrict__ vout) {
-  __shared__ uint32_t run[256];
-  for (int d = threadIdx.x; d < 256; d += 64) run[d] = hist[(int64_t)d * ntiles + blockIdx.x];
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * TILE;
-  const int64_t end = min(base + TILE, n);
-  for (int64_t c = base; c < end; c += 64) {
-    const int64_t i = c + threadIdx.x;
-    const bool ok = i < end;
-    const uint32_t k = ok ? kin[i] : 0u;
-    const uint32_t d = (k >> shift) & 255u;
-    const uint64_t peers = digit_peers(d, ok);
-    const uint32_t slot = run[d] + (uint32_t)__popcll(peers & lanes_below());  // lanes of the same digit keep their order
-    __syncthreads();
-    if (ok) {
-      kout[slot] = k;
-      vout[slot] = vin[i];
-      if ((peers & lanes_below()) == 0) run[d] += (uint32_t)__popcll(peers);
-    }
-    __syncthreads();
-  }
-}
-
-// sorts (k0, v0) by the low key_bits bits; returns which buffer pair holds the result (0: k0/v0, 1: k1/v1)
-int radix_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t* hist, int64_t n, int key_bits, hipStream_t s) {
-  const int64_t nt = tiles_of(n);
-  int cur = 0;
-  for (int shift = 0; shift < key_bits; shift += 8) {
-    uint32_t *ki = cur ? k1 : k0, *vi = cur ? v1 : v0, *ko = cur ? k0 : k1, *vo = cur ? v0 : v1;
-    hipLaunchKernelGGL(radix_hist_kernel, dim3((unsigned)nt), dim3(64), 0, s, ki, n, shift, hist, nt);
-    hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(1), dim3(SCAN_NT), 0, s, hist, (const int64_t*)nullptr, 256 * nt, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3((unsigned)nt), dim3(64), 0, s, ki, vi, n, shift, hist, nt, ko, vo);
-    cur ^= 1;
-  }
-  return cur;
-}
-
 __global__ void count_heads_kernel(const uint32_t* __restrict__ keys, int64_t n, uint32_t* __restrict__ count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   wave_count_add(i < n && (i == 0 || keys[i] != keys[i - 1]), count);
@@ -129,12 +77,7 @@ __global__ void count_heads_kernel(const uint32_t* __restrict__ keys, int64_t n,
 __global__ void dense_start_kernel(const uint32_t* __restrict__ keys, int64_t m, int64_t ncells, uint32_t* __restrict__ start) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c > ncells) return;
-  int64_t lo = 0, hi = m;  // first position with key >= c
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < (uint32_t)c) lo = mid + 1; else hi = mid;
-  }
-  start[c] = (uint32_t)lo;
+  start[c] = (uint32_t)first_ge(keys, 0, m, (uint32_t)c);  // c == ncells: beyond every key
 }
 
 __global__ void recs_kernel(const float* __restrict__ p, const uint32_t* __restrict__ order, int64_t m, float4v* __restrict__ recs) {
@@ -519,15 +462,19 @@ __global__ void to_i32_kernel(const uint32_t* __restrict__ a, int n, int32_t* __
 }
 
 // the workspaces, sized on a null base and carved on the caller's (a braced list is evaluated left to right: the regions lie in that order).
-// First the sort buffers of f3r_nn_build / _query
-struct SortWs {
-  uint32_t *k0, *v0, *k1, *v1, *hist, *misc;
+// First f3r_nn_build / _query: the sort's buffers over 32-bit keys, then the MISC_BYTES tail
+struct NNWs {
+  SortWs<uint32_t> sort;
+  uint32_t* misc;
   size_t bytes;
 };
-SortWs carve(void* ws, int64_t n) {
+NNWs nn_ws(void* ws, int64_t n) {
   Carve c(ws, 256);
-  return {c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(n), c.take<uint32_t>(256 * tiles_of(n) + 1),
-          c.take<uint32_t>(MISC_BYTES / 4), c.bytes()};
+  NNWs w;
+  w.sort = sort_ws<uint32_t>(c, n);
+  w.misc = c.take<uint32_t>(MISC_BYTES / 4);
+  w.bytes = c.bytes();
+  return w;
 }
 struct StatsWs {
   double *dots, *partial;
@@ -553,41 +500,13 @@ PrepareWs prepare_ws(void* ws, int n_samples, int n_views, int64_t L) {
           c.take<uint8_t>(BL), c.bytes()};
 }
 
-int key_bits_of(int64_t ncells) {
-  int b = 0;
-  while (b < 32 && ((int64_t)1 << b) < ncells) ++b;
-  return b;
-}
-
-// grid of cell h over the (finite) box [lo, hi]: at most MAX_DIM cells per axis
-void set_grid(Grid& g, const double lo[3], const double hi[3], double h) {
-  double ext = 0.0;
-  for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[a] - lo[a]);
-  if (!(ext > 0.0)) h = 1.0;
-  else if (!(h >= ext / (MAX_DIM - 0.5))) h = ext / (MAX_DIM - 0.5);  // also a NaN / zero h
-  g.h = h;
-  g.inv_h = 1.0 / h;
-  g.ncells = 1;
-  for (int a = 0; a < 3; ++a) {
-    g.lo[a] = lo[a];
-    g.hi[a] = hi[a];
-    g.dims[a] = (int)std::min<double>(std::max(std::floor((hi[a] - lo[a]) * g.inv_h) + 1.0, 1.0), MAX_DIM);
-    g.ncells *= g.dims[a];
-  }
-}
+constexpr int64_t NO_CAP = INT64_MAX;  // f3r_nn_build bounds its grids by MAX_DIM per axis only: set_grid's cell cap never binds
 
 // key space of the grids: g[1] after g[0]
 void finish_grids(NNHeader& H) {
   H.g[1].base = (uint32_t)H.g[0].ncells;
   H.ncells = H.g[0].ncells + (H.ngrid == 2 ? H.g[1].ncells : 0);
   H.key_bits = key_bits_of(H.ncells);
-}
-
-double box_volume(const double lo[3], const double hi[3]) {
-  double ext = 0.0, vol = 1.0;
-  for (int a = 0; a < 3; ++a) ext = std::max(ext, hi[a] - lo[a]);
-  for (int a = 0; a < 3; ++a) vol *= std::max(hi[a] - lo[a], 1e-3 * ext);
-  return vol;
 }
 
 }  // namespace
@@ -599,7 +518,7 @@ extern "C" size_t f3r_nn_index_bytes(int64_t m) {
 
 extern "C" size_t f3r_nn_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return carve(nullptr, n).bytes;
+  return nn_ws(nullptr, n).bytes;
 }
 
 extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t index_bytes, void* workspace, size_t ws_bytes, f3r_stream_t stream) {
@@ -613,13 +532,13 @@ extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t ind
   H.m = 0;
   H.ngrid = 1;
   const double unit_lo[3] = {0.0, 0.0, 0.0}, unit_hi[3] = {0.0, 0.0, 0.0};
-  set_grid(H.g[0], unit_lo, unit_hi, 1.0);
+  set_grid(H.g[0], unit_lo, unit_hi, 1.0, NO_CAP);
   finish_grids(H);
   // an empty index first: if the build fails below, the buffer still holds a valid (empty) index
   if (hipMemcpyAsync(ix, &H, sizeof(H), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
     return f3r_check_launch("f3r_nn_build");
   if (m == 0) return f3r_check_launch("f3r_nn_build");
-  SortWs w = carve(workspace, m);
+  const NNWs w = nn_ws(workspace, m);
   // ---- bounding box.  NaN keys order beyond +-inf, so any NaN or inf coordinate makes an end of the box non-finite.
   const uint32_t bb_init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
   uint32_t bb[8];
@@ -640,9 +559,10 @@ extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t ind
   double tlo[3] = {lo[0], lo[1], lo[2]}, thi[3] = {hi[0], hi[1], hi[2]};
   int64_t m_out = 0;
   if (m >= 4096 && ext > 0.0) {
-    float* ax = (float*)w.k0;
-    float* ay = (float*)w.v0;
-    float* az = (float*)w.k1;
+    // fp32 scratch borrowed from the sort before any key is written: keys_a, idx_a, keys_b of the 32-bit carving hold m words each
+    float* ax = (float*)w.sort.keys_a;
+    float* ay = (float*)w.sort.idx_a;
+    float* az = (float*)w.sort.keys_b;
     float* qv = (float*)(w.misc + 8);
     float q[6];
     hipLaunchKernelGGL(deinterleave_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, m, ax, ay, az);
@@ -658,7 +578,7 @@ extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t ind
     }
     if (text < 0.25 * ext) {
       Grid t;
-      set_grid(t, tlo, thi, 1.0);
+      set_grid(t, tlo, thi, 1.0, NO_CAP);
       uint32_t cnt = 0;
       (void)hipMemsetAsync(w.misc + 7, 0, 4, s);
       hipLaunchKernelGGL(outside_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, m, t, w.misc + 7);
@@ -670,22 +590,21 @@ extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t ind
   H.m = m;
   if (m_out > 0) {
     H.ngrid = 2;
-    set_grid(H.g[1], lo, hi, std::cbrt(box_volume(lo, hi) * 16.0 / (double)m_out));
+    set_grid(H.g[1], lo, hi, first_cell_size(box_volume(lo, hi), m_out), NO_CAP);
   } else {
     for (int a = 0; a < 3; ++a) { tlo[a] = lo[a]; thi[a] = hi[a]; }
   }
   const int64_t m_in = m - m_out;
   // ---- cell size of g[0]: 16 points per cell if the cloud filled its box, then one refinement from the occupied-cell count unless
   //      that lands within 8..32 already
-  set_grid(H.g[0], tlo, thi, std::cbrt(box_volume(tlo, thi) * 16.0 / (double)m_in));
+  set_grid(H.g[0], tlo, thi, first_cell_size(box_volume(tlo, thi), m_in), NO_CAP);
   finish_grids(H);
   uint32_t* dhdr = w.misc + 16;  // a device copy of the header for the key kernel (after the bbox / count / quantile words)
-  int res = 0;
+  const uint32_t *ks = w.sort.keys_a, *vs = w.sort.idx_a;
   for (int round = 0; round < 2; ++round) {
     (void)hipMemcpyAsync(dhdr, &H, sizeof(H), hipMemcpyHostToDevice, s);
-    hipLaunchKernelGGL(key_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, m, (const NNHeader*)dhdr, w.k0, w.v0);
-    res = radix_sort(w.k0, w.v0, w.k1, w.v1, w.hist, m, H.key_bits, s);
-    uint32_t* ks = res ? w.k1 : w.k0;
+    hipLaunchKernelGGL(key_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, m, (const NNHeader*)dhdr, w.sort.keys_a, w.sort.idx_a);
+    sort_pairs_lsd(w.sort, m, (H.key_bits + 7) / 8, s, &ks, &vs);
     uint32_t occ = 0;
     (void)hipMemsetAsync(w.misc + 7, 0, 4, s);
     hipLaunchKernelGGL(count_heads_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, ks, m, w.misc + 7);
@@ -693,16 +612,13 @@ extern "C" int f3r_nn_build(const float* pts, int64_t m, void* index, size_t ind
     if (hipStreamSynchronize(s) != hipSuccess) return f3r_check_launch("f3r_nn_build");
     H.occupied = occ;
     const double ppc = (double)m / (double)std::max<uint32_t>(occ, 1);
-    if (round == 1 || (ppc >= 8.0 && ppc <= 32.0) || H.g[0].ncells == 1) break;
-    // too few points per cell: a surface (~h^2 per cell); too many: the points fill a smaller volume than the box (~h^3 per cell)
+    if (round == 1 || occupancy_ok(ppc) || H.g[0].ncells == 1) break;
     const double h_old = H.g[0].h;
-    set_grid(H.g[0], tlo, thi, H.g[0].h * (ppc < 8.0 ? std::sqrt(16.0 / ppc) : std::cbrt(16.0 / ppc)));
+    set_grid(H.g[0], tlo, thi, refined_cell_size(h_old, ppc), NO_CAP);
     finish_grids(H);
     if (H.g[0].h == h_old) break;
   }
   // ---- records, keys, cell table
-  const uint32_t* ks = res ? w.k1 : w.k0;
-  const uint32_t* vs = res ? w.v1 : w.v0;
   H.dense = (H.ncells <= dense_cap(m)) ? 1 : 0;
   hipLaunchKernelGGL(recs_kernel, dim3(blocks_of(m, 256)), dim3(256), 0, s, pts, vs, m, (float4v*)(ix + HDR_BYTES));
   uint32_t* keys = (uint32_t*)(ix + HDR_BYTES + 16 * m);
@@ -728,7 +644,8 @@ extern "C" int f3r_nn_query(const void* index, const float* query, int64_t n, do
   if (n == 0) return F3R_OK;
   hipStream_t s = (hipStream_t)stream;
   // cKDTree rejects non-finite queries (ValueError); so does this, before the search
-  uint32_t* bad = carve(workspace, n).misc;
+  const NNWs w = nn_ws(workspace, n);
+  uint32_t* bad = w.misc;
   uint32_t nbad = 0;
   (void)hipMemsetAsync(bad, 0, 4, s);
   hipLaunchKernelGGL(nonfinite_kernel, dim3(blocks_of(3 * n, 256)), dim3(256), 0, s, query, 3 * n, bad);
@@ -741,10 +658,10 @@ extern "C" int f3r_nn_query(const void* index, const float* query, int64_t n, do
     return f3r_check_launch("f3r_nn_query");
   }
   // queries sorted by their (clamped) cell of the same grid: neighbouring threads walk neighbouring cells
-  SortWs w = carve(workspace, n);
-  hipLaunchKernelGGL(key_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, query, n, (const NNHeader*)index, w.k0, w.v0);
-  const int res = radix_sort(w.k0, w.v0, w.k1, w.v1, w.hist, n, H.key_bits, s);
-  hipLaunchKernelGGL(nn1_kernel, dim3(blocks_of(n, 128)), dim3(128), 0, s, (const uint8_t*)index, query, res ? w.v1 : w.v0, n, dist, idx);
+  const uint32_t *ks, *order;
+  hipLaunchKernelGGL(key_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, query, n, (const NNHeader*)index, w.sort.keys_a, w.sort.idx_a);
+  sort_pairs_lsd(w.sort, n, (H.key_bits + 7) / 8, s, &ks, &order);
+  hipLaunchKernelGGL(nn1_kernel, dim3(blocks_of(n, 128)), dim3(128), 0, s, (const uint8_t*)index, query, order, n, dist, idx);
   return f3r_check_launch("f3r_nn_query");
 }
 

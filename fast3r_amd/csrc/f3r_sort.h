@@ -1,8 +1,10 @@
-// The stable LSD radix sort of (64-bit key, 32-bit value) pairs with 8-bit digits, shared by the voxel downsampler (f3r_cloud.hip) and the
-// sparsification curves of the depth metrics (f3r_depth.hip): per-tile histograms laid out digit-major, a two-level exclusive scan, and a
-// scatter that ranks the keys of a tile in index order with ballots.  Keys of equal digits keep their order in every pass, so the sort is
-// stable; integer atomics on LDS counters only, so two runs give the same bits.  Header-only: kernels with internal linkage, so each file
-// that includes it carries its own copy, and the host driver that launches them.
+// The stable LSD radix sort of (key, 32-bit value) pairs with 8-bit digits, shared by the voxel downsampler (f3r_cloud.hip), the
+// sparsification curves of the depth metrics (f3r_depth.hip), the view matcher's index (f3r_match.hip) -- 64-bit keys, the default -- and the
+// nearest-neighbour index and query order of the reconstruction metrics (f3r_recon.hip, 32-bit cell keys): per-tile histograms laid out
+// digit-major, a two-level exclusive scan, and a scatter that ranks the keys of a tile in index order with ballots.  Keys of equal digits
+// keep their order in every pass, so the sort is stable and its output does not depend on the tile geometry; integer atomics on LDS
+// counters only, so two runs give the same bits.  Header-only: kernel templates with internal linkage, so each file that includes it
+// carries its own copy, and the host driver that launches them.
 #pragma once
 
 #include <algorithm>
@@ -18,7 +20,8 @@ constexpr int SORT_PER = SORT_SUB / 64;
 static_assert(SORT_NT == 256, "one thread per digit");
 
 // hist[digit * n_tiles + tile] = keys of the tile with that digit: digit-major, so one flat scan gives every (digit, tile) its first slot
-static __global__ __launch_bounds__(SORT_NT) void sort_hist_kernel(const uint64_t* __restrict__ keys, int64_t n, int shift,
+template <class K = uint64_t>
+static __global__ __launch_bounds__(SORT_NT) void sort_hist_kernel(const K* __restrict__ keys, int64_t n, int shift,
                                                                    uint32_t* __restrict__ hist, int64_t n_tiles) {
   __shared__ uint32_t cnt[256];
   cnt[threadIdx.x] = 0;
@@ -31,10 +34,11 @@ static __global__ __launch_bounds__(SORT_NT) void sort_hist_kernel(const uint64_
 
 // one stable pass (after the two-level scan of the histogram: rows of row_len words, then the rows' totals): wave w owns keys [sub, sub + SORT_SUB) of the tile and ranks them 64 at a time in lane order; a key's slot is the
 // scanned first slot of its (digit, tile), plus the same digit's keys in the waves before, plus its rank within its wave
-static __global__ __launch_bounds__(SORT_NT) void sort_scatter_kernel(const uint64_t* __restrict__ kin, const uint32_t* __restrict__ vin, int64_t n,
+template <class K = uint64_t>
+static __global__ __launch_bounds__(SORT_NT) void sort_scatter_kernel(const K* __restrict__ kin, const uint32_t* __restrict__ vin, int64_t n,
                                                                       int shift, const uint32_t* __restrict__ hist, int64_t n_tiles,
                                                                       const uint32_t* __restrict__ row_base, int64_t row_len,
-                                                                      uint64_t* __restrict__ kout, uint32_t* __restrict__ vout) {
+                                                                      K* __restrict__ kout, uint32_t* __restrict__ vout) {
   __shared__ uint32_t cnt[SORT_WAVES][256];
   __shared__ uint32_t gbase[256];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
@@ -47,13 +51,13 @@ static __global__ __launch_bounds__(SORT_NT) void sort_scatter_kernel(const uint
   }
   __syncthreads();
   const int64_t sub = base + (int64_t)w * SORT_SUB;
-  uint64_t k[SORT_PER];
+  K k[SORT_PER];
   uint32_t v[SORT_PER], rk[SORT_PER];
 #pragma unroll
   for (int s = 0; s < SORT_PER; ++s) {
     const int64_t i = sub + s * 64 + lane;
     const bool ok = i < end;
-    k[s] = ok ? kin[i] : 0ull;
+    k[s] = ok ? kin[i] : (K)0;
     v[s] = ok ? vin[i] : 0u;
   }
 #pragma unroll
@@ -90,17 +94,19 @@ static __global__ __launch_bounds__(SORT_NT) void sort_scatter_kernel(const uint
 }
 
 // ---- host
+template <class K = uint64_t>
 struct SortWs {  // the sort's part of a workspace: two key and two value buffers of n entries, the histogram and its rows' totals
-  uint64_t *keys_a, *keys_b;
+  K *keys_a, *keys_b;
   uint32_t *idx_a, *idx_b, *hist, *row_tot;
   int64_t sort_tiles, hist_rows, hist_row_len;
 };
 
-inline SortWs sort_ws(Carve& c, int64_t n) {
-  SortWs w = {};
+template <class K = uint64_t>
+inline SortWs<K> sort_ws(Carve& c, int64_t n) {
+  SortWs<K> w = {};
   w.sort_tiles = (n + SORT_TILE - 1) / SORT_TILE;
-  w.keys_a = c.take<uint64_t>(n);
-  w.keys_b = c.take<uint64_t>(n);
+  w.keys_a = c.template take<K>(n);
+  w.keys_b = c.template take<K>(n);
   w.idx_a = c.take<uint32_t>(n);
   w.idx_b = c.take<uint32_t>(n);
   // the digit-major histogram is scanned as hist_rows rows of hist_row_len words by as many workgroups, then the rows' totals by one
@@ -113,19 +119,21 @@ inline SortWs sort_ws(Carve& c, int64_t n) {
 }
 
 // `passes` stable passes over the low 8 * passes bits of the n keys in keys_a (values in idx_a).  The sorted pairs end in keys_a / idx_a
-// after an even number of passes and in keys_b / idx_b after an odd one: *keys and *values say where.  Launches only.
-inline void sort_pairs_lsd(const SortWs& w, int64_t n, int passes, hipStream_t s, const uint64_t** keys, const uint32_t** values) {
-  uint64_t *kin = w.keys_a, *kout = w.keys_b;
+// after an even number of passes (none included: the pairs stay where they are) and in keys_b / idx_b after an odd one: *keys and *values
+// say where.  Launches only.
+template <class K>
+inline void sort_pairs_lsd(const SortWs<K>& w, int64_t n, int passes, hipStream_t s, const K** keys, const uint32_t** values) {
+  K *kin = w.keys_a, *kout = w.keys_b;
   uint32_t *vin = w.idx_a, *vout = w.idx_b;
   for (int pass = 0; pass < passes; ++pass) {
     const dim3 g((unsigned)w.sort_tiles), b(SORT_NT);
-    hipLaunchKernelGGL(sort_hist_kernel, g, b, 0, s, (const uint64_t*)kin, n, pass * 8, w.hist, w.sort_tiles);
+    hipLaunchKernelGGL(sort_hist_kernel<K>, g, b, 0, s, (const K*)kin, n, pass * 8, w.hist, w.sort_tiles);
     // the words past the histogram in the last row hold anything: they follow every word that is read, and the last row's total is not used
     hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3((unsigned)w.hist_rows), dim3(SCAN_NT), 0, s, w.hist, (const int64_t*)nullptr,
                        w.hist_row_len, w.row_tot);
     hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(1), dim3(SCAN_NT), 0, s, w.row_tot, (const int64_t*)nullptr, w.hist_rows,
                        (uint32_t*)nullptr);
-    hipLaunchKernelGGL(sort_scatter_kernel, g, b, 0, s, (const uint64_t*)kin, (const uint32_t*)vin, n, pass * 8, (const uint32_t*)w.hist,
+    hipLaunchKernelGGL(sort_scatter_kernel<K>, g, b, 0, s, (const K*)kin, (const uint32_t*)vin, n, pass * 8, (const uint32_t*)w.hist,
                        w.sort_tiles, (const uint32_t*)w.row_tot, w.hist_row_len, kout, vout);
     std::swap(kin, kout);
     std::swap(vin, vout);

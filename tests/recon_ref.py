@@ -206,3 +206,63 @@ def make_eval_case(B, sizes, seed, holes=True):
         preds.append({"pts3d_in_other_view": torch.stack(prs).float(), "conf": torch.stack(cfs).float(),
                       "pts3d_local": torch.stack(loc).float(), "conf_local": torch.stack(cls).float()})
     return views, preds
+
+
+# ---- the bytes of one nearest-neighbour index (csrc/f3r_nn.h), restated: header fields, fp64 cell keys, the stable order ------------
+NN_HDR_BYTES = 256
+
+
+def nn_header(raw):
+    """the NNHeader at the start of `raw` (uint8): two 88-byte grids {lo[3], hi[3], h, inv_h: fp64; dims[3]: int32; base: uint32; ncells:
+    int64}, then ngrid, dense: int32 (byte 176), m, ncells, occupied: int64, key_bits: int32"""
+    grids = []
+    for k in range(2):
+        b = raw[88 * k:88 * (k + 1)]
+        f = b[:64].view(np.float64)
+        grids.append({"lo": f[0:3].copy(), "hi": f[3:6].copy(), "h": float(f[6]), "inv_h": float(f[7]), "dims": b[64:76].view(np.int32).astype(np.int64),
+                      "base": int(b[76:80].view(np.uint32)[0]), "ncells": int(b[80:88].view(np.int64)[0])})
+    ngrid, dense = (int(v) for v in raw[176:184].view(np.int32))
+    m, ncells, occupied = (int(v) for v in raw[184:208].view(np.int64))
+    return {"g": grids, "ngrid": ngrid, "dense": dense, "m": m, "ncells": ncells, "occupied": occupied, "key_bits": int(raw[208:212].view(np.int32)[0])}
+
+
+def nn_cell_keys(H, pts):
+    """point_key of every fp32 point in fp64, one operation at a time: cell_coord's clamp, the grid choice, the grids' base"""
+    p = pts.astype(np.float64)
+
+    def keys_of(g):
+        c = []
+        for a in range(3):
+            f = np.floor((p[:, a] - g["lo"][a]) * g["inv_h"])
+            c.append(np.where(f >= 0.0, np.minimum(f, float(g["dims"][a] - 1)), 0.0).astype(np.int64))
+        return g["base"] + (c[2] * g["dims"][1] + c[1]) * g["dims"][0] + c[0]
+
+    k = keys_of(H["g"][0])
+    if H["ngrid"] == 2:
+        g = H["g"][0]
+        inside = np.all((p >= g["lo"]) & (p <= g["hi"]), axis=1)
+        k = np.where(inside, k, keys_of(H["g"][1]))
+    return k
+
+
+def check_nn_index(raw, pts, stored_keys=True):
+    """asserts that the index in `raw` (uint8, from its header on) over the fp32 points `pts` holds what its own header implies: records
+    = the points in the stable order of their cell keys with their original indices, the sorted keys after them (f3r_nn_build; the
+    per-view indexes of f3r_match_index leave that region unused), and with `dense` the first sorted position of every cell.  -> header"""
+    H = nn_header(raw)
+    m = H["m"]
+    assert m == len(pts) and H["ngrid"] in (1, 2) and H["ncells"] == H["g"][0]["ncells"] + (H["g"][1]["ncells"] if H["ngrid"] == 2 else 0)
+    assert all(int(np.prod(g["dims"])) == g["ncells"] for g in H["g"][:H["ngrid"]]) and H["g"][0]["base"] == 0
+    keys = nn_cell_keys(H, pts)
+    assert m == 0 or (keys.min() >= 0 and keys.max() < H["ncells"])
+    order = np.argsort(keys, kind="stable")
+    want = keys[order]
+    recs = raw[NN_HDR_BYTES:NN_HDR_BYTES + 16 * m].view(np.uint32).reshape(m, 4)
+    if stored_keys:
+        assert np.array_equal(raw[NN_HDR_BYTES + 16 * m:NN_HDR_BYTES + 20 * m].view(np.uint32), want), "sorted keys"
+    assert np.array_equal(recs[:, 3], order), "record order"
+    assert np.array_equal(recs[:, :3], np.ascontiguousarray(pts[order]).view(np.uint32)), "record coordinates"
+    if H["dense"]:
+        table = raw[NN_HDR_BYTES + 20 * m:NN_HDR_BYTES + 20 * m + 4 * (H["ncells"] + 1)].view(np.uint32)
+        assert np.array_equal(table, np.searchsorted(want, np.arange(H["ncells"] + 1), "left")), "cell starts"
+    return H

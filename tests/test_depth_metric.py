@@ -226,6 +226,20 @@ def test_build_script_carries_the_file_the_flag_and_the_shared_sort():
     assert not re.search(r"atomicAdd\([^)]*(double|float)", depth)
 
 
+def test_the_index_builders_share_the_sort_the_sizing_rules_and_the_search():
+    """f3r_recon.hip and f3r_match.hip take the LSD passes from f3r_sort.h and the grid-sizing rules from f3r_nn.h; no second copy anywhere"""
+    csrc = os.path.join(ROOT, "fast3r_amd", "csrc")
+    files = {os.path.relpath(os.path.join(d, f), csrc): open(os.path.join(d, f)).read() for d, _, fs in os.walk(csrc) if os.path.basename(d) != "obj"
+             for f in sorted(fs) if f.endswith((".hip", ".h", ".cpp", ".py", ".sh"))}
+    for f in ("f3r_recon.hip", "f3r_match.hip"):
+        assert '#include "f3r_sort.h"' in files[f] and '#include "f3r_nn.h"' in files[f] and "sort_pairs_lsd(" in files[f], f
+    for gone in ("radix_scatter_kernel", "set_grid_dev", "box_volume_dev"):
+        assert not [f for f, src in files.items() if gone in src], gone
+    for name, home in (("set_grid", "f3r_nn.h"), ("first_ge", "f3r_prims.h"), ("key_bits_of", "f3r_nn.h")):
+        defined = [f for f, src in files.items() if re.search(r"^[\w \t]*\b(?:void|double|int|int64_t|bool) %s\(" % name, src, flags=re.M)]
+        assert defined == [home], (name, defined)
+
+
 def test_a_library_without_the_depth_metrics_still_loads(tmp_path, monkeypatch):
     from fast3r_amd import _lib, post_ops
     names = [n for n in _lib.SYMBOLS if n not in _lib.SYMBOL_IF_PRESENT_DEPTH and n not in ("f3r_version", "f3r_sizeof")]

@@ -102,6 +102,25 @@ def test_candidate_counts_across_the_wave_and_the_sort_tile(built_lib):
     assert ref["n_candidates"] == list(C.COUNTS) and ref["counts"].max() > 100 and not ref["counts"][(ref["pairs"] == 0).any(1)].any()  # pairs with the empty view
 
 
+def test_per_view_index_bytes_vs_numpy_restatement(built_lib):
+    """The per-view indexes f3r_match_index writes, not the matches they give: three views of 0, 65 and 2049 candidates (an empty slice, one
+    past a wave, one past a sort tile); each slice's records and dense cell starts equal recon_ref.check_nn_index's numpy restatement from
+    that view's own header.  A slice starts 256 bytes + the (V + 1)-word unit table (rounded to 256) + 256 x its scanned unit count in."""
+    import recon_ref
+    from fast3r_amd import post_ops
+    counts = [0, 65, 2049]
+    pts = np.concatenate([recon_ref.make_cloud("uniform", 65, 21), recon_ref.make_cloud("surface", 2049, 22)])
+    raw = post_ops.match_index(torch.from_numpy(pts).to(DEV), counts)["index"].cpu().numpy()
+    assert raw[:4].view(np.uint32)[0] == 0                                      # no view with a NaN / inf coordinate
+    units = raw[256:256 + 4 * (len(counts) + 1)].view(np.uint32)
+    assert units.tolist() == np.concatenate([[0], np.cumsum([(512 + 36 * m + 255) // 256 for m in counts])]).tolist()
+    seg = np.concatenate([[0], np.cumsum(counts)])
+    for v, m in enumerate(counts):
+        H = recon_ref.check_nn_index(raw[512 + 256 * int(units[v]):512 + 256 * int(units[v + 1])], pts[seg[v]:seg[v + 1]], stored_keys=False)
+        print(f"view {v}: {m} candidates, {H['ncells']} cells, {H['occupied']} occupied")
+        assert H["ngrid"] == 1 and H["dense"] == 1 and 1 <= H["ncells"] <= 4 * m + 63
+
+
 def test_one_view_matches_itself(built_lib):
     case = C.views_case(1, 12, 15, [(0, 0)])
     _, got, _ = check("one_view", case)

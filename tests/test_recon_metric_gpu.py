@@ -144,6 +144,34 @@ def _ngrid(ix):
     return int(ix.buf.view(torch.int32)[44].item())  # NNHeader.ngrid: after the two 88-byte grids
 
 
+INDEX_CASES = [("uniform", m, 80 + k) for k, m in enumerate((1, 63, 64, 65, 2047, 2048, 2049, 4097, 6145))] + [
+    ("duplicates", 20000, 8),   # long runs of equal keys across the sort's tiles
+    ("outliers", 30000, 6),     # two grids, one key space
+    ("uniform", 1025000, 90),   # more than 65,536 cells: the smallest uniform size (in steps of 5000) whose keys take 17 bits, three passes
+]
+
+
+def test_index_bytes_vs_numpy_restatement(dev):
+    """The index itself, not the answers it gives (an exact search hides a mis-sorted or mis-tabulated index while some ring still finds
+    the point): the sorted keys, the records' order and coordinates and the dense cell starts equal recon_ref.check_nn_index's numpy
+    restatement from the header the build wrote.  Database sizes at the wave and the 2048-key tile of the shared sort, a third tile
+    with a one-key tail, and 0 .. 3 sort passes ((key_bits + 7) // 8)."""
+    from fast3r_amd.recon_metric import NNIndex
+    passes = {}
+    for kind, m, seed in INDEX_CASES:
+        pts = recon_ref.make_cloud(kind, m, seed)
+        raw = NNIndex(torch.from_numpy(pts).to(dev)).buf.view(torch.uint8).cpu().numpy()
+        H = recon_ref.check_nn_index(raw, pts)
+        assert (1 << H["key_bits"]) >= H["ncells"] and (H["key_bits"] == 0 or (1 << (H["key_bits"] - 1)) < H["ncells"])
+        passes[(kind, m)] = (H["key_bits"] + 7) // 8
+        print(f"{kind} {m}: ngrid {H['ngrid']}, dense {H['dense']}, {H['ncells']} cells, {H['occupied']} occupied, {H['key_bits']} key bits")
+        if kind == "outliers":
+            assert H["ngrid"] == 2
+        if m == 1025000:
+            assert H["key_bits"] >= 17
+    assert {1, 2, 3} <= set(passes.values()), passes
+
+
 def test_far_outliers_get_their_own_grid_and_stay_exact(dev):
     """1 M points in two clusters + 0.1 % outliers at 1e4 x the scene: the outliers go to a second grid; 1-NN of every outlier and
     of 4096 sampled inliers, and k-NN of sampled points (outliers included), equal the brute force"""
