@@ -39,8 +39,8 @@ def _moments(d, mask, log1p):
     f = torch.log1p(d) if log1p else d
     good = mask & ~torch.isnan(f)
     B = d.shape[0]
-    return (mask.reshape(B, -1).sum(1).to(F64), good.reshape(B, -1).sum(1).to(F64),
-            torch.where(good, f, torch.zeros_like(f)).reshape(B, -1).sum(1))
+    return (mask.reshape(B, mask[0].numel()).sum(1).to(F64), good.reshape(B, mask[0].numel()).sum(1).to(F64),
+            torch.where(good, f, torch.zeros_like(f)).reshape(B, mask[0].numel()).sum(1))  # not -1: a view may have no pixels
 
 
 def _factor(cnt, nn, s, version):
@@ -50,14 +50,16 @@ def _factor(cnt, nn, s, version):
     return _clip_min(torch.where(nn != cnt, torch.full_like(s, float("nan")), s / cnt))
 
 
-def multiview_conf_loss(views, preds, version=4, norm_mode="avg_dis", gt_scale=False, local_scale_consistent=False, dist_clip=None, alpha=1.0):
-    """-> (loss, details): Python floats, details with the reference's keys in the reference's order."""
+def multiview_conf_loss(views, preds, version=4, norm_mode="avg_dis", gt_scale=False, local_scale_consistent=False, dist_clip=None, alpha=1.0,
+                        inv=None):
+    """-> (loss, details): Python floats, details with the reference's keys in the reference's order.  inv: the (B, 4, 4) float64 inverse
+    poses per view, for a caller that inverts them another way (default: torch.linalg.inv)."""
     assert version in (3, 4) and norm_mode in ("avg_dis", "avg_log1p")
     log1p = norm_mode == "avg_log1p"
     V = len(views)
     dev = preds[0]["pts3d_in_other_view"].device
     local = "pts3d_local" in preds[0]
-    inv = [_inverse_poses(v["camera_pose"], dev) for v in views]
+    inv = [_inverse_poses(v["camera_pose"], dev) for v in views] if inv is None else [m.to(dev) for m in inv]
     sets = [("global", "pts3d_in_other_view", "conf")] + ([("local", "pts3d_local", "conf_local")] if local else [])
 
     def geometry(v, kind):

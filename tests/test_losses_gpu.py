@@ -66,6 +66,10 @@ def check_outputs(got, ref64, ref32=None, d=None, what=""):
         if math.isnan(got[k]):
             failures.append(f"{what} {k}: NaN where the reference has {want}")
             continue
+        if math.isinf(want) or math.isinf(got[k]):  # equal infinities pass, anything else fails (max(0.0, nan) below would let them through)
+            if got[k] != want:
+                failures.append(f"{what} {k}: {got[k]!r} vs fp64 {want!r}")
+            continue
         err = max(0.0, abs(got[k] - want) - extra)
         worst = max(worst, err / scale(want))
         if err > REL_F64 * scale(want):
