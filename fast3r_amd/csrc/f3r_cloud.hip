@@ -12,14 +12,15 @@
 // Integer atomics only (LDS histogram counters, the bounds keys): two runs give the same bits.  Built with -ffp-contract=off.
 #include "f3r_common.h"
 #include "f3r_post_common.h"
+#include "f3r_view_row.h"
 #include "f3r_sort.h"  // the LSD passes of the voxel sort (SORT_TILE, sort_ws, sort_pairs_lsd), shared with f3r_depth.hip
 
 #include <algorithm>
 
 namespace {
 
-constexpr int CLOUD_TILE = 1024;               // pixels of one combine workgroup (one wave, 16 steps of 64)
-constexpr int CLOUD_STEPS = CLOUD_TILE / 64;
+constexpr int CLOUD_TILE = 1024;               // pixels, or sorted keys, of one compaction workgroup (one wave; tile_compact, f3r_prims.h)
+constexpr int CLOUD_STEPS = CLOUD_TILE / 64;     // the combine kernels: 16 steps of 64
 constexpr int FPS_TILE = 1024;               // points of one tile of the tiled path
 constexpr int FPS_NT = 256;
 constexpr int FPS_PER = FPS_TILE / FPS_NT;
@@ -32,59 +33,41 @@ static_assert(CLOUD_TILE == F3R_CLOUD_TILE && SORT_TILE == F3R_CLOUD_SORT_TILE &
                   FPS_ONE_MAX == F3R_CLOUD_FPS_ONE_MAX,
               "include/f3r.h states the tile lengths");
 
-struct CloudRow {  // one row of the device table, 12 x 8 bytes: the mesh rows (f3r_mesh_threshold reads the same table)
-  const float* conf;    // (H W) fp32, or null: no threshold test
-  const float* pts;     // (H W, 3) fp32
-  const void* img;      // fp32 planes (3, H W) in [-1, 1], or with img_u8 the (H W, 3) bytes themselves
-  const uint8_t* mask;  // (H W) bytes, nonzero = keep, or null
-  int64_t H, W;
-  int64_t vbase;
-  int64_t img_u8;
-  int64_t k_lo, k_hi, gamma_bits, reserved;  // the threshold kernel's
-};
-static_assert(sizeof(CloudRow) == 12 * 8, "include/f3r.h states the row layout");
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// combine
-__device__ __forceinline__ bool cloud_keep(const CloudRow& r, bool use_conf, float t, int64_t i, int64_t n) {
-  bool v = i < n;
-  if (v && use_conf) v = r.conf[i] > t;
-  if (v && r.mask) v = r.mask[i] != 0;
-  return v;
-}
-
+// combine (rows: ViewRow, f3r_view_row.h).  These two kernels keep their own fixed-step loops, not tile_count / tile_compact of
+// f3r_prims.h: measured through the walker the combine stage was 2 to 3 % slower than these loops (docs/rows_f.md).
 // cnt[tile] = kept pixels of the tile (n_tiles + 1 words; the last is zeroed for the scan's total)
-__global__ __launch_bounds__(64) void combine_count_kernel(const CloudRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
+__global__ __launch_bounds__(64) void combine_count_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                            const float* __restrict__ thr, uint32_t* __restrict__ cnt, int64_t n_tiles) {
   const int seg = last_le(ts, 0, S, blockIdx.x);
-  const CloudRow r = rows[seg];
+  const ViewRow r = rows[seg];
   const int64_t n = r.H * r.W, base = (blockIdx.x - ts[seg]) * CLOUD_TILE;
   const bool use_conf = thr && r.conf;
   const float t = use_conf ? thr[seg] : 0.f;
   uint32_t c = 0;
-  for (int s = 0; s < CLOUD_STEPS; ++s) c += wave_flag_count(cloud_keep(r, use_conf, t, base + s * 64 + threadIdx.x, n));
+  for (int s = 0; s < CLOUD_STEPS; ++s) c += wave_flag_count(view_keep(r, use_conf, t, base + s * 64 + threadIdx.x, n));
   if (threadIdx.x == 0) {
     cnt[blockIdx.x] = c;
     if (blockIdx.x == 0) cnt[n_tiles] = 0;
   }
 }
 
-__global__ __launch_bounds__(64) void combine_write_kernel(const CloudRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
+__global__ __launch_bounds__(64) void combine_write_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                            const float* __restrict__ thr, const uint32_t* __restrict__ scan, int flip,
                                                            float* __restrict__ out_p, uint8_t* __restrict__ out_c) {
   const int seg = last_le(ts, 0, S, blockIdx.x);
-  const CloudRow r = rows[seg];
+  const ViewRow r = rows[seg];
   const int64_t n = r.H * r.W, base = (blockIdx.x - ts[seg]) * CLOUD_TILE;
   const bool use_conf = thr && r.conf;
   const float t = use_conf ? thr[seg] : 0.f;
   int64_t run = scan[blockIdx.x];
   for (int s = 0; s < CLOUD_STEPS; ++s) {
     const int64_t i = base + s * 64 + threadIdx.x;
-    const bool keep = cloud_keep(r, use_conf, t, i, n);
+    const bool keep = view_keep(r, use_conf, t, i, n);
     uint64_t bal;
     const int64_t o = run + compact_rank(keep, bal);
     if (keep) {
-      const float x = r.pts[i * 3 + 0], y = r.pts[i * 3 + 1], z = r.pts[i * 3 + 2];
+      const float x = r.pts[i * 3 + 0], y = r.pts[i * 3 + 1], z = r.pts[i * 3 + 2];  // store_point through out_p's __restrict__
       out_p[o * 3 + 0] = x;
       out_p[o * 3 + 1] = flip ? z : y;
       out_p[o * 3 + 2] = flip ? -y : z;
@@ -95,7 +78,7 @@ __global__ __launch_bounds__(64) void combine_write_kernel(const CloudRow* __res
       } else {
         const float* g = (const float*)r.img;
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) out_c[o * 3 + ch] = sat_u8((g[(int64_t)ch * n + i] + 1.0f) * 127.5f);
+        for (int ch = 0; ch < 3; ++ch) out_c[o * 3 + ch] = colour_u8(g[(int64_t)ch * n + i]);
       }
     }
     run += __popcll(bal);
@@ -124,14 +107,11 @@ __global__ __launch_bounds__(BOUNDS_NT) void bounds_kernel(const float* __restri
     }
   }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = min(lo[a], (uint32_t)__shfl_xor(lo[a], off, 64));
-      hi[a] = max(hi[a], (uint32_t)__shfl_xor(hi[a], off, 64));
-    }
-    bad += __shfl_xor(bad, off, 64);
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = wave_min(lo[a]);
+    hi[a] = wave_max(hi[a]);
   }
+  bad = wave_sum(bad);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -156,17 +136,14 @@ __global__ __launch_bounds__(256) void voxel_key_kernel(const float* __restrict_
 }
 
 // segment heads: key differs from its predecessor's.  cnt[tile] = heads of the tile (n_tiles + 1 words, the last zeroed)
-__device__ __forceinline__ bool is_head(const uint64_t* __restrict__ keys, int64_t i, int64_t n) {
-  return i < n && (i == 0 || keys[i] != keys[i - 1]);
-}
+__device__ __forceinline__ bool is_head(const uint64_t* __restrict__ keys, int64_t i) { return i == 0 || keys[i] != keys[i - 1]; }
 
 __global__ __launch_bounds__(64) void head_count_kernel(const uint64_t* __restrict__ keys, int64_t n, uint32_t* __restrict__ cnt,
                                                         int64_t n_tiles) {
-  const int64_t base = (int64_t)blockIdx.x * CLOUD_TILE;
-  uint32_t c = 0;
-  for (int s = 0; s < CLOUD_STEPS; ++s) c += wave_flag_count(is_head(keys, base + s * 64 + threadIdx.x, n));
+  uint32_t c[1];
+  tile_count<CLOUD_TILE>((int64_t)blockIdx.x * CLOUD_TILE, n, [&](int64_t i) { return is_head(keys, i); }, c);
   if (threadIdx.x == 0) {
-    cnt[blockIdx.x] = c;
+    cnt[blockIdx.x] = c[0];
     if (blockIdx.x == 0) cnt[n_tiles] = 0;
   }
 }
@@ -174,16 +151,9 @@ __global__ __launch_bounds__(64) void head_count_kernel(const uint64_t* __restri
 // starts[v] = first sorted position of voxel v; starts[n_voxels] = n; *n_voxels = the scan's total
 __global__ __launch_bounds__(64) void head_starts_kernel(const uint64_t* __restrict__ keys, int64_t n, const uint32_t* __restrict__ scan,
                                                          int64_t n_tiles, uint32_t* __restrict__ starts, uint32_t* __restrict__ n_voxels) {
-  const int64_t base = (int64_t)blockIdx.x * CLOUD_TILE;
-  uint32_t run = scan[blockIdx.x];
-  for (int s = 0; s < CLOUD_STEPS; ++s) {
-    const int64_t i = base + s * 64 + threadIdx.x;
-    const bool h = is_head(keys, i, n);
-    uint64_t bal;
-    const uint32_t o = run + compact_rank(h, bal);
-    if (h) starts[o] = (uint32_t)i;
-    run += (uint32_t)__popcll(bal);
-  }
+  uint32_t run[1] = {scan[blockIdx.x]};
+  tile_compact<CLOUD_TILE>((int64_t)blockIdx.x * CLOUD_TILE, n, run, [&](int64_t i) { return is_head(keys, i); },
+                           [&](int64_t i, uint32_t, const uint32_t(&o)[1]) { starts[o[0]] = (uint32_t)i; });
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const uint32_t total = scan[n_tiles];
     starts[total] = (uint32_t)n;
@@ -401,7 +371,7 @@ extern "C" int f3r_cloud_combine_count(const int64_t* table, int n_views, int64_
   F3R_REQUIRE(n_views >= 1 && n_tiles >= n_views && n_tiles < (1ll << 31), "f3r_cloud_combine_count: %d views, %lld tiles; need at least one view and one tile per view",
               n_views, (long long)n_tiles);
   hipStream_t s = (hipStream_t)stream;
-  const CloudRow* rows = (const CloudRow*)table;
+  const ViewRow* rows = (const ViewRow*)table;
   const int64_t* ts = table + (int64_t)n_views * 12;
   hipLaunchKernelGGL(combine_count_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, rows, ts, n_views, thresholds, scan, n_tiles);
   hipLaunchKernelGGL(exclusive_scan_rows_kernel<SCAN_NT>, dim3(1), dim3(SCAN_NT), 0, s, scan, (const int64_t*)nullptr, n_tiles + 1,
@@ -414,7 +384,7 @@ extern "C" int f3r_cloud_combine_write(const int64_t* table, int n_views, int64_
   F3R_REQUIRE(table && scan && points && colors, "f3r_cloud_combine_write: null pointer");
   F3R_REQUIRE(n_views >= 1 && n_tiles >= n_views && n_tiles < (1ll << 31), "f3r_cloud_combine_write: %d views, %lld tiles; need at least one view and one tile per view",
               n_views, (long long)n_tiles);
-  const CloudRow* rows = (const CloudRow*)table;
+  const ViewRow* rows = (const ViewRow*)table;
   const int64_t* ts = table + (int64_t)n_views * 12;
   hipLaunchKernelGGL(combine_write_kernel, dim3((unsigned)n_tiles), dim3(64), 0, (hipStream_t)stream, rows, ts, n_views, thresholds, scan,
                      flip_axes ? 1 : 0, points, colors);

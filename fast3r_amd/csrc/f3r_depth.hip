@@ -21,7 +21,6 @@ namespace {
 constexpr int TILE = 1024;          // pixels of one workgroup of the error and compaction kernels
 constexpr int ERR_NT = 256;
 constexpr int PX = TILE / ERR_NT;   // consecutive pixels of one thread of the error kernel: 16 bytes of depth, 48 of pointmap
-constexpr int STEPS = TILE / 64;    // the compaction kernels: one wave, 16 steps of 64 pixels
 constexpr int MED_NT = 1024;
 constexpr int NP = 6;               // partials of a tile: sum e, sum (sp - g)^2, the four inlier counts
 constexpr int ROW = 8;              // words of a table row
@@ -238,14 +237,10 @@ __global__ __launch_bounds__(64) void depth_count_kernel(const DepthRow* __restr
   const DepthRow r = rows[seg];
   const bool use_thr = P.use_thr && r.conf;
   const float thr = (float)out[(int64_t)seg * P.out_ld + C_THR];
-  const int64_t base = ((int64_t)blockIdx.x - ts[seg]) * TILE;
-  uint32_t c = 0;
-  for (int s = 0; s < STEPS; ++s) {
-    const int64_t i = base + s * 64 + threadIdx.x;
-    c += wave_flag_count(i < r.n && valid_at(r, use_thr, thr, i));
-  }
+  uint32_t c[1];
+  tile_count<TILE>(((int64_t)blockIdx.x - ts[seg]) * TILE, r.n, [&](int64_t i) { return valid_at(r, use_thr, thr, i); }, c);
   if (threadIdx.x == 0) {
-    cnt[blockIdx.x] = c;
+    cnt[blockIdx.x] = c[0];
     if (blockIdx.x == 0) cnt[n_tiles] = 0;
   }
 }
@@ -261,28 +256,22 @@ __global__ __launch_bounds__(64) void depth_compact_kernel(const DepthRow* __res
   const bool use_thr = P.use_thr && r.conf;
   const float thr = (float)o[C_THR];
   const double s = o[C_SCALE];
-  const int64_t base = ((int64_t)blockIdx.x - ts[seg]) * TILE;
-  uint32_t run = scan[blockIdx.x];
-  for (int st = 0; st < STEPS; ++st) {
-    const int64_t i = base + st * 64 + threadIdx.x;
-    const bool keep = i < r.n && valid_at(r, use_thr, thr, i);
-    uint64_t bal;
-    const uint32_t slot = run + compact_rank(keep, bal);
-    if (keep) {
-      uint32_t key;
-      if (by_error) {
-        double sp, d;
-        const double e = rel_error(P, s, r.g[i], r.p[i * r.p_stride + r.p_chan], sp, d);
-        err[r.base + i] = e;
-        key = ~fkey((float)e);  // descending e
-      } else {
-        key = r.conf ? fkey(r.conf[i]) : 0u;
-      }
-      keys[slot] = ((uint64_t)seg << 32) | key;
-      idx[slot] = (uint32_t)i;
-    }
-    run += (uint32_t)__popcll(bal);
-  }
+  uint32_t run[1] = {scan[blockIdx.x]};
+  tile_compact<TILE>(
+      ((int64_t)blockIdx.x - ts[seg]) * TILE, r.n, run, [&](int64_t i) { return valid_at(r, use_thr, thr, i); },
+      [&](int64_t i, uint32_t, const uint32_t(&slot)[1]) {
+        uint32_t key;
+        if (by_error) {
+          double sp, d;
+          const double e = rel_error(P, s, r.g[i], r.p[i * r.p_stride + r.p_chan], sp, d);
+          err[r.base + i] = e;
+          key = ~fkey((float)e);  // descending e
+        } else {
+          key = r.conf ? fkey(r.conf[i]) : 0u;
+        }
+        keys[slot[0]] = ((uint64_t)seg << 32) | key;
+        idx[slot[0]] = (uint32_t)i;
+      });
 }
 
 // the slots past the valid pixels hold the largest key: a stable sort leaves them where they are, after every segment

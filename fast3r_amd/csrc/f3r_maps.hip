@@ -215,7 +215,7 @@ __global__ __launch_bounds__(MAPS_NT) void maps_rgb_kernel(const int64_t* __rest
     for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
       for (int j = 0; j < MAPS_PER; ++j)
-        if (p0 + j < n) col[j] |= (uint32_t)sat_u8((v[ch][j] + 1.0f) * 127.5f) << (8 * ch);
+        if (p0 + j < n) col[j] |= (uint32_t)colour_u8(v[ch][j]) << (8 * ch);
     store4(r.dst, r.pitch, r.W, p0, n, col);
   }
 }

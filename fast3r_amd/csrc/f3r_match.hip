@@ -258,15 +258,15 @@ __global__ __launch_bounds__(64) void mv_count_kernel(const int32_t* __restrict_
   const int64_t tile = blockIdx.x;
   const int p = last_le(tile_off, 0, P, tile);
   const PairView w = pair_view(pairs, p, seg, V, qoff, D, Q);
-  const int64_t base = (tile - tile_off[p]) * MATCH_TILE, end = min(base + (int64_t)MATCH_TILE, w.nj);
-  uint32_t n = 0;
-  if (w.ok)
-    for (int64_t q = base + threadIdx.x; q < end; q += 64) {
-      int32_t a;
-      n += reciprocal(w, nn_idx, q, a) ? 1u : 0u;
-    }
-  n = wave_sum(n);
-  if (threadIdx.x == 0) cnt[tile] = n;
+  uint32_t n[1];
+  tile_count<MATCH_TILE>(
+      (tile - tile_off[p]) * MATCH_TILE, w.nj,
+      [&](int64_t q) {
+        int32_t a;
+        return w.ok && reciprocal(w, nn_idx, q, a);
+      },
+      n);
+  if (threadIdx.x == 0) cnt[tile] = n[0];
 }
 
 // offsets[p] = matches before pair p (the scanned count of its first tile; tile_off[P] is the word after the last tile: the total)
@@ -288,24 +288,20 @@ __global__ __launch_bounds__(64) void mv_write_kernel(const int32_t* __restrict_
   const PairView w = pair_view(pairs, p, seg, V, qoff, D, Q);
   if (!w.ok) return;
   const int wi = max(widths[pairs[4 * p]], 1), wj = max(widths[pairs[4 * p + 1]], 1);
-  const int64_t base = (tile - tile_off[p]) * MATCH_TILE, end = min(base + (int64_t)MATCH_TILE, w.nj);
-  int64_t run = cnt[tile];
-  for (int64_t c = base; c < end; c += 64) {
-    const int64_t q = c + threadIdx.x;
-    int32_t a = 0;
-    const bool keep = q < end && reciprocal(w, nn_idx, q, a);
-    uint64_t bal;
-    const int64_t o = run + compact_rank(keep, bal);
-    if (keep && o < M) {
-      const int32_t pj = pix[w.sj + q], pi = pix[w.si + a];
-      xy_j[2 * o] = pj % wj;
-      xy_j[2 * o + 1] = pj / wj;
-      xy_i[2 * o] = pi % wi;
-      xy_i[2 * o + 1] = pi / wi;
-      dist[o] = nn_dist[w.q_ji + q];
-    }
-    run += __popcll(bal);
-  }
+  int64_t run[1] = {cnt[tile]};
+  int32_t a = 0;  // candidate q's neighbour in view i: flags leaves it for emit
+  tile_compact<MATCH_TILE>(
+      (tile - tile_off[p]) * MATCH_TILE, w.nj, run, [&](int64_t q) { return reciprocal(w, nn_idx, q, a); },
+      [&](int64_t q, uint32_t, const int64_t(&slot)[1]) {
+        const int64_t o = slot[0];
+        if (o >= M) return;
+        const int32_t pj = pix[w.sj + q], pi = pix[w.si + a];
+        xy_j[2 * o] = pj % wj;
+        xy_j[2 * o + 1] = pj / wj;
+        xy_i[2 * o] = pi % wi;
+        xy_i[2 * o + 1] = pi / wi;
+        dist[o] = nn_dist[w.q_ji + q];
+      });
 }
 
 // ---- host

@@ -14,6 +14,7 @@
 // -ffp-contract=off: the interpolation and the colour arithmetic round each fp32 operation on its own, as numpy does.
 #include "f3r_common.h"
 #include "f3r_post_common.h"
+#include "f3r_view_row.h"  // the rows of the device table, 12 x 8 bytes: ViewRow
 
 #include <algorithm>
 
@@ -24,28 +25,14 @@ constexpr int MESH_STEPS = MESH_TILE / 64;     // = bitmap words per vertex tile
 constexpr int THR_NT = 1024;                   // threads of a threshold workgroup
 static_assert(MESH_TILE == F3R_MESH_TILE, "include/f3r.h states the tile length");
 
-struct MeshRow {  // one row of the device table, 12 x 8 bytes
-  const float* conf;    // (H W) fp32, or null: validity is the mask alone
-  const float* pts;     // (H W, 3) fp32
-  const void* img;      // fp32 planes (3, H W) in [-1, 1], or with img_u8 the (H W, 3) bytes themselves
-  const uint8_t* mask;  // (H W) bytes, nonzero = valid, or null
-  int64_t H, W;
-  int64_t vbase;        // sum of H W over the views before this one
-  int64_t img_u8;
-  int64_t k_lo, k_hi;   // the two 0-based ranks np.percentile reads
-  int64_t gamma_bits;   // its fp32 interpolation weight, as bits
-  int64_t reserved;
-};
-static_assert(sizeof(MeshRow) == 12 * 8, "include/f3r.h states the row layout");
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // thr[v] = np.percentile(conf of view v, p): numpy's _lerp on the order statistics k_lo, k_hi with weight gamma; NaN if any conf is NaN
-__global__ __launch_bounds__(THR_NT) void mesh_threshold_kernel(const MeshRow* __restrict__ rows, float* __restrict__ thr,
+__global__ __launch_bounds__(THR_NT) void mesh_threshold_kernel(const ViewRow* __restrict__ rows, float* __restrict__ thr,
                                                                 uint32_t* __restrict__ nan_count) {
   __shared__ uint32_t hist[2048];
   __shared__ int64_t sh_i64[2];
   __shared__ uint32_t sh_nan;
-  const MeshRow r = rows[blockIdx.x];
+  const ViewRow r = rows[blockIdx.x];
   const int64_t n = r.H * r.W;
   if (threadIdx.x == 0) sh_nan = 0;
   __syncthreads();
@@ -74,56 +61,49 @@ __global__ __launch_bounds__(THR_NT) void mesh_threshold_kernel(const MeshRow* _
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // validity bitmap: view v's words start at 16 tsv[v]; pixel i = bit i % 64 of word i / 64; bits beyond H W are zero
-__global__ __launch_bounds__(64) void mesh_valid_kernel(const MeshRow* __restrict__ rows, const int64_t* __restrict__ tsv, int S,
+__global__ __launch_bounds__(64) void mesh_valid_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ tsv, int S,
                                                         const float* __restrict__ thr, uint64_t* __restrict__ bits) {
   const int seg = last_le(tsv, 0, S, blockIdx.x);
-  const MeshRow r = rows[seg];
+  const ViewRow r = rows[seg];
   const int64_t n = r.H * r.W, base = (blockIdx.x - tsv[seg]) * MESH_TILE;
   const bool use_conf = thr && r.conf;
   const float t = use_conf ? thr[seg] : 0.f;
   for (int s = 0; s < MESH_STEPS; ++s) {
-    const int64_t i = base + s * 64 + threadIdx.x;
-    bool v = i < n;
-    if (v && use_conf) v = r.conf[i] > t;
-    if (v && r.mask) v = r.mask[i] != 0;
-    const uint64_t b = __ballot(v);
+    const uint64_t b = __ballot(view_keep(r, use_conf, t, base + s * 64 + threadIdx.x, n));
     if (threadIdx.x == 0) bits[(int64_t)blockIdx.x * MESH_STEPS + s] = b;
   }
 }
 
 __device__ __forceinline__ bool vbit(const uint64_t* __restrict__ vb, uint32_t i) { return (vb[i >> 6] >> (i & 63)) & 1ull; }
 
-// quad q of a view of width W: its top-left pixel i, and whether triangles A (i, i+1, i+W) and B (i+1, i+W, i+W+1) are kept
-__device__ __forceinline__ void quad_keep(const uint64_t* __restrict__ vb, uint32_t q, uint32_t W, uint32_t& i, bool& a, bool& b) {
+// quad q of a view of width W: i = its top-left pixel; bit 0 = triangle A (i, i+1, i+W) is kept, bit 1 = triangle B (i+1, i+W, i+W+1)
+__device__ __forceinline__ uint32_t quad_keep(const uint64_t* __restrict__ vb, uint32_t q, uint32_t W, uint32_t& i) {
   const uint32_t y = q / (W - 1), x = q - y * (W - 1);
   i = y * W + x;
-  const bool v2 = vbit(vb, i + 1), v3 = vbit(vb, i + W);
-  a = v2 && v3 && vbit(vb, i);
-  b = v2 && v3 && vbit(vb, i + W + 1);
+  const bool v23 = vbit(vb, i + 1) && vbit(vb, i + W);
+  return (v23 && vbit(vb, i) ? 1u : 0u) | (v23 && vbit(vb, i + W + 1) ? 2u : 0u);
 }
 
-__device__ __forceinline__ int64_t quads_of(const MeshRow& r) { return (r.H - 1) * (r.W - 1); }
+__device__ __forceinline__ int64_t quads_of(const ViewRow& r) { return (r.H - 1) * (r.W - 1); }
 
 // cnt[0][tile] = kept A, cnt[1][tile] = kept B (rows of n_tiles + 1 words; the last word of each row is zeroed for the scan's total)
-__global__ __launch_bounds__(64) void mesh_count_kernel(const MeshRow* __restrict__ rows, const int64_t* __restrict__ tsv,
+__global__ __launch_bounds__(64) void mesh_count_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ tsv,
                                                         const int64_t* __restrict__ tsq, int S, const uint64_t* __restrict__ bits,
                                                         uint32_t* __restrict__ cnt, int64_t n_tiles) {
   const int seg = last_le(tsq, 0, S, blockIdx.x);
-  const MeshRow r = rows[seg];
+  const ViewRow r = rows[seg];
   const uint64_t* vb = bits + tsv[seg] * MESH_STEPS;
-  const int64_t Q = quads_of(r), base = (blockIdx.x - tsq[seg]) * MESH_TILE;
-  uint32_t ca = 0, cb = 0;
-  for (int s = 0; s < MESH_STEPS; ++s) {
-    const int64_t q = base + s * 64 + threadIdx.x;
-    bool a = false, b = false;
-    uint32_t i;
-    if (q < Q) quad_keep(vb, (uint32_t)q, (uint32_t)r.W, i, a, b);
-    ca += wave_flag_count(a);
-    cb += wave_flag_count(b);
-  }
+  uint32_t c[2];
+  tile_count<MESH_TILE>(
+      (blockIdx.x - tsq[seg]) * MESH_TILE, quads_of(r),
+      [&](int64_t q) {
+        uint32_t i;
+        return quad_keep(vb, (uint32_t)q, (uint32_t)r.W, i);
+      },
+      c);
   if (threadIdx.x == 0) {
-    cnt[blockIdx.x] = ca;
-    cnt[n_tiles + 1 + blockIdx.x] = cb;
+    cnt[blockIdx.x] = c[0];
+    cnt[n_tiles + 1 + blockIdx.x] = c[1];
     if (blockIdx.x == 0) cnt[n_tiles] = cnt[2 * n_tiles + 1] = 0;
   }
 }
@@ -139,11 +119,11 @@ __device__ __forceinline__ bool vertex_used(const uint64_t* __restrict__ vb, uin
 }
 
 // ubits: the "used" bitmap, laid out like the validity bitmap; cntv[tile] = used vertices of the tile (n_tiles + 1 words, last zeroed)
-__global__ __launch_bounds__(64) void mesh_used_kernel(const MeshRow* __restrict__ rows, const int64_t* __restrict__ tsv, int S,
+__global__ __launch_bounds__(64) void mesh_used_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ tsv, int S,
                                                        const uint64_t* __restrict__ bits, uint64_t* __restrict__ ubits,
                                                        uint32_t* __restrict__ cntv, int64_t n_tiles) {
   const int seg = last_le(tsv, 0, S, blockIdx.x);
-  const MeshRow r = rows[seg];
+  const ViewRow r = rows[seg];
   const uint64_t* vb = bits + tsv[seg] * MESH_STEPS;
   const int64_t n = r.H * r.W, base = (blockIdx.x - tsv[seg]) * MESH_TILE;
   uint32_t c = 0;
@@ -161,7 +141,7 @@ __global__ __launch_bounds__(64) void mesh_used_kernel(const MeshRow* __restrict
 }
 
 // counts[v] = { kept A, kept B, used vertices (H W without the used scan) } of view v, from the scans
-__global__ void mesh_totals_kernel(const MeshRow* __restrict__ rows, const int64_t* __restrict__ tsv, const int64_t* __restrict__ tsq, int S,
+__global__ void mesh_totals_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ tsv, const int64_t* __restrict__ tsq, int S,
                                    const uint32_t* __restrict__ scanf, int64_t n_quad_tiles, const uint32_t* __restrict__ scanv,
                                    uint32_t* __restrict__ counts) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -175,11 +155,11 @@ __global__ void mesh_totals_kernel(const MeshRow* __restrict__ rows, const int64
 // ---------------------------------------------------------------------------------------------------------------------------
 // vertices: every pixel at vbase + i, or with DROP the used ones at their rank (and remap[vbase + i] = that rank, -1 if unused)
 template <bool DROP>
-__global__ __launch_bounds__(64) void mesh_vertex_kernel(const MeshRow* __restrict__ rows, const int64_t* __restrict__ tsv, int S,
+__global__ __launch_bounds__(64) void mesh_vertex_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ tsv, int S,
                                                          const uint64_t* __restrict__ ubits, const uint32_t* __restrict__ scanv, int flip,
                                                          float* __restrict__ out, int32_t* __restrict__ remap) {
   const int seg = last_le(tsv, 0, S, blockIdx.x);
-  const MeshRow r = rows[seg];
+  const ViewRow r = rows[seg];
   const int64_t n = r.H * r.W, base = (blockIdx.x - tsv[seg]) * MESH_TILE;
   int64_t run = DROP ? (int64_t)scanv[blockIdx.x] : 0;
   for (int s = 0; s < MESH_STEPS; ++s) {
@@ -194,12 +174,7 @@ __global__ __launch_bounds__(64) void mesh_vertex_kernel(const MeshRow* __restri
       run += __popcll(w);
       if (ok) remap[r.vbase + i] = keep ? (int32_t)o : -1;
     }
-    if (keep) {
-      const float x = r.pts[i * 3 + 0], y = r.pts[i * 3 + 1], z = r.pts[i * 3 + 2];
-      out[o * 3 + 0] = x;
-      out[o * 3 + 1] = flip ? z : y;
-      out[o * 3 + 2] = flip ? -y : z;
-    }
+    if (keep) store_point(r, i, flip, out, o);
   }
 }
 
@@ -213,67 +188,45 @@ __device__ __forceinline__ void put_face(IDX* __restrict__ faces, uint8_t* __res
   for (int ch = 0; ch < 3; ++ch) col[p * 3 + ch] = (uint8_t)(rgb >> (8 * ch));
 }
 
-__device__ __forceinline__ uint32_t pixel_rgb(const MeshRow& r, int64_t n, int64_t i) {
-  uint32_t pk = 0;
-  if (r.img_u8) {
-    const uint8_t* g = (const uint8_t*)r.img + i * 3;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) pk |= (uint32_t)g[ch] << (8 * ch);
-  } else {
-    const float* g = (const float*)r.img;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) pk |= (uint32_t)sat_u8((g[(int64_t)ch * n + i] + 1.0f) * 127.5f) << (8 * ch);
-  }
-  return pk;
-}
-
 // faces of view v from slot mult (A before + B before): [kept A][A backward][kept B][B backward] (mult = 2), or [kept A][kept B] (mult = 1)
 template <class IDX, bool REMAP>
-__global__ __launch_bounds__(64) void mesh_face_kernel(const MeshRow* __restrict__ rows, const int64_t* __restrict__ tsv,
+__global__ __launch_bounds__(64) void mesh_face_kernel(const ViewRow* __restrict__ rows, const int64_t* __restrict__ tsv,
                                                        const int64_t* __restrict__ tsq, int S, const uint64_t* __restrict__ bits,
                                                        const uint32_t* __restrict__ scanf, int64_t n_tiles, int mult,
                                                        const int32_t* __restrict__ remap, IDX* __restrict__ faces, uint8_t* __restrict__ col) {
   const int seg = last_le(tsq, 0, S, blockIdx.x);
-  const MeshRow r = rows[seg];
+  const ViewRow r = rows[seg];
   const uint64_t* vb = bits + tsv[seg] * MESH_STEPS;
-  const int64_t Q = quads_of(r), n = r.H * r.W, base = (blockIdx.x - tsq[seg]) * MESH_TILE;
+  const int64_t n = r.H * r.W;
   const uint32_t* sa = scanf;
   const uint32_t* sb = scanf + n_tiles + 1;
   const int64_t t0 = tsq[seg], t1 = tsq[seg + 1];
   const int64_t a0 = sa[t0], b0 = sb[t0], av = (int64_t)sa[t1] - a0, bv = (int64_t)sb[t1] - b0;
   const int64_t fa = (int64_t)mult * (a0 + b0), fb = fa + (int64_t)mult * av;
-  int64_t run_a = (int64_t)sa[blockIdx.x] - a0, run_b = (int64_t)sb[blockIdx.x] - b0;
-  for (int s = 0; s < MESH_STEPS; ++s) {
-    const int64_t q = base + s * 64 + threadIdx.x;
-    bool a = false, b = false;
-    uint32_t i = 0;
-    if (q < Q) quad_keep(vb, (uint32_t)q, (uint32_t)r.W, i, a, b);
-    uint64_t bal_a, bal_b;
-    const uint32_t rank_a = compact_rank(a, bal_a), rank_b = compact_rank(b, bal_b);
-    if (a || b) {
-      int64_t g1 = r.vbase + i, g2 = g1 + 1, g3 = g1 + r.W, g4 = g3 + 1;
-      if (REMAP) {  // a kept triangle's vertices are used: their remap entries are >= 0
-        g2 = remap[g2];
-        g3 = remap[g3];
-        if (a) g1 = remap[g1];
-        if (b) g4 = remap[g4];
-      }
-      if (a) {
-        const uint32_t rgb = pixel_rgb(r, n, i);  // the quad's top-left pixel
-        const int64_t p = fa + run_a + rank_a;
-        put_face(faces, col, p, g1, g2, g3, rgb);
-        if (mult == 2) put_face(faces, col, p + av, g3, g2, g1, rgb);
-      }
-      if (b) {
-        const uint32_t rgb = pixel_rgb(r, n, (int64_t)i + r.W + 1);  // its bottom-right pixel
-        const int64_t p = fb + run_b + rank_b;
-        put_face(faces, col, p, g2, g3, g4, rgb);
-        if (mult == 2) put_face(faces, col, p + bv, g4, g3, g2, rgb);
-      }
-    }
-    run_a += __popcll(bal_a);
-    run_b += __popcll(bal_b);
-  }
+  int64_t run[2] = {fa + sa[blockIdx.x] - a0, fb + sb[blockIdx.x] - b0};
+  uint32_t i = 0;  // the quad's top-left pixel: flags leaves it for emit
+  tile_compact<MESH_TILE>(
+      (blockIdx.x - tsq[seg]) * MESH_TILE, quads_of(r), run, [&](int64_t q) { return quad_keep(vb, (uint32_t)q, (uint32_t)r.W, i); },
+      [&](int64_t, uint32_t ab, const int64_t(&p)[2]) {
+        const bool a = ab & 1u, b = ab & 2u;
+        int64_t g1 = r.vbase + i, g2 = g1 + 1, g3 = g1 + r.W, g4 = g3 + 1;
+        if (REMAP) {  // a kept triangle's vertices are used: their remap entries are >= 0
+          g2 = remap[g2];
+          g3 = remap[g3];
+          if (a) g1 = remap[g1];
+          if (b) g4 = remap[g4];
+        }
+        if (a) {
+          const uint32_t rgb = pixel_rgb(r, n, i);  // the quad's top-left pixel
+          put_face(faces, col, p[0], g1, g2, g3, rgb);
+          if (mult == 2) put_face(faces, col, p[0] + av, g3, g2, g1, rgb);
+        }
+        if (b) {
+          const uint32_t rgb = pixel_rgb(r, n, (int64_t)i + r.W + 1);  // its bottom-right pixel
+          put_face(faces, col, p[1], g2, g3, g4, rgb);
+          if (mult == 2) put_face(faces, col, p[1] + bv, g4, g3, g2, rgb);
+        }
+      });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -351,7 +304,7 @@ extern "C" size_t f3r_mesh_workspace_bytes(int64_t n_vertex_tiles, int64_t n_qua
 extern "C" int f3r_mesh_threshold(const int64_t* table, int n_views, float* thresholds, uint32_t* nan_counts, f3r_stream_t stream) {
   F3R_REQUIRE(table && thresholds && nan_counts, "f3r_mesh_threshold: null pointer");
   F3R_REQUIRE(n_views >= 1, "f3r_mesh_threshold: n_views = %d; need at least one view", n_views);
-  hipLaunchKernelGGL(mesh_threshold_kernel, dim3(n_views), dim3(THR_NT), 0, (hipStream_t)stream, (const MeshRow*)table, thresholds, nan_counts);
+  hipLaunchKernelGGL(mesh_threshold_kernel, dim3(n_views), dim3(THR_NT), 0, (hipStream_t)stream, (const ViewRow*)table, thresholds, nan_counts);
   return f3r_check_launch("f3r_mesh_threshold");
 }
 
@@ -363,7 +316,7 @@ extern "C" int f3r_mesh_count(const int64_t* table, const int64_t* host_hw, int 
   const MeshWs m = mesh_ws(workspace, n_vertex_tiles, n_quad_tiles, total_vertices, drop_unreferenced);
   F3R_REQUIRE(workspace_bytes >= m.bytes, "f3r_mesh_count: workspace too small (%zu bytes; need %zu)", workspace_bytes, m.bytes);
   hipStream_t s = (hipStream_t)stream;
-  const MeshRow* rows = (const MeshRow*)table;
+  const ViewRow* rows = (const ViewRow*)table;
   const int64_t* tsv = table + (int64_t)n_views * 12;
   const int64_t* tsq = tsv + n_views + 1;
   const dim3 gv((unsigned)n_vertex_tiles), gq((unsigned)n_quad_tiles), b(64);
@@ -392,7 +345,7 @@ extern "C" int f3r_mesh_write(const int64_t* table, const int64_t* host_hw, int 
   const MeshWs m = mesh_ws((void*)workspace, n_vertex_tiles, n_quad_tiles, total_vertices, drop_unreferenced);
   F3R_REQUIRE(workspace_bytes >= m.bytes, "f3r_mesh_write: workspace too small (%zu bytes; need %zu)", workspace_bytes, m.bytes);
   hipStream_t s = (hipStream_t)stream;
-  const MeshRow* rows = (const MeshRow*)table;
+  const ViewRow* rows = (const ViewRow*)table;
   const int64_t* tsv = table + (int64_t)n_views * 12;
   const int64_t* tsq = tsv + n_views + 1;
   const dim3 gv((unsigned)n_vertex_tiles), gq((unsigned)n_quad_tiles), b(64);

@@ -12,6 +12,8 @@
 //     passes) starts at +0.0, so neither a thread's value nor a wave's sum can be -0.0.  A new caller keeps to that.
 //   * digit_peers and compact_rank rank lanes in lane order, and exclusive_scan_rows_kernel is integer arithmetic: slots never depend on
 //     which lane or workgroup ran first.
+//   * tile_count adds integers, and tile_compact walks a tile in ascending 64-element steps and ranks with compact_rank: the slot of a kept
+//     element is the scanned count of the tiles before its own plus the number of kept elements before it in its tile, nothing else.
 #pragma once
 
 #include <type_traits>
@@ -37,12 +39,14 @@ __device__ __forceinline__ double dkey_inv(uint64_t k) {
   return __builtin_bit_cast(double, u);
 }
 
-// ---- the 8-bit colour of an image value (scene, sky and mesh form (img + 1) * 127.5 themselves)
+// ---- the 8-bit colour of an image value
 __device__ __forceinline__ uint8_t sat_u8(float y) {  // truncation to uint8; below 0 and NaN -> 0, above 255 -> 255
   if (!(y > 0.f)) return 0;
   if (y >= 255.f) return 255;
   return (uint8_t)(int)y;
 }
+// the colour line of an image value in [-1, 1]: an add and a multiply, each rounded (every file that calls it is built with -ffp-contract=off)
+__device__ __forceinline__ uint8_t colour_u8(float v) { return sat_u8((v + 1.0f) * 127.5f); }
 
 // ---- ballots
 __device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
@@ -122,6 +126,55 @@ __device__ __forceinline__ void block_sum(const double* v, double (*red)[LD], do
     out[threadIdx.x] = s;
   }
   __syncthreads();
+}
+
+// ---- the tile walk of an ordered compaction with K streams (1 or 2), called by one wave.  The tile is the elements [base, stop),
+// stop = min(base + TILE, end).  flags(i) gives an in-range element's mask, once per element per kernel: bit k set = kept in stream k; bits
+// K and up are the caller's and travel to emit untouched.  Lanes at or past stop have mask 0 and never call flags.
+// Count kernel, scan of the counts, then tile_compact with run[k] = the scanned count: that is the whole compaction.
+//
+// n[k] = the tile's kept elements of stream k, in every lane.  Each lane counts its own elements and one wave_sum adds the lanes: integer
+// sums, the same number as a ballot count per step, and the lanes' loads do not wait for one another.
+template <int TILE, int K, class Flags>
+__device__ __forceinline__ void tile_count(int64_t base, int64_t end, Flags flags, uint32_t (&n)[K]) {
+  static_assert(TILE % 64 == 0 && (K == 1 || K == 2), "tile_count: whole waves, one or two streams");
+  const int64_t stop = min(base + (int64_t)TILE, end);
+#pragma unroll
+  for (int k = 0; k < K; ++k) n[k] = 0;
+  for (int64_t i = base + (threadIdx.x & 63); i < stop; i += 64) {
+    const uint32_t m = (uint32_t)flags(i);
+#pragma unroll
+    for (int k = 0; k < K; ++k) n[k] += (m >> k) & 1u;
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) n[k] = wave_sum(n[k]);
+}
+
+// The steps c = base, base + 64, .. < stop in ascending order.  emit(i, mask, slots) runs on the lanes with a stream bit set: slots[k] =
+// run[k] + the lane's rank among the tile's keepers of stream k so far, meaningful where mask bit k is set.  A lane's emit follows its
+// flags of the same step directly, before any later flags: a kernel may leave what flags looked up in a local for emit (mesh_face_kernel,
+// mv_write_kernel).  On return run[k] has advanced by the tile's count.  S: the caller's slot type.
+template <int TILE, int K, class S, class Flags, class Emit>
+__device__ __forceinline__ void tile_compact(int64_t base, int64_t end, S (&run)[K], Flags flags, Emit emit) {
+  static_assert(TILE % 64 == 0 && (K == 1 || K == 2), "tile_compact: whole waves, one or two streams");
+  const int64_t stop = min(base + (int64_t)TILE, end);
+  const auto step = [&](int64_t c) {
+    const int64_t i = c + (threadIdx.x & 63);
+    const uint32_t m = i < stop ? (uint32_t)flags(i) : 0u;
+    S slots[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      uint64_t bal;
+      slots[k] = run[k] + (S)compact_rank((m >> k) & 1u, bal);
+      run[k] += (S)__popcll(bal);
+    }
+    if (m & ((1u << K) - 1u)) emit(i, m, slots);
+  };
+  if (stop - base == TILE) {  // a full tile has a constant trip count, as the fixed-step kernels had: the compiler unrolls a small step
+    for (int s = 0; s < TILE / 64; ++s) step(base + s * 64);
+  } else {
+    for (int64_t c = base; c < stop; c += 64) step(c);
+  }
 }
 
 // ---- minima and maxima of integers (for floats: of their order-preserving keys).  Order-free: every tree gives the same value.

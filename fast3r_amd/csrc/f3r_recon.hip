@@ -49,11 +49,10 @@ __global__ void bbox_kernel(const float* __restrict__ p, int64_t m, uint32_t* __
       mn[a] = min(mn[a], k);
       mx[a] = max(mx[a], k);
     }
-  for (int a = 0; a < 3; ++a)
-    for (int off = 32; off > 0; off >>= 1) {
-      mn[a] = min(mn[a], (uint32_t)__shfl_xor((int)mn[a], off, 64));
-      mx[a] = max(mx[a], (uint32_t)__shfl_xor((int)mx[a], off, 64));
-    }
+  for (int a = 0; a < 3; ++a) {
+    mn[a] = wave_min(mn[a]);
+    mx[a] = wave_max(mx[a]);
+  }
   if ((threadIdx.x & 63) == 0)
     for (int a = 0; a < 3; ++a) {
       atomicMin(&bb[a], mn[a]);
@@ -326,8 +325,11 @@ __global__ __launch_bounds__(PNT) void recon_thr_kernel(const float* __restrict_
   }
 }
 
-// masks of pixel g: bit 0 = pred / ICP-GT (valid & conf >= thr_metric), bit 1 = metrics GT (valid), bit 2 = ICP weight (conf >= thr_icp)
-__device__ __forceinline__ uint32_t pix_mask(const float* conf, const uint8_t* valid, const float* thr, int s, int64_t g) {
+// masks of pixel g of sample i: bit 0 = pred / ICP-GT (valid & conf >= thr_metric), bit 1 = metrics GT (valid), bit 2 = ICP weight
+// (conf >= thr_icp); the thresholds are those of the view whose segment holds g
+__device__ __forceinline__ uint32_t pix_mask(const float* conf, const uint8_t* valid, const int64_t* seg, const float* thr, int i, int V,
+                                                int64_t g) {
+  const int s = last_le(seg, i * V, (i + 1) * V, g);
   const float c = conf[g];
   const bool v = valid[g] != 0;
   return (v && c >= thr[2 * s] ? 1u : 0u) | (v ? 2u : 0u) | (c >= thr[2 * s + 1] ? 4u : 0u);
@@ -336,19 +338,11 @@ __device__ __forceinline__ uint32_t pix_mask(const float* conf, const uint8_t* v
 __global__ __launch_bounds__(64) void recon_count_kernel(const float* __restrict__ conf, const uint8_t* __restrict__ valid, const int64_t* __restrict__ seg,
                                                          const float* __restrict__ thr, int V, int64_t L, int64_t ntiles, uint32_t* __restrict__ cnt) {
   const int i = blockIdx.y;
-  const int64_t base = (int64_t)blockIdx.x * TILE, end = min(base + TILE, L);
-  uint32_t a = 0, b = 0;
-  for (int64_t p = base + threadIdx.x; p < end; p += 64) {
-    const int64_t g = (int64_t)i * L + p;
-    const uint32_t mk = pix_mask(conf, valid, thr, last_le(seg, i * V, (i + 1) * V, g), g);
-    a += mk & 1u;
-    b += (mk >> 1) & 1u;
-  }
-  a = wave_sum(a);
-  b = wave_sum(b);
+  uint32_t n[2];
+  tile_count<TILE>((int64_t)blockIdx.x * TILE, L, [&](int64_t p) { return pix_mask(conf, valid, seg, thr, i, V, (int64_t)i * L + p); }, n);
   if (threadIdx.x == 0) {
-    cnt[(int64_t)i * ntiles + blockIdx.x] = a;
-    cnt[((int64_t)gridDim.y + i) * ntiles + blockIdx.x] = b;
+    cnt[(int64_t)i * ntiles + blockIdx.x] = n[0];
+    cnt[((int64_t)gridDim.y + i) * ntiles + blockIdx.x] = n[1];
   }
 }
 
@@ -358,29 +352,24 @@ __global__ __launch_bounds__(64) void recon_compact_kernel(const float* __restri
                                                            int V, int64_t L, int64_t ntiles, const uint32_t* __restrict__ cnt, float* __restrict__ pred_c,
                                                            float* __restrict__ gticp_c, uint8_t* __restrict__ w_c, float* __restrict__ gt_c) {
   const int i = blockIdx.y;
-  const int64_t base = (int64_t)blockIdx.x * TILE, end = min(base + TILE, L);
-  uint32_t ra = cnt[(int64_t)i * ntiles + blockIdx.x], rb = cnt[((int64_t)gridDim.y + i) * ntiles + blockIdx.x];
-  for (int64_t c = base; c < end; c += 64) {
-    const int64_t p = c + threadIdx.x;
-    const int64_t g = (int64_t)i * L + p;
-    const uint32_t mk = p < end ? pix_mask(conf, valid, thr, last_le(seg, i * V, (i + 1) * V, g), g) : 0u;
-    uint64_t ba, bb;
-    const uint32_t ka = compact_rank(mk & 1u, ba), kb = compact_rank(mk & 2u, bb);
-    if (mk & 1u) {
-      const int64_t o = (int64_t)i * L + ra + ka;
-      for (int a = 0; a < 3; ++a) {
-        pred_c[o * 3 + a] = pred[g * 3 + a];
-        gticp_c[o * 3 + a] = gt[g * 3 + a];
-      }
-      w_c[o] = (mk & 4u) ? 1 : 0;
-    }
-    if (mk & 2u) {
-      const int64_t o = (int64_t)i * L + rb + kb;
-      for (int a = 0; a < 3; ++a) gt_c[o * 3 + a] = gt[g * 3 + a];
-    }
-    ra += (uint32_t)__popcll(ba);
-    rb += (uint32_t)__popcll(bb);
-  }
+  uint32_t run[2] = {cnt[(int64_t)i * ntiles + blockIdx.x], cnt[((int64_t)gridDim.y + i) * ntiles + blockIdx.x]};
+  tile_compact<TILE>(
+      (int64_t)blockIdx.x * TILE, L, run, [&](int64_t p) { return pix_mask(conf, valid, seg, thr, i, V, (int64_t)i * L + p); },
+      [&](int64_t p, uint32_t mk, const uint32_t(&k)[2]) {
+        const int64_t g = (int64_t)i * L + p;
+        if (mk & 1u) {
+          const int64_t o = (int64_t)i * L + k[0];
+          for (int a = 0; a < 3; ++a) {
+            pred_c[o * 3 + a] = pred[g * 3 + a];
+            gticp_c[o * 3 + a] = gt[g * 3 + a];
+          }
+          w_c[o] = (mk & 4u) ? 1 : 0;
+        }
+        if (mk & 2u) {
+          const int64_t o = (int64_t)i * L + k[1];
+          for (int a = 0; a < 3; ++a) gt_c[o * 3 + a] = gt[g * 3 + a];
+        }
+      });
 }
 
 // weighted (0/1) Umeyama over the kept points of sample blockIdx.x: fp64 raw moments of the weight-1 pairs, then the align solve

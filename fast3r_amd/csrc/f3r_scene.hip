@@ -54,9 +54,6 @@ __device__ __forceinline__ uint32_t conf_key(float c) {
 }
 __device__ __forceinline__ float conf_of_key(uint32_t k) { return fkey_inv(~k); }
 
-// the segment that owns this workgroup's tile: ts[s] <= blockIdx.x < ts[s + 1] (every segment has at least one tile)
-__device__ __forceinline__ int find_seg(const int64_t* __restrict__ ts, int S) { return last_le(ts, 0, S, blockIdx.x); }
-
 // stats[seg * 4 + {0: smallest key = largest conf, 1: largest non-NaN key = smallest conf, 2: NaN count, 3: count of mask > 0}]
 __global__ void scene_stats_init_kernel(uint32_t* __restrict__ stats, int S) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -69,7 +66,7 @@ __global__ __launch_bounds__(SCENE_NT) void scene_hist_kernel(const SegRow* __re
                                                               uint32_t* __restrict__ stats, u32x4* __restrict__ recs) {
   __shared__ uint32_t cnt[256];
   __shared__ uint32_t red[4];
-  const int seg = find_seg(ts, S);
+  const int seg = last_le(ts, 0, S, blockIdx.x);  // the segment that owns this tile (every segment has at least one)
   const SegRow r = rows[seg];
   const int64_t t = blockIdx.x - ts[seg], nt = ts[seg + 1] - ts[seg];
   const int64_t base = t * SCENE_TILE, end = min(base + (int64_t)SCENE_TILE, r.len);
@@ -97,7 +94,7 @@ __global__ __launch_bounds__(SCENE_NT) void scene_hist_kernel(const SegRow* __re
       rec[2] = __builtin_bit_cast(uint32_t, p3[2]);
       uint32_t pk = (uint32_t)(uint8_t)mk << 24;
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) pk |= (uint32_t)sat_u8((r.img[(int64_t)ch * r.len + i] + 1.0f) * 127.5f) << (8 * ch);
+      for (int ch = 0; ch < 3; ++ch) pk |= (uint32_t)colour_u8(r.img[(int64_t)ch * r.len + i]) << (8 * ch);
       rec[3] = pk;
       recs[r.off + i] = rec;
     } else {
@@ -131,7 +128,7 @@ __global__ __launch_bounds__(SCENE_NT) void scene_scatter_kernel(const SegRow* _
   __shared__ uint32_t cnt[4][256];
   __shared__ uint32_t lbase[256], gbase[256], wsum[4];
   __shared__ uint8_t slut[FINAL ? 768 : 4];
-  const int seg = find_seg(ts, S);
+  const int seg = last_le(ts, 0, S, blockIdx.x);  // the segment that owns this tile (every segment has at least one)
   const SegRow r = rows[seg];
   const int64_t t = blockIdx.x - ts[seg], nt = ts[seg + 1] - ts[seg];
   const int64_t base = t * SCENE_TILE, end = min(base + (int64_t)SCENE_TILE, r.len);
@@ -331,37 +328,35 @@ struct ColRow {  // 5 x 8 bytes
 
 __global__ __launch_bounds__(64) void collect_count_kernel(const ColRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                            uint32_t* __restrict__ counts) {
-  const int seg = find_seg(ts, S);
+  const int seg = last_le(ts, 0, S, blockIdx.x);  // the segment that owns this tile (every segment has at least one)
   const ColRow r = rows[seg];
-  const int64_t base = (blockIdx.x - ts[seg]) * COL_TILE, end = min(base + (int64_t)COL_TILE, r.num);
-  uint32_t c = 0;
-  for (int64_t i = base + threadIdx.x; i < end; i += 64) c += r.mask ? (r.mask[i] > 0 ? 1u : 0u) : 1u;
-  c = wave_sum(c);
-  if (threadIdx.x == 0) counts[blockIdx.x] = c;
+  uint32_t c[1];
+  tile_count<COL_TILE>((blockIdx.x - ts[seg]) * COL_TILE, r.num, [&](int64_t i) { return !r.mask || r.mask[i] > 0; }, c);
+  if (threadIdx.x == 0) counts[blockIdx.x] = c[0];
 }
 
 __global__ __launch_bounds__(64) void collect_write_kernel(const ColRow* __restrict__ rows, const int64_t* __restrict__ ts, int S,
                                                            const uint32_t* __restrict__ scan, float* __restrict__ out_pts,
                                                            uint8_t* __restrict__ out_col) {
-  const int seg = find_seg(ts, S);
+  const int seg = last_le(ts, 0, S, blockIdx.x);  // the segment that owns this tile (every segment has at least one)
   const ColRow r = rows[seg];
-  const int64_t base = (blockIdx.x - ts[seg]) * COL_TILE, end = min(base + (int64_t)COL_TILE, r.num);
-  int64_t run = scan[blockIdx.x];
-  for (int64_t c0 = base; c0 < end; c0 += 64) {
-    const int64_t i = c0 + threadIdx.x;
-    const bool keep = i < end && (r.mask ? r.mask[i] > 0 : true);
-    uint64_t bal;
-    const uint32_t rank = compact_rank(keep, bal);
-    if (keep) {
-      const int64_t q = run + rank;
-      out_pts[q * 3 + 0] = r.pts[i * 3 + 0];
-      out_pts[q * 3 + 1] = r.pts[i * 3 + 1];
-      out_pts[q * 3 + 2] = r.pts[i * 3 + 2];
+  int64_t run[1] = {scan[blockIdx.x]};
+  tile_compact<COL_TILE>(
+      (blockIdx.x - ts[seg]) * COL_TILE, r.num, run, [&](int64_t i) { return !r.mask || r.mask[i] > 0; },
+      [&](int64_t i, uint32_t, const int64_t(&q)[1]) {
+        float p[3];  // every load before the first store: the compiler cannot tell that the outputs do not overlap the inputs
+        uint8_t c[3];
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) out_col[q * 3 + ch] = r.col ? r.col[i * 3 + ch] : (uint8_t)((r.const_col >> (8 * ch)) & 255);
-    }
-    run += __popcll(bal);
-  }
+        for (int ch = 0; ch < 3; ++ch) {
+          p[ch] = r.pts[i * 3 + ch];
+          c[ch] = r.col ? r.col[i * 3 + ch] : (uint8_t)((r.const_col >> (8 * ch)) & 255);
+        }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          out_pts[q[0] * 3 + ch] = p[ch];
+          out_col[q[0] * 3 + ch] = c[ch];
+        }
+      });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

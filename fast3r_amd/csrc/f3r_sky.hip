@@ -60,7 +60,7 @@ __constant__ HsvTab kHsvTab = make_hsv_tab();
 
 // steps 1-3 for one pixel: is it sky-coloured?
 __device__ __forceinline__ bool sky_colour(float fr, float fg, float fb, bool in_upper, const int32_t* sdiv, const int32_t* hdiv) {
-  const int r = sat_u8((fr + 1.0f) * 127.5f), g = sat_u8((fg + 1.0f) * 127.5f), b = sat_u8((fb + 1.0f) * 127.5f);
+  const int r = colour_u8(fr), g = colour_u8(fg), b = colour_u8(fb);
   const int v = max(r, max(g, b)), mn = min(r, min(g, b)), d = v - mn;
   const int s = (d * sdiv[v] + 2048) >> 12;
   const int h0 = v == r ? g - b : (v == g ? b - r + 2 * d : r - g + 4 * d);

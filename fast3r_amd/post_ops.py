@@ -350,40 +350,41 @@ def mesh_index_id(index_dtype):
     raise ValueError(f"mesh: index_dtype must be torch.int32 or torch.int64, got {index_dtype}")
 
 
-def mesh_build(conf, pts, img, mask, shapes, ranks, *, double_sided=True, drop_unreferenced=False, flip_axes=False, index_dtype=torch.int64):
-    """The triangle mesh of a list of views in one pass (f3r_mesh_threshold / _count / _write, include/f3r.h).  Lists over views of GPU
-    tensors: conf (H W,) fp32 or None (validity is the mask alone), pts (H W, 3) fp32, img (3, H W) fp32 planes or (H W, 3) uint8 colours,
-    mask (H W,) uint8 or None; shapes[i] = (H, W); ranks[i] = (k_lo, k_hi, gamma) as scene.percentile_indexes gives them (ignored without
-    conf).  -> dict(vertices (Nv, 3) fp32, faces (F, 3) index_dtype, face_colors (F, 3) uint8 on the device; thresholds (V,) fp32 and
-    nan_counts (V,) numpy, or None without any conf; counts (V, 3) int64 numpy: kept A, kept B, vertices per view).  The host reads back
-    the per-view counts once, between the count and the write."""
+def _view_count(who, conf, pts, img, mask, shapes, ranks):
     V = len(pts)
     if V < 1 or not (len(conf) == len(img) == len(mask) == len(shapes) == len(ranks) == V):
-        raise ValueError("mesh_build: need one conf, pts, img, mask, shape and rank entry per view, and at least one view")
-    idx_id = mesh_index_id(index_dtype)
+        raise ValueError(f"{who}: need one conf, pts, img, mask, shape and rank entry per view, and at least one view")
+    return V
+
+
+def _view_rows(who, conf, pts, img, mask, shapes, ranks, pixel_bits=None):
+    """The per-view checks of mesh_build and cloud_combine (who: the caller's name for the messages) and the rows of their device table
+    (ViewRow, csrc/f3r_view_row.h), after _view_count.  pixel_bits: a view must have fewer than 2^pixel_bits pixels.  -> (rows, pixels
+    per view, the contiguous tensors the rows point into, the total number of pixels)"""
+    V = len(pts)
     dev = pts[0].device
     f32, u8 = torch.float32, torch.uint8
-    rows, hw, pix, quads, keep, vbase = [], [], [], [], [], 0
+    rows, pix, keep, vbase = [], [], [], 0
     for i in range(V):
         H, W = int(shapes[i][0]), int(shapes[i][1])
-        if H < 1 or W < 1:
-            raise ValueError(f"mesh_build: view {i} is {H} x {W}; need H, W >= 1")
+        if H < 1 or W < 1 or (pixel_bits and H * W >= 2 ** pixel_bits):
+            raise ValueError(f"{who}: view {i} is {H} x {W}; need H, W >= 1" + (f" and H * W < 2^{pixel_bits}" if pixel_bits else ""))
         n = H * W
         c, p, g, m = conf[i], pts[i], img[i], mask[i]
         for t in (c, p, g, m):
             if t is not None:
                 require_gpu(t, f"view {i}")
                 if t.device != dev:
-                    raise ValueError(f"mesh_build: view {i}: tensors on {t.device} and {dev}")
+                    raise ValueError(f"{who}: view {i}: tensors on {t.device} and {dev}")
         if p.dtype != f32 or tuple(p.shape) != (n, 3):
-            raise ValueError(f"mesh_build: view {i}: pts must be ({n}, 3) fp32, got {tuple(p.shape)} {p.dtype}")
+            raise ValueError(f"{who}: view {i}: pts must be ({n}, 3) fp32, got {tuple(p.shape)} {p.dtype}")
         if c is not None and (c.dtype != f32 or tuple(c.shape) != (n,)):
-            raise ValueError(f"mesh_build: view {i}: conf must be ({n},) fp32, got {tuple(c.shape)} {c.dtype}")
+            raise ValueError(f"{who}: view {i}: conf must be ({n},) fp32, got {tuple(c.shape)} {c.dtype}")
         img_u8 = g.dtype == u8
         if not ((img_u8 and tuple(g.shape) == (n, 3)) or (g.dtype == f32 and tuple(g.shape) == (3, n))):
-            raise ValueError(f"mesh_build: view {i}: img must be (3, {n}) fp32 planes or ({n}, 3) uint8, got {tuple(g.shape)} {g.dtype}")
+            raise ValueError(f"{who}: view {i}: img must be (3, {n}) fp32 planes or ({n}, 3) uint8, got {tuple(g.shape)} {g.dtype}")
         if m is not None and (m.dtype != u8 or tuple(m.shape) != (n,)):
-            raise ValueError(f"mesh_build: view {i}: mask must be ({n},) uint8, got {tuple(m.shape)} {m.dtype}")
+            raise ValueError(f"{who}: view {i}: mask must be ({n},) uint8, got {tuple(m.shape)} {m.dtype}")
         c = None if c is None else c.contiguous()
         m = None if m is None else m.contiguous()
         p, g = p.contiguous(), g.contiguous()
@@ -392,11 +393,25 @@ def mesh_build(conf, pts, img, mask, shapes, ranks, *, double_sided=True, drop_u
         gamma_bits = int(np.asarray(gamma, dtype=np.float32).reshape(1).view(np.uint32)[0])
         rows.append([0 if c is None else c.data_ptr(), p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), H, W, vbase,
                      int(img_u8), int(k_lo), int(k_hi), gamma_bits, 0])
-        hw += [H, W]
         pix.append(n)
-        quads.append((H - 1) * (W - 1))
         vbase += n
-    total = vbase
+    return rows, pix, keep, vbase
+
+
+def mesh_build(conf, pts, img, mask, shapes, ranks, *, double_sided=True, drop_unreferenced=False, flip_axes=False, index_dtype=torch.int64):
+    """The triangle mesh of a list of views in one pass (f3r_mesh_threshold / _count / _write, include/f3r.h).  Lists over views of GPU
+    tensors: conf (H W,) fp32 or None (validity is the mask alone), pts (H W, 3) fp32, img (3, H W) fp32 planes or (H W, 3) uint8 colours,
+    mask (H W,) uint8 or None; shapes[i] = (H, W); ranks[i] = (k_lo, k_hi, gamma) as scene.percentile_indexes gives them (ignored without
+    conf).  -> dict(vertices (Nv, 3) fp32, faces (F, 3) index_dtype, face_colors (F, 3) uint8 on the device; thresholds (V,) fp32 and
+    nan_counts (V,) numpy, or None without any conf; counts (V, 3) int64 numpy: kept A, kept B, vertices per view).  The host reads back
+    the per-view counts once, between the count and the write."""
+    V = _view_count("mesh_build", conf, pts, img, mask, shapes, ranks)
+    idx_id = mesh_index_id(index_dtype)
+    rows, pix, keep, total = _view_rows("mesh_build", conf, pts, img, mask, shapes, ranks)
+    dev = pts[0].device
+    f32, u8 = torch.float32, torch.uint8
+    hw = [x for r in rows for x in r[4:6]]
+    quads = [(r[4] - 1) * (r[5] - 1) for r in rows]
     if total >= 2 ** 31:
         raise ValueError(f"mesh_build: {total} vertices; the indices are 32-bit: need fewer than 2^31 in all")
     tsv = tile_starts(pix, _lib.MESH_TILE)
@@ -464,43 +479,11 @@ def cloud_combine(conf, pts, img, mask, shapes, ranks, *, flip_axes=False, thres
     in view order then pixel order, or (None, None) when nothing is kept.  The host reads back one word: the total.  With return_offsets a
     third entry follows: the V end offsets of the views in the cloud (ascending Python ints, read from the tile scan: V words read back
     instead of one)."""
-    V = len(pts)
-    if V < 1 or not (len(conf) == len(img) == len(mask) == len(shapes) == len(ranks) == V):
-        raise ValueError("cloud_combine: need one conf, pts, img, mask, shape and rank entry per view, and at least one view")
+    V = _view_count("cloud_combine", conf, pts, img, mask, shapes, ranks)
     count, write = _lib.entry("f3r_cloud_combine_count"), _lib.entry("f3r_cloud_combine_write")
+    rows, pix, keep, _ = _view_rows("cloud_combine", conf, pts, img, mask, shapes, ranks, pixel_bits=31)
     dev = pts[0].device
     f32, u8 = torch.float32, torch.uint8
-    rows, pix, keep, vbase = [], [], [], 0
-    for i in range(V):
-        H, W = int(shapes[i][0]), int(shapes[i][1])
-        if H < 1 or W < 1 or H * W >= 2 ** 31:
-            raise ValueError(f"cloud_combine: view {i} is {H} x {W}; need H, W >= 1 and H * W < 2^31")
-        n = H * W
-        c, p, g, m = conf[i], pts[i], img[i], mask[i]
-        for t in (c, p, g, m):
-            if t is not None:
-                require_gpu(t, f"view {i}")
-                if t.device != dev:
-                    raise ValueError(f"cloud_combine: view {i}: tensors on {t.device} and {dev}")
-        if p.dtype != f32 or tuple(p.shape) != (n, 3):
-            raise ValueError(f"cloud_combine: view {i}: pts must be ({n}, 3) fp32, got {tuple(p.shape)} {p.dtype}")
-        if c is not None and (c.dtype != f32 or tuple(c.shape) != (n,)):
-            raise ValueError(f"cloud_combine: view {i}: conf must be ({n},) fp32, got {tuple(c.shape)} {c.dtype}")
-        img_u8 = g.dtype == u8
-        if not ((img_u8 and tuple(g.shape) == (n, 3)) or (g.dtype == f32 and tuple(g.shape) == (3, n))):
-            raise ValueError(f"cloud_combine: view {i}: img must be (3, {n}) fp32 planes or ({n}, 3) uint8, got {tuple(g.shape)} {g.dtype}")
-        if m is not None and (m.dtype != u8 or tuple(m.shape) != (n,)):
-            raise ValueError(f"cloud_combine: view {i}: mask must be ({n},) uint8, got {tuple(m.shape)} {m.dtype}")
-        c = None if c is None else c.contiguous()
-        m = None if m is None else m.contiguous()
-        p, g = p.contiguous(), g.contiguous()
-        keep += [c, p, g, m]
-        k_lo, k_hi, gamma = (0, 0, 0.0) if c is None else ranks[i]
-        gamma_bits = int(np.asarray(gamma, dtype=np.float32).reshape(1).view(np.uint32)[0])
-        rows.append([0 if c is None else c.data_ptr(), p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), H, W, vbase,
-                     int(img_u8), int(k_lo), int(k_hi), gamma_bits, 0])
-        pix.append(n)
-        vbase += n
     starts = tile_starts(pix, _lib.CLOUD_TILE)
     n_tiles = starts[-1]
     if n_tiles >= 2 ** 31:
@@ -537,11 +520,12 @@ def cloud_combine(conf, pts, img, mask, shapes, ranks, *, flip_axes=False, thres
     return (out_p, out_c, ends) if return_offsets else (out_p, out_c)
 
 
-def _cloud_points(points, who, colors=None):
+def _cloud_points(points, who, colors=None, bits=31):
+    """the (n, 3) fp32 cloud and its optional (n, 3) uint8 colours, contiguous, and n < 2^bits (31: the exporters, 32: the renderer)"""
     require_gpu(points, "points")
     n = points.shape[0] if points.dim() == 2 else -1
-    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or not 1 <= n < 2 ** 31:
-        raise ValueError(f"{who}: points must be (1 <= n < 2^31, 3) fp32, got {tuple(points.shape)} {points.dtype}")
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or not 1 <= n < 2 ** bits:
+        raise ValueError(f"{who}: points must be (1 <= n < 2^{bits}, 3) fp32, got {tuple(points.shape)} {points.dtype}")
     if colors is not None:
         require_gpu(colors, "colors")
         if tuple(colors.shape) != (n, 3) or colors.dtype != torch.uint8 or colors.device != points.device:
@@ -694,17 +678,25 @@ def _render_viewport(width, height, who):
     return width, height
 
 
-def _render_cloud(points, who, colors=None):
-    require_gpu(points, "points")
-    n = points.shape[0] if points.dim() == 2 else -1
-    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32 or not 1 <= n < 2 ** 32:
-        raise ValueError(f"{who}: points must be (1 <= n < 2^32, 3) fp32, got {tuple(points.shape)} {points.dtype}")
-    if colors is not None:
-        require_gpu(colors, "colors")
-        if tuple(colors.shape) != (n, 3) or colors.dtype != torch.uint8 or colors.device != points.device:
-            raise ValueError(f"{who}: colors must be ({n}, 3) uint8 on {points.device}, got {tuple(colors.shape)} {colors.dtype} on {colors.device}")
-        colors = colors.contiguous()
-    return points.contiguous(), colors, n
+def _keys_ok(keys, device):
+    return keys.dim() == 2 and keys.dtype == torch.int64 and keys.is_contiguous() and keys.device == device
+
+
+def _render_keys(keys, device, who):
+    """`keys` as render_keys made it, on `device` -> (width, height)"""
+    if not _keys_ok(keys, device):
+        raise ValueError(f"{who}: keys must be a contiguous (height, width) int64 tensor on {device}, got {tuple(keys.shape)} "
+                         f"{keys.dtype} on {keys.device}")
+    height, width = keys.shape
+    return _render_viewport(width, height, who)
+
+
+def _camera(camera, who):
+    """the 17 doubles of include/f3r.h (V row-major, sx, sy, cx, cy, znear) as a C array"""
+    cam = [float(c) for c in camera]
+    if len(cam) != 17:
+        raise ValueError(f"{who}: camera must hold 17 numbers (V, sx, sy, cx, cy, znear), got {len(cam)}")
+    return (ctypes.c_double * 17)(*cam)
 
 
 def render_keys(width, height, device):
@@ -722,18 +714,12 @@ def render_splat(points, n0, n1, camera, point_size, keys):
     """Points [n0, n1) of the cloud (n, 3) fp32 go into `keys` (what render_keys returned; written in place) through `camera`, the 17
     doubles of include/f3r.h (V row-major, sx, sy, cx, cy, znear) (f3r_render_splat).  Calls accumulate."""
     fn = _lib.entry("f3r_render_splat")
-    points, _, n = _render_cloud(points, "render_splat")
+    points, _, n = _cloud_points(points, "render_splat", bits=32)
     require_gpu(keys, "keys")
-    if keys.dim() != 2 or keys.dtype != torch.int64 or not keys.is_contiguous() or keys.device != points.device:
-        raise ValueError(f"render_splat: keys must be a contiguous (height, width) int64 tensor on {points.device}, got {tuple(keys.shape)} "
-                         f"{keys.dtype} on {keys.device}")
-    height, width = keys.shape
-    _render_viewport(width, height, "render_splat")
-    cam = [float(c) for c in camera]
-    if len(cam) != 17:
-        raise ValueError(f"render_splat: camera must hold 17 numbers (V, sx, sy, cx, cy, znear), got {len(cam)}")
+    width, height = _render_keys(keys, points.device, "render_splat")
+    cam = _camera(camera, "render_splat")
     with torch.cuda.device(points.device):
-        check(fn(ptr(points), n, int(n0), int(n1), (ctypes.c_double * 17)(*cam), float(point_size), width, height, ptr(keys),
+        check(fn(ptr(points), n, int(n0), int(n1), cam, float(point_size), width, height, ptr(keys),
                  stream_ptr()), "f3r_render_splat")
 
 
@@ -744,7 +730,7 @@ def render_resolve(keys, colors, background=(255, 255, 255), *, return_depth=Fal
     require_gpu(keys, "keys")
     require_gpu(colors, "colors")
     n = colors.shape[0] if colors.dim() == 2 else -1
-    if (keys.dim() != 2 or keys.dtype != torch.int64 or not keys.is_contiguous() or colors.dim() != 2 or colors.shape[1] != 3
+    if (not _keys_ok(keys, keys.device) or colors.dim() != 2 or colors.shape[1] != 3
             or colors.dtype != torch.uint8 or colors.device != keys.device or not 1 <= n < 2 ** 32):
         raise ValueError(f"render_resolve: keys contiguous (height, width) int64 and colors (1 <= n < 2^32, 3) uint8 on one device, got "
                          f"{tuple(keys.shape)} {keys.dtype} on {keys.device}, {tuple(colors.shape)} {colors.dtype} on {colors.device}")
@@ -766,7 +752,7 @@ def render_center(points):
     """The mean of the cloud's coordinates as three Python floats: the fp64 sums of f3r_render_center (a fixed order: two runs give the same
     bits), each divided by n on the host.  One readback of three doubles."""
     fn = _lib.entry("f3r_render_center")
-    points, _, n = _render_cloud(points, "render_center")
+    points, _, n = _cloud_points(points, "render_center", bits=32)
     buf = torch.empty((_lib.RENDER_CENTER_PARTS + 1) * 3, dtype=torch.float64, device=points.device)
     with torch.cuda.device(points.device):
         check(fn(ptr(points), n, ptr(buf[3:]), ptr(buf), stream_ptr()), "f3r_render_center")
@@ -809,22 +795,16 @@ def raster_triangles(vertices, faces, camera, keys, *, f0=0, f1=None, index_base
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int32, torch.int64) or faces.device != vertices.device:
         raise ValueError(f"raster_triangles: faces must be (nf, 3) int32 or int64 on {vertices.device}, got {tuple(faces.shape)} {faces.dtype} "
                          f"on {faces.device}")
-    if keys.dim() != 2 or keys.dtype != torch.int64 or not keys.is_contiguous() or keys.device != vertices.device:
-        raise ValueError(f"raster_triangles: keys must be a contiguous (height, width) int64 tensor on {vertices.device}, got "
-                         f"{tuple(keys.shape)} {keys.dtype} on {keys.device}")
-    height, width = keys.shape
-    _render_viewport(width, height, "raster_triangles")
+    width, height = _render_keys(keys, vertices.device, "raster_triangles")
     nf = faces.shape[0]
     f1 = nf if f1 is None else int(f1)
-    cam = [float(c) for c in camera]
-    if len(cam) != 17:
-        raise ValueError(f"raster_triangles: camera must hold 17 numbers (V, sx, sy, cx, cy, znear), got {len(cam)}")
+    cam = _camera(camera, "raster_triangles")
     if nf == 0 and int(f0) == 0 and f1 == 0:
         return
     vertices, faces = vertices.contiguous(), faces.contiguous()
     ws, nbytes = raster_workspace(vertices.device, faces_per_launch)
     with torch.cuda.device(vertices.device):
-        check(fn(ptr(vertices), nv, ptr(faces), mesh_index_id(faces.dtype), nf, int(f0), f1, int(index_base), (ctypes.c_double * 17)(*cam),
+        check(fn(ptr(vertices), nv, ptr(faces), mesh_index_id(faces.dtype), nf, int(f0), f1, int(index_base), cam,
                  width, height, ptr(keys), ptr(ws), nbytes, int(faces_per_launch), stream_ptr()), "f3r_raster_triangles")
 
 
@@ -1232,12 +1212,18 @@ def clean_frame_id(frame):
     raise ValueError(f"clean_confidence: frame must be 'world' or 'camera', got {frame!r}")
 
 
-def clean_table(shapes, starts):
-    """the host table of f3r_clean_confidence: rows (H, W, first element) of the views, then the starts of the neighbour lists"""
+def _shape_rows(shapes):
+    """rows (H, W, first element) of views that lie one after another, and the total number of elements"""
     rows, off = [], 0
     for H, W in shapes:
         rows.append([int(H), int(W), off])
         off += int(H) * int(W)
+    return rows, off
+
+
+def clean_table(shapes, starts):
+    """the host table of f3r_clean_confidence: rows (H, W, first element) of the views, then the starts of the neighbour lists"""
+    rows, off = _shape_rows(shapes)
     return table_words(rows, [int(s) for s in starts]), off
 
 
@@ -1294,10 +1280,7 @@ def galign_tables(shapes, edges, maps, device=None):
     only).  Edges may share a map: only its address is stored.  -> dict with the host arrays (kept alive for the calls), their device copies
     and the maps themselves."""
     N, E = len(shapes), len(edges)
-    rows, off = [], 0
-    for H, W in shapes:
-        rows.append([int(H), int(W), off])
-        off += int(H) * int(W)
+    rows, off = _shape_rows(shapes)
     eh, eh_p = _host_i32([x for e in edges for x in e])
     lists = [[] for _ in range(N)]
     for o, v in enumerate(eh.tolist()):

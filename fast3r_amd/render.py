@@ -158,7 +158,7 @@ def render_points(points, colors, camera=None, *, width=1920, height=1080, point
     the call returns a generator of one frame per segment, frame i showing points [0, segments[i]) (a generator keeps memory bounded:
     1500 frames of 1080p are 9 GB).  return_depth: (picture, (height, width) fp32 eye distance, +inf where empty) instead of the picture.
     A point with a NaN or inf coordinate is not drawn; with camera=None it is a ValueError.  Inputs are never written."""
-    points, colors, n = post_ops._render_cloud(points, "render_points", colors)
+    points, colors, n = post_ops._cloud_points(points, "render_points", colors, bits=32)
     if colors is None:
         raise ValueError("render_points: colors must be an (n, 3) uint8 device tensor")
     if camera is None:

@@ -68,7 +68,7 @@ def render_mesh(mesh, camera=None, *, points=None, colors=None, point_size=5.0, 
     vertices, faces, face_colors = _mesh_parts(mesh, "render_mesh")
     n = 0
     if points is not None:
-        points, colors, n = post_ops._render_cloud(points, "render_mesh", colors)
+        points, colors, n = post_ops._cloud_points(points, "render_mesh", colors, bits=32)
         if colors is None:
             raise ValueError("render_mesh: points need colors, an (n, 3) uint8 device tensor")
     if n == 0 and faces.shape[0] == 0:

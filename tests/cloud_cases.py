@@ -1,5 +1,7 @@
 """Seeded recipes for the point-cloud export tests (tests/test_cloud.py, tests/test_cloud_gpu.py): everything is numpy, built from a
 RandomState, so the CPU self-checks and the GPU comparisons see the same inputs."""
+import functools
+
 import numpy as np
 
 import cloud_ref as R
@@ -67,12 +69,19 @@ def one_voxel(n=5000, seed=11):
     return (10.0 + 0.4 * rs.rand(n, 3)).astype(F32), rs.randint(0, 256, (n, 3)).astype(np.uint8), 1.0
 
 
-def own_voxels(seed=12):
-    """the 12 x 11 x 10 integer lattice, shuffled: with voxel size 1 every point is its own voxel"""
+def own_voxels(seed=12, n=None):
+    """the 12 x 11 x 10 integer lattice, shuffled (its first n points): with voxel size 1 every point is its own voxel"""
     rs = np.random.RandomState(seed)
     g = np.stack(np.meshgrid(np.arange(12), np.arange(11), np.arange(10), indexing="ij"), -1).reshape(-1, 3)
-    g = g[rs.permutation(len(g))]
+    g = g[rs.permutation(len(g))][:n]
     return g.astype(F32), rs.randint(0, 256, (len(g), 3)).astype(np.uint8), 1.0
+
+
+# as many voxels as points, around the T = 1024 heads of one tile of the head compaction
+assert T == 1024
+own_voxels_1023 = functools.partial(own_voxels, n=1023)
+own_voxels_1024 = functools.partial(own_voxels, n=1024)
+own_voxels_1025 = functools.partial(own_voxels, n=1025)
 
 
 def on_boundaries(seed=13, n=700):

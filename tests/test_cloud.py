@@ -97,13 +97,14 @@ def test_voxel_restatement_against_unique_grouping():
     assert np.abs(got_c.astype(np.int64) - np.floor(csum / cnt[:, None]).astype(np.int64)).max() <= 1
 
 
-@pytest.mark.parametrize("recipe", ["on_boundaries", "duplicates", "small_integers", "own_voxels"])
+@pytest.mark.parametrize("recipe", ["on_boundaries", "duplicates", "small_integers", "own_voxels", "own_voxels_1023", "own_voxels_1024",
+                                    "own_voxels_1025"])
 def test_vectorised_voxel_restatement_equals_the_point_loop(recipe):
     p, c, vs = getattr(C, recipe)()
     a, b = R.voxel_down_sample(p, c, vs), R.voxel_down_sample_loop(p, c, vs)
     for x, y in zip(a, b):
         assert x.dtype == y.dtype and x.tobytes() == y.tobytes()
-    if recipe == "own_voxels":
+    if recipe.startswith("own_voxels"):
         assert len(a[0]) == len(p) and (a[2] == 1).all()
 
 

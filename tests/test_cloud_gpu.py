@@ -106,7 +106,8 @@ def test_voxel_sizes_around_the_sort_tile(built_lib, n):
     assert ok
 
 
-@pytest.mark.parametrize("recipe", ["one_voxel", "own_voxels", "on_boundaries", "duplicates", "small_integers"])
+@pytest.mark.parametrize("recipe", ["one_voxel", "own_voxels", "on_boundaries", "duplicates", "small_integers", "own_voxels_1023", "own_voxels_1024",
+                                    "own_voxels_1025"])
 def test_voxel_recipes(built_lib, recipe):
     import fast3r_amd
     p, c, vs = getattr(C, recipe)()
@@ -114,7 +115,7 @@ def test_voxel_recipes(built_lib, recipe):
     assert ok, recipe
     if recipe == "one_voxel":
         assert want[2].tolist() == [5000] and out["passes"] == 0
-    if recipe == "own_voxels":
+    if recipe.startswith("own_voxels"):
         assert len(want[0]) == len(p) and same(out["colors"], want[1])
     gp, gc, gn = fast3r_amd.voxel_down_sample(dev(p), dev(c), vs)   # the public name returns the same three
     assert torch.equal(gp, out["points"]) and torch.equal(gc, out["colors"]) and torch.equal(gn, out["counts"])
